@@ -14,7 +14,13 @@ One "step" = one whole job by SURVEY.md 8(d)'s clock: reset accumulators -> for 
 the 2-bit packed reads from page-locked host memory -> sketch -> index (+ mid_occ) -> seed / klib-order sort
 / chain / coverage for every query -> rows (D2H).  What happens before the clock: FASTQ parse (here: the
 synthetic generator) and the host-side 2-bit packing that the parser thread does (reported as host_pack_s).
-`value` = target bases / step time.  `hbm_resident_value` leaves the H2D out (reads already packed in HBM).
+`value` = target bases / step time.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  `--full` adds everything else: one
+profiled step (per-kernel table, roofline of the dominant kernel, whose launches the timed steps then carry HIP events
+around), `hbm_resident_value` (the H2D left out: reads already packed in HBM), the north-star pass, the golden-row and
+table checks, the CPU baseline, the device-copy ceiling and the files-in / table-out call (`end_to_end`).
+`--dump-outputs DIR` writes the coverage table of the last timed step as float64 arrays (write_outputs).
 """
 import argparse
 import json
@@ -54,12 +60,25 @@ CONFIG_LABEL = {
 }
 
 
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, capped by the cgroup's CPU quota where there is one (os.cpu_count() is the
+    whole host's)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, -(-int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
 def cpu_baseline(cfg_name, F, Q, n_t, n_q):
     """The reference's own minimap2-coverage (oracle/_ref, kind "reference") or the C restatement
     (kind "port") on a bounded sample of the same workload, timed on this host's cores."""
     from longqc_amd import synth
     from tests import oracle_bind
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     n_t = min(n_t, len(F)); n_q = min(n_q, len(Q))
     sub_q = Q.subset(range(n_q))
     with tempfile.TemporaryDirectory() as d:
@@ -170,6 +189,47 @@ def table_properties(table_text, names, lengths):
             "max_coverage": round(float(np.max(cov)), 3) if cov else None, "problems": bad[:5]}
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+
+
+def coverage_arrays(table_text):
+    """The 9-column coverage table (minimap2-coverage.c:545-617) as float64 arrays.  rows: one per query in the queries' order, the
+    columns length, lambda, coverage, meanQ, divergence, lambda2 coverage (2, 3, 6-9; NaN where the table prints nan); regions /
+    mregions: (query, start, end) of every interval of columns 4 / 5."""
+    rows, regs, mregs = [], [], []
+    for i, l in enumerate(table_text.splitlines()):
+        f = l.split("\t")
+        rows.append([float(f[1]), float(f[2])] + [float(x) for x in f[5:9]])
+        for col, out in ((f[3], regs), (f[4], mregs)):
+            if col != "0":
+                out += [(i, float(a), float(b)) for a, b in (r.split("-") for r in col.split(","))]
+    return {"rows": np.array(rows, dtype=np.float64).reshape(-1, 6), "regions": np.array(regs, dtype=np.float64).reshape(-1, 3),
+            "mregions": np.array(mregs, dtype=np.float64).reshape(-1, 3)}
+
+
+def sdust_arrays(table_text):
+    """The sdust table (sdust.c:136-222) as float64 arrays.  rows: one per read in file order, the columns masked bases, length,
+    masked fraction, meanQ, QV7 count."""
+    rows = [[float(x) for x in l.split("\t")[1:6]] for l in table_text.splitlines()]
+    return {"rows": np.array(rows, dtype=np.float64).reshape(-1, 5)}
+
+
+def write_outputs(d, arrays):
+    """DIR/<name>.npy for every array.  Beyond DUMP_BYTES in all, every array keeps the same fraction of its rows, drawn with a fixed
+    seed (the same rows from run to run), and DIR/<name>_index.npy holds the row numbers kept."""
+    os.makedirs(d, exist_ok=True)
+    keep = 1.0
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        keep = DUMP_BYTES * 0.99 / sum(a.nbytes + 8 * a.shape[0] for a in arrays.values())     # (with the index arrays)
+    rng = np.random.default_rng(12345)
+    for name, a in sorted(arrays.items()):
+        if keep < 1.0:
+            idx = np.sort(rng.choice(a.shape[0], size=int(a.shape[0] * keep), replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def sdust_bench(args):
     """`bench.py --config sdust`: the low-complexity table of every read of configs[1] (50 000 synthetic ONT reads ~15 kb, 744 Mbases) --
     what lq_mask.py gets from the reference's `sdust` binary chunk by chunk (lq_mask.py:17-23,99-121; sdust.c:136-222).  A step is one call
@@ -204,9 +264,11 @@ def sdust_bench(args):
                                        "QV7 count per read" % (len(T), T.n_bases, base or "the temp dir"),
                            "clock": "one lqsdust_main call: FASTQ parse + H2D + k_sdust (one read per thread, sdust.c:70-134) + meanQ / QV7 + rows written; wall clock", "parallelism": "single GPU"},
                 "rows": table.count("\n"), "synth_gen_s": round(gen_s, 1)}
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, sdust_arrays(table))
         ref = os.path.join(os.path.dirname(oracle_bind.REF_BIN), "sdust")
-        if os.path.exists(ref) and not args.no_cpu_baseline:
-            cores = min(os.cpu_count() or 1, 64)
+        if args.full and os.path.exists(ref) and not args.no_cpu_baseline:
+            cores = min(usable_cpus(), 64)
             cuts = [len(T) * i // cores for i in range(cores + 1)]
             files = []
             for i in range(cores):
@@ -244,10 +306,15 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="target reads in the CPU baseline sample (~20-30 s of reference time)")
     ap.add_argument("--cache", default="", help="directory for the generated reads (re-used by later runs of the same config on this machine)")
     ap.add_argument("--index-size", default="", help="override the preset's -I (e.g. 2M: many index parts on a small input; tests)")
-    ap.add_argument("--workers", type=int, default=0, help="processes of the synthetic generator (0: one per core, at most 64)")
+    ap.add_argument("--workers", type=int, default=0, help="processes of the synthetic generator (0: one per usable core, at most 64)")
     ap.add_argument("--front-only", action="store_true", help="not the bench: upload + sketch + index of the first part alone, --steps times, nothing else on the device; "
                                                                 "prints the per-kernel HIP-event times of the build side undisturbed (development aid)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: profiled step and roofline, HBM-resident rerun, north-star pass, golden rows, "
+                                                        "table checks, CPU baseline, copy ceiling, end_to_end (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the coverage table of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == "sdust":
         return sdust_bench(args)
 
@@ -292,7 +359,7 @@ def main():
             if os.path.exists(cache + ".off.npy"):
                 F = synth.FlatReads(0, np.load(cache + ".flat.npy"), np.load(cache + ".off.npy"))
         if F is None:
-            F = synth.make_reads_flat(cfg, genome, workers=args.workers)         # every read of the config, flat ASCII
+            F = synth.make_reads_flat(cfg, genome, workers=args.workers or min(64, usable_cpus()))     # every read of the config, flat ASCII
             if cache and rank == 0:
                 os.makedirs(args.cache, exist_ok=True)
                 np.save(cache + ".flat.npy", F.flat); np.save(cache + ".off.tmp.npy", F.off); os.replace(cache + ".off.tmp.npy", cache + ".off.npy")
@@ -302,7 +369,7 @@ def main():
         # Every rank generates a contiguous 1/N of the reads to learn their lengths (a read's length is only known once its errors
         # are drawn), the lengths are all-gathered, the parts and every rank's shares of them follow from the lengths, and a rank
         # then generates exactly the reads of its shares (every read has its own RNG stream: synth._one_read).
-        wk = args.workers or max(1, min(64, (os.cpu_count() or 1) // world))
+        wk = args.workers or max(1, min(64, usable_cpus() // world))
         n = cfg.n_reads
         a0, b0 = n * rank // world, n * (rank + 1) // world
         mine = np.diff(synth.make_reads_flat(cfg, genome, n_reads=b0 - a0, read_offset=a0, workers=wk).off).astype(np.int64)
@@ -485,47 +552,49 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # one untimed step with HIP events around every launch (level 2: events only, nothing waits for them): the per-kernel
-    # table and the name of the dominant kernel; the timed steps then carry events around that kernel only
-    eng.set_profiling(2)
-    step()
-    all_st = [s for s in eng.stage_times() if s["name"].startswith("k_") or s["name"].startswith("index_") or s["name"].startswith("h2d_")]
-    kern = [s for s in all_st if not s["name"].startswith("h2d_")]
-    prof_stats = eng.map_stats()                                                  # (of the profiled step: the second pass's anchors)
-    # What bounds the step: the kernel -- or the group of kernels that together do one line of SURVEY 8d's byte table -- with the
-    # largest device time per step (HIP events around every launch of one untimed step).  Nothing is left out (round 5 left out the
-    # serial token walks and the build side, and reported the 4th-largest entry):
-    #   * "anchor sort, second pass": every kernel that reproduces klib's radix sort for the queries that own an observable tie
-    #     (records, histograms, two-bucket passes, checkpoint solvers, token walkers, scatters, children).  SURVEY's line: 32 B per
-    #     sorted anchor (read 16, write 16), A2 = the second pass's anchors.  Eight levels of an MSD sort behind one figure.
-    #   * "chain": k_run_list + k_chain + k_chain_wave, 16 B per anchor the chain stage reads (what the first pass wrote + A2);
-    #     SURVEY's 16 A' + 8 C for the chained anchors and the chains are not known per step and left out (a lower bound on bytes).
-    #   * every other kernel by its own algorithmic bytes (StageTimer).
-    SORT2 = ("k_sort_init", "k_rs_hist", "k_sort_two", "k_ck_", "k_sort_walk", "k_rs_scatter", "k_rs_children")
-    CHAIN = ("k_run_list", "k_chain")
-    A2 = float((prof_stats or {}).get("klib_anchors", 0))
-    groups = {}
-    def add(label, s, bytes_):
-        g = groups.setdefault(label, {"name": label, "members": [], "total_ms": 0.0, "launches": 0, "algo_bytes": 0.0})
-        g["members"].append(s["name"]); g["total_ms"] += s["total_ms"]; g["launches"] += s["launches"]; g["algo_bytes"] += bytes_
-    for s_ in kern:
-        if s_["name"].startswith(SORT2):
-            add("anchor sort, second pass (klib order: k_rs_*, k_sort_*, k_ck_*)", s_, 0.0)
-        elif s_["name"].startswith(CHAIN):
-            add("chain (k_run_list, k_chain, k_chain_wave)", s_, 0.0)
-        else:
-            add(s_["name"], s_, float(s_["algo_bytes"]))
-    for lab, g in groups.items():
-        if lab.startswith("anchor sort"):
-            g["algo_bytes"] = 32.0 * A2; g["byte_model"] = "32 B per second-pass anchor (SURVEY 8d 'anchor sort': 16 read + 16 written), A2 = %d" % int(A2)
-        elif lab.startswith("chain"):
-            g["algo_bytes"] = 16.0 * (float(written[0]) + A2); g["byte_model"] = "16 B per anchor the chain stage reads (first-pass survivors + second-pass anchors); chained anchors and chains not counted"
-    build_side = ("k_sketch", "k_mask", "index_", "k_mark", "k_fill", "k_table", "k_sort_keys", "k_head")
-    cand = [g for g in groups.values() if g["algo_bytes"] > 0]
-    dom_g = max(cand or list(groups.values()), key=lambda g: g["total_ms"]) if groups else None
-    dom_name = dom_g["name"] if dom_g else None
-    eng.set_profiling(0)
-    eng.set_profiling(2, only="|".join(dom_g["members"]) if dom_g else None)
+    all_st, groups, dom_g, dom_name = [], {}, None, None
+    if args.full:
+        # one untimed step with HIP events around every launch (level 2: events only, nothing waits for them): the per-kernel
+        # table and the name of the dominant kernel; the timed steps then carry events around that kernel only
+        eng.set_profiling(2)
+        step()
+        all_st = [s for s in eng.stage_times() if s["name"].startswith("k_") or s["name"].startswith("index_") or s["name"].startswith("h2d_")]
+        kern = [s for s in all_st if not s["name"].startswith("h2d_")]
+        prof_stats = eng.map_stats()                                                  # (of the profiled step: the second pass's anchors)
+        # What bounds the step: the kernel -- or the group of kernels that together do one line of SURVEY 8d's byte table -- with the
+        # largest device time per step (HIP events around every launch of one untimed step).  Nothing is left out (round 5 left out the
+        # serial token walks and the build side, and reported the 4th-largest entry):
+        #   * "anchor sort, second pass": every kernel that reproduces klib's radix sort for the queries that own an observable tie
+        #     (records, histograms, two-bucket passes, checkpoint solvers, token walkers, scatters, children).  SURVEY's line: 32 B per
+        #     sorted anchor (read 16, write 16), A2 = the second pass's anchors.  Eight levels of an MSD sort behind one figure.
+        #   * "chain": k_run_list + k_chain + k_chain_wave, 16 B per anchor the chain stage reads (what the first pass wrote + A2);
+        #     SURVEY's 16 A' + 8 C for the chained anchors and the chains are not known per step and left out (a lower bound on bytes).
+        #   * every other kernel by its own algorithmic bytes (StageTimer).
+        SORT2 = ("k_sort_init", "k_rs_hist", "k_sort_two", "k_ck_", "k_sort_walk", "k_rs_scatter", "k_rs_children")
+        CHAIN = ("k_run_list", "k_chain")
+        A2 = float((prof_stats or {}).get("klib_anchors", 0))
+        groups = {}
+        def add(label, s, bytes_):
+            g = groups.setdefault(label, {"name": label, "members": [], "total_ms": 0.0, "launches": 0, "algo_bytes": 0.0})
+            g["members"].append(s["name"]); g["total_ms"] += s["total_ms"]; g["launches"] += s["launches"]; g["algo_bytes"] += bytes_
+        for s_ in kern:
+            if s_["name"].startswith(SORT2):
+                add("anchor sort, second pass (klib order: k_rs_*, k_sort_*, k_ck_*)", s_, 0.0)
+            elif s_["name"].startswith(CHAIN):
+                add("chain (k_run_list, k_chain, k_chain_wave)", s_, 0.0)
+            else:
+                add(s_["name"], s_, float(s_["algo_bytes"]))
+        for lab, g in groups.items():
+            if lab.startswith("anchor sort"):
+                g["algo_bytes"] = 32.0 * A2; g["byte_model"] = "32 B per second-pass anchor (SURVEY 8d 'anchor sort': 16 read + 16 written), A2 = %d" % int(A2)
+            elif lab.startswith("chain"):
+                g["algo_bytes"] = 16.0 * (float(written[0]) + A2); g["byte_model"] = "16 B per anchor the chain stage reads (first-pass survivors + second-pass anchors); chained anchors and chains not counted"
+        build_side = ("k_sketch", "k_mask", "index_", "k_mark", "k_fill", "k_table", "k_sort_keys", "k_head")
+        cand = [g for g in groups.values() if g["algo_bytes"] > 0]
+        dom_g = max(cand or list(groups.values()), key=lambda g: g["total_ms"]) if groups else None
+        dom_name = dom_g["name"] if dom_g else None
+        eng.set_profiling(0)
+        eng.set_profiling(2, only="|".join(dom_g["members"]) if dom_g else None)
     dt = timed(args.steps)
     ms_per_step = dt / max(args.steps, 1) * 1e3
     value = total_bases / (ms_per_step / 1e3) / 1e6
@@ -554,15 +623,17 @@ def main():
         table = table[0] or ""
     else:
         table = eng.table_text()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, coverage_arrays(table))
     n_qm_counted = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             n_qm_counted = float(sum(r["n_mini"] for r in eng.rows()))          # the queries' minimizers, counted (the rows carry them)
         except Exception:
             n_qm_counted = None
     # the same job with the reads already resident in HBM (single-part workloads only: a multi-part job re-uses the part's buffers)
     resident = None
-    if len(parts) == 1 and world == 1:
+    if len(parts) == 1 and world == 1 and args.full:
         dt_r = timed(max(1, args.steps), h2d=False)
         resident = total_bases / (dt_r / max(1, args.steps)) / 1e6
 
@@ -570,7 +641,7 @@ def main():
     # every kernel alone on the device (profiling level 1: each launch waited for, lanes one after the other), so that the
     # times are the kernels' own and not what they stretch to beside the other streams
     north = None
-    if world == 1 and not args.no_north_star:
+    if world == 1 and args.full and not args.no_north_star:
         eng.set_profiling(0); eng.set_profiling(1)
         eng.reset(); build(0); eng.part_map(pts[0]); eng.sync()
         u = {x["name"]: x for x in eng.stage_times()}
@@ -688,16 +759,16 @@ def main():
                                        "the front of part i + 1 under the mapping of part i), rows gathered on rank 0" % (world, dist.get_world_size(), dist.get_backend())),
                        "scaling_model_s": None if world == 1 else {"queries_sharded": round(tq, 3), "parts_across_gpus": round(tp, 3), "single_gpu": round(multigpu.QueryShardRunner.scaling_model(1, part_bases), 3),
                                                                    "note": "predicted seconds per job from the single-GPU stage rates of round 4 (longqc_amd/multigpu.py); the faster split runs"}},
-            "roofline": roof, "north_star": north,
             "host_pack_s": round(t_pack, 3), "synth_gen_s": round(t_gen, 2),
             "value_incl_host_pack": round(total_bases / (ms_per_step / 1e3 + t_pack) / 1e6, 3),
-            "hbm_resident_value": round(resident, 3) if resident else None,
             "anchors_per_s": round(n_anchors / (ms_per_step / 1e3), 1),
         }
-        if full_config:
-            line["golden_rows"] = golden_check(args.config, table)
-        line["table_properties"] = table_properties(table, Q.names, [int(x.shape[0]) for x in Q.seqs])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update({"roofline": roof, "north_star": north, "hbm_resident_value": round(resident, 3) if resident else None})
+            if full_config:
+                line["golden_rows"] = golden_check(args.config, table)
+            line["table_properties"] = table_properties(table, Q.names, [int(x.shape[0]) for x in Q.seqs])
+        if world == 1 and args.full and not args.no_cpu_baseline:
             n_t = args.cpu_sample or {"cfg3": 25000, "cfg2": 35000, "cfg4": 15000, "cfg4s": 15000, "cfg5": 5000, "cfg5s": 5000}.get(args.config, 25000)
             line["cpu_baseline"] = cpu_baseline(args.config, F, Q, n_t, len(Q) if n_t >= len(F) else max(50, n_t // 100))
         if one_dev:
@@ -708,7 +779,7 @@ def main():
         if cc:
             line["roofline"]["measured_copy_ceiling"] = {"GB/s": cc, "frac_of_it": round(line["roofline"]["achieved"] / cc, 4),
                                                          "what": "bytes read + written per second of a 2-GiB device-to-device copy on this box, best of 5"}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if rank == 0 and world == 1 and args.full and not args.no_end_to_end:
         # The drop-in call as LongQC issues it (INTEGRATION.md level 1 / 2): files in, table out -- FASTA/Q parse (targets: plain
         # FASTA on tmpfs, parsed from the mapping by the host's cores; queries: FASTQ), 2-bit packing, upload, every part, rows,
         # formatting, with the parts in run_files' own pipeline.  SURVEY 8d: "once including it, to compare like-for-like with
@@ -767,12 +838,12 @@ def main():
             line["end_to_end"] = {"value": round(total_bases / best / 1e6, 3), "unit": "Mbases/s", "seconds": round(best, 3), "seconds_inside_the_call": call_s, "table_identical_to_timed_steps": same,
                                   "files": "targets: plain FASTA (%.1f GB) on %s, queries: FASTQ; best of 2 runs, device idle for 8 s before each" % (os.path.getsize(tf) / 1e9, base or "the temp dir"),
                                   "what": "the executable minimap2-coverage-mi355x as a subprocess, LongQC's argv: process start + HIP start-up + parse (mapped file, %d host threads) + 2-bit pack + H2D + sketch + index + map "
-                                          "of every part in run_files' pipeline + rows + table text; wall clock around the process" % min(64, os.cpu_count() or 1),
+                                          "of every part in run_files' pipeline + rows + table text; wall clock around the process" % min(64, usable_cpus()),
                                   "log_tail": log_tail, "file_write_s": round(t_write, 1)}
             if gz:
                 line["end_to_end"]["gz"] = gz
             # the reference on the same files, all reads and all queries, when the host has the cores for it (measured, not quoted)
-            cores = os.cpu_count() or 1
+            cores = usable_cpus()
             from tests import oracle_bind
             if cores >= 64 and oracle_bind.have_ref() and not args.no_cpu_baseline and line.get("cpu_baseline"):
                 t0 = time.time()

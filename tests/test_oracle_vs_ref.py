@@ -1,14 +1,14 @@
-"""Pins the oracle against the reference itself, live: runs oracle/_ref (the reference's own sources
-compiled by oracle/Makefile) on seeded synthetic sets and diffs tables and function-level dumps.
-Needs oracle/_ref, i.e. the build container (skipped where /root/reference was never available)."""
+"""Pins the oracle against the reference itself: runs oracle/_ref (the reference's own sources compiled by
+oracle/Makefile) on seeded synthetic sets and diffs tables and function-level dumps.  Where oracle/_ref is not
+built, what the reference printed for the same argv and input bytes stands in (tests/golden/ref_runs/, recorded
+by tests/golden/make_ref_runs.py; tests/oracle_bind.py)."""
+import json
 import os
 
 import pytest
 
 from tests import oracle_bind
-from tests.helpers import ONT
-
-pytestmark = pytest.mark.skipif(not oracle_bind.have_ref(), reason="oracle/_ref not built")
+from tests.helpers import GOLDEN, ONT
 
 VARIANTS = {
     "ont": ONT,
@@ -65,16 +65,10 @@ def test_klib_order_matters_stable_sort_is_not_exact(tmp_path):
 
 def test_q2p_table_regenerated_equals_reference_literals():
     """meanQ's lookup table is rebuilt numerically by the oracle and the product (10^(-q/10) to 15 decimals, eight
-    entries one unit higher); compare that description with the literals in the reference source (read as data)."""
-    import re
+    entries one unit higher); compare that description with the literals of the reference's table (lqutils.c), kept
+    as data in tests/golden/q2p_literals.json (tests/golden/make_q2p_golden.py)."""
     from decimal import Decimal
-    src = "/root/reference/minimap2-coverage/lqutils.c"
-    if not os.path.exists(src):
-        pytest.skip("reference sources not present")
-    txt = open(src).read()
-    block = txt[txt.rindex("double q2p[] = {"):]
-    block = block[:block.index("};")]
-    lits = re.findall(r"\d\.\d{15}", block)
+    lits = json.load(open(os.path.join(GOLDEN, "q2p_literals.json")))["literals"]
     assert len(lits) == 127
     up = {34, 39, 58, 62, 67, 71, 72, 82}
     for q, v in enumerate(lits):

@@ -42,13 +42,10 @@ def test_oracle_sdust_equals_the_reference_table(case, tmp_path):
 
 
 def test_oracle_sdust_vs_reference_binary_on_synthetic_reads(datasets):
-    ref = os.path.join(os.path.dirname(oracle_bind.REF_BIN), "sdust")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/sdust not built (needs /root/reference)")
     tf, _ = datasets("small")
     for extra in ([], ["-w", "20"], ["-t", "12"]):
-        a = subprocess.run([ref] + extra + [tf], stdout=subprocess.PIPE, check=True).stdout
-        b = subprocess.run([oracle_bind.ensure_oracle(), "sdust"] + extra + [tf], stdout=subprocess.PIPE, check=True).stdout
+        a = oracle_bind.ref_sdust(extra + [tf])
+        b = subprocess.run([oracle_bind.ensure_oracle(), "sdust"] + extra + [tf], stdout=subprocess.PIPE, check=True).stdout.decode()
         assert a == b
 
 

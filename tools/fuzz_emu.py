@@ -116,14 +116,14 @@ def run_one(seed: int, keep: str = "", verbose: bool = False) -> int:
         # it, or maps from the one the reference wrote; the reference's table from its own file is the same `want` (checked)
         via = seed % 3 if "-I" in argv or seed % 2 else 0
         if via:
-            import subprocess
             kw = [a for i, a in enumerate(argv) if a in ("-k", "-w", "-H", "-I") or (i and argv[i - 1] in ("-k", "-w", "-I"))]
             # (the mapping call keeps -k / -w / -H: the reference sizes its match counters from the command line's sketch,
             # minimap2-coverage.c:419-422, and writes past them when the index file's parameters yield more minimizers)
             rest = [a for i, a in enumerate(argv) if not (a == "-I" or (i and argv[i - 1] == "-I"))]
             mmi_ref, mmi_own = os.path.join(d, "ref.mmi"), os.path.join(d, "own.mmi")
-            r = subprocess.run([oracle_bind.REF_BIN] + kw + ["-d", mmi_ref, tf], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-            if r.returncode != 0:
+            try:
+                oracle_bind.ref_index(kw + ["-d", mmi_ref, tf], mmi_ref)
+            except RuntimeError:
                 return 2
             want2 = oracle_bind.ref_table(rest + [mmi_ref, qf])
             if want2 != want:                       # (the reference itself: mapping from its dump = mapping from the reads)

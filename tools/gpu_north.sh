@@ -1,14 +1,14 @@
 #!/bin/bash
 # bench with the north-star pass (every kernel alone on the device): step time + the seed / sketch kernels' own times
-#   VARIANTS="base|LQCOV_SEED_BUCKET=4096" CFG=cfg3 STEPS=2 bash tools/gpu_north.sh
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; : > gpurun_out/north.log
+#   VARIANTS="base|LQCOV_SEED_BUCKET=4096" CFG=cfg3 STEPS=2 bash tools/gpu_north.sh      (results in $OUT, default /tmp/lqcov_out)
+cd "$(dirname "$0")/.."; OUT=${OUT:-/tmp/lqcov_out}; mkdir -p $OUT; : > $OUT/north.log
 IFS='|' read -ra VS <<< "${VARIANTS:-base}"
 N=0
 for V in "${VS[@]}"; do
   E="$V"; [ "$V" = base ] && E=""
   N=$((N+1))
-  env $E timeout ${LIMIT:-400} python bench.py --config ${CFG:-cfg3} --steps ${STEPS:-2} --warmup 1 --no-cpu-baseline --no-end-to-end --cache /tmp/lqcov_cache 2>gpurun_out/north_err.log | tail -1 > gpurun_out/north_$N.json
-  python - "$V" gpurun_out/north_$N.json >> gpurun_out/north.log 2>&1 <<'PY'
+  env $E timeout ${LIMIT:-400} python bench.py --full --config ${CFG:-cfg3} --steps ${STEPS:-2} --warmup 1 --no-cpu-baseline --no-end-to-end --cache /tmp/lqcov_cache 2>$OUT/north_err.log | tail -1 > $OUT/north_$N.json
+  python - "$V" $OUT/north_$N.json "$OUT/north_err.log" >> $OUT/north.log 2>&1 <<'PY'
 import sys, json
 try:
     j = json.load(open(sys.argv[2]))
@@ -19,7 +19,7 @@ try:
         print("   sketch alone:", n["sketch"]["kernels"], n["sketch"]["ms"], "frac", n["sketch"]["frac_of_hbm_peak"], "combined", n["combined"]["frac_of_hbm_peak"])
     print("   one step:", {k: round(v) for k, v in list(j["roofline"]["kernel_ms_one_step"].items())[:18]})
 except Exception as e:
-    print("%-44s failed: %r" % (sys.argv[1], e)); print(open("gpurun_out/north_err.log").read()[-800:])
+    print("%-44s failed: %r" % (sys.argv[1], e)); print(open(sys.argv[3]).read()[-800:])
 PY
 done
-cat gpurun_out/north.log
+cat $OUT/north.log

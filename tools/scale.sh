@@ -8,7 +8,7 @@ NGPU=$(python -c "import torch; print(torch.cuda.device_count())")
 for N in 1 2 4 8; do
   [ "$N" -gt "$NGPU" ] && { echo "N=$N: skipped ($NGPU GPU(s) here)"; continue; }
   if [ "$N" = 1 ]; then L="python bench.py"; else L="python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py"; fi
-  HSA_ENABLE_IPC_MODE_LEGACY=0 $L --gpus $N --steps ${STEPS:-5} --warmup ${WARMUP:-2} --no-cpu-baseline --no-end-to-end --no-north-star ${CONFIG:+--config $CONFIG} --cache /tmp/lqcov_cache 2>/tmp/scale_$N.err | tail -1 | python -c "
+  HSA_ENABLE_IPC_MODE_LEGACY=0 $L --full --gpus $N --steps ${STEPS:-5} --warmup ${WARMUP:-2} --no-cpu-baseline --no-end-to-end --no-north-star ${CONFIG:+--config $CONFIG} --cache /tmp/lqcov_cache 2>/tmp/scale_$N.err | tail -1 | python -c "
 import sys, json
 try:
     j = json.loads(sys.stdin.read())
