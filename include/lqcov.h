@@ -109,6 +109,13 @@ int lqcov_run_files(lqcov_handle *h, const char *target_path, const char *query_
 int lqcov_run_files_ex(lqcov_handle *h, const char *target_path, const char *query_path, const char *dump_path,
                        const char *out_path, const char *err_path);
 
+/* lqcov_run_files for n_sets query files at once, set s mapped with -p med[s] / -q good[s] and its table written to out_paths[s]:
+ * the targets (plain, gzip or a prebuilt .mmi) are read, sketched and indexed once for all sets.  Each file is parsed as
+ * lqcov_run_files parses one; sets with qualities and sets without cannot be mixed (LQCOV_E_DOMAIN).  err_path gets the
+ * parameter echo and one line per set with its -p / -q.  No index dump. */
+int lqcov_run_files_sets(lqcov_handle *h, const char *target_path, uint32_t n_sets, const char *const *query_paths,
+                         const int32_t *med, const int32_t *good, const char *const *out_paths, const char *err_path);
+
 /* ---- level 2: handle ---------------------------------------------------------------------- */
 void lqcov_params_default(lqcov_params *p);                                /* minimap2-coverage.c:229-388 */
 /* parse the reference's option table; fills target/query with pointers into argv.   :166-197 */
@@ -129,6 +136,18 @@ int  lqcov_get_stage_times(lqcov_handle *h, lqcov_stage_time *out, int max_out);
  * == main pass 1 (minimap2-coverage.c:406-444) + mm_bseq_read2 (bseq.c:68-102).              */
 int lqcov_set_queries(lqcov_handle *h, uint32_t n, const uint8_t *seq, const uint64_t *seq_off,
                       const uint8_t *qual, const char *names, const uint64_t *name_off);
+
+/* Several query sets mapped in one pass over the targets, each with its own -p / -q (LongQC's `sampleqc --short` runs two calls
+ * that differ only in the query file and -p, longQC.py:438-445,527-543; its spike-in filter runs one per subsample,
+ * longQC.py:553-575).  The reads are those of lqcov_set_queries for the concatenation of the sets in set order: set s holds the
+ * queries set_first[s] .. set_first[s + 1] - 1 (set_first[0] == 0, set_first[n_sets] == n; a set may be empty) and is mapped with
+ * -p min_score_med[s], -q min_score_good[s], checked as the option parser checks one call (>= -m, -q >= -p, < 65536).  The
+ * 500-Mbase query mini-batch rule applies to each set.  Every other option is the handle's.  Each query is mapped on its own
+ * against a part, so every set's rows are those of a call of its own.  lqcov_set_queries is the case of one set. */
+int lqcov_set_query_sets(lqcov_handle *h, uint32_t n, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *qual,
+                         const char *names, const uint64_t *name_off, uint32_t n_sets, const uint32_t *set_first /* n_sets + 1 */,
+                         const int32_t *min_score_med, const int32_t *min_score_good);
+int lqcov_n_query_sets(const lqcov_handle *h);       /* 1 after lqcov_set_queries */
 
 /* Index parts == iterations of the loop at minimap2-coverage.c:449-458.  The caller decides the
  * part boundaries (lqcov_run_files applies the reference's rule, index.c:244,311-316). */
@@ -194,6 +213,9 @@ int lqcov_get_rows(lqcov_handle *h, lqcov_row *rows, uint32_t n_rows);
 int lqcov_get_regions(lqcov_handle *h, const lqcov_region **regs, uint32_t *n_regs, const lqcov_region **mregs, uint32_t *n_mregs);
 /* Text of the table, rows in query order (minimap2-coverage.c:567-605). names as in lqcov_set_queries. */
 int lqcov_write_table(lqcov_handle *h, const char *out_path);
+/* The rows of one query set, in that set's order: the table a call of its own would print (for two sets, lqcov_write_table is
+ * their concatenation, LongQC's merged_coverage_out.txt, longQC.py:527-543). */
+int lqcov_write_table_set(lqcov_handle *h, uint32_t set, const char *out_path);
 
 /* ---- parity / inspection ------------------------------------------------------------------ */
 int32_t  lqcov_mid_occ(const lqcov_handle *h);                             /* map.c:50 */

@@ -104,6 +104,12 @@ def load_library(path: Optional[str] = None):
         "lqcov_reserve_hbm": (C.c_int, [H, C.c_uint64]),
         "lqcov_format_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p]),
         "lqcov_write_table": (C.c_int, [H, C.c_char_p]),
+        "lqcov_set_query_sets": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "lqcov_n_query_sets": (C.c_int, [H]),
+        "lqcov_write_table_set": (C.c_int, [H, C.c_uint32, C.c_char_p]),
+        "lqcov_run_files_sets": (C.c_int, [H, C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_char_p), C.c_char_p]),
         "lqcov_run_files": (C.c_int, [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
         "lqcov_run_files_ex": (C.c_int, [H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]),
         "lqcov_part_dump": (C.c_int, [H, C.c_int, C.c_char_p, C.c_int]),
@@ -300,6 +306,34 @@ class Engine:
         self._ck(self.lib.lqcov_set_queries(self.h, len(seqs), flat.ctypes.data, off.ctypes.data,
                                             q.ctypes.data if q is not None else None, nb, noff.ctypes.data))
 
+    def set_query_sets(self, sets: Sequence[Tuple[Sequence[str], Sequence[np.ndarray], Optional[Sequence[np.ndarray]], int, int]]):
+        """Several query sets on one handle, each mapped with its own -p / -q: sets = [(names, seqs, quals or None, med, good), ...].
+        The tables of the sets are those of one call per set (table_text(set=s)); the other options are the handle's.
+        Sets with qualities and sets without cannot be mixed (the mean quality column is per call)."""
+        names, seqs, quals, first, med, good = [], [], [], [0], [], []
+        with_qual = None
+        for nm, sq, ql, m, g in sets:
+            if len(sq) != len(nm) or (ql is not None and len(ql) != len(sq)):
+                raise ValueError("names, sequences and qualities of a set must have the same length")
+            if len(sq):
+                if with_qual is not None and with_qual != (ql is not None):
+                    raise LqcovError(-5, "query sets with qualities mixed with sets without")
+                with_qual = ql is not None
+            names += list(nm); seqs += list(sq); quals += list(ql) if ql is not None else []
+            first.append(len(seqs)); med.append(int(m)); good.append(int(g))
+        flat, off = _flat(seqs)
+        nb, noff = _names(names)
+        q = _flat(quals)[0] if with_qual else None
+        first = np.asarray(first, dtype=np.uint32)
+        med, good = np.asarray(med, dtype=np.int32), np.asarray(good, dtype=np.int32)
+        self._ck(self.lib.lqcov_set_query_sets(self.h, len(seqs), flat.ctypes.data, off.ctypes.data,
+                                               q.ctypes.data if q is not None else None, nb, noff.ctypes.data,
+                                               len(sets), first.ctypes.data, med.ctypes.data, good.ctypes.data))
+
+    @property
+    def n_query_sets(self) -> int:
+        return self._ck(self.lib.lqcov_n_query_sets(self.h))
+
     def part_begin(self) -> int:
         return self._ck(self.lib.lqcov_part_begin(self.h))
 
@@ -364,6 +398,18 @@ class Engine:
         enc = lambda v: v.encode() if v else None
         self._ck(self.lib.lqcov_run_files_ex(self.h, target.encode(), enc(query), enc(dump), enc(out), enc(err)))
 
+    def run_files_sets(self, target: str, queries: Sequence[str], meds: Sequence[int], goods: Sequence[int], outs: Sequence[str],
+                       err: Optional[str] = None):
+        """one pass over `target` for every query file: queries[s] mapped with -p meds[s] / -q goods[s], its table in outs[s]"""
+        n = len(queries)
+        if not (len(meds) == len(goods) == len(outs) == n):
+            raise ValueError("one -p, one -q and one output per query file")
+        qa = (C.c_char_p * max(n, 1))(*[q.encode() for q in queries])
+        oa = (C.c_char_p * max(n, 1))(*[o.encode() for o in outs])
+        med, good = np.asarray(meds, dtype=np.int32), np.asarray(goods, dtype=np.int32)
+        self._ck(self.lib.lqcov_run_files_sets(self.h, target.encode(), n, qa, med.ctypes.data, good.ctypes.data, oa,
+                                               err.encode() if err else None))
+
     def part_dump(self, part: int, path: str, append: bool = False):
         self._ck(self.lib.lqcov_part_dump(self.h, part, path.encode(), 1 if append else 0))
 
@@ -408,13 +454,17 @@ class Engine:
         mregs = np.ctypeslib.as_array(C.cast(mp, C.POINTER(C.c_uint32)), shape=(nm.value, 2)).copy() if nm.value else np.zeros((0, 2), np.uint32)
         return rows, regs, mregs
 
-    def write_table(self, path: str):
-        self._ck(self.lib.lqcov_write_table(self.h, path.encode()))
+    def write_table(self, path: str, set: Optional[int] = None):
+        """every row in the caller's order; set: the rows of that query set only (lqcov_set_query_sets)"""
+        if set is None:
+            self._ck(self.lib.lqcov_write_table(self.h, path.encode()))
+        else:
+            self._ck(self.lib.lqcov_write_table_set(self.h, int(set), path.encode()))
 
-    def table_text(self) -> str:
+    def table_text(self, set: Optional[int] = None) -> str:
         import tempfile
         with tempfile.NamedTemporaryFile("r", suffix=".tsv") as f:
-            self.write_table(f.name)
+            self.write_table(f.name, set=set)
             return open(f.name).read()
 
     # -- inspection --

@@ -278,6 +278,22 @@ int lqcov_set_queries(lqcov_handle *h, uint32_t n, const uint8_t *seq, const uin
 	return guard(h, [&] { if (!seq_off || (n && !seq)) throw std::invalid_argument("null read buffers"); h->set_queries(n, seq, seq_off, qual, names, name_off); });
 }
 
+int lqcov_set_query_sets(lqcov_handle *h, uint32_t n, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *qual,
+                         const char *names, const uint64_t *name_off, uint32_t n_sets, const uint32_t *set_first,
+                         const int32_t *min_score_med, const int32_t *min_score_good)
+{
+	return guard(h, [&] {
+		if (!seq_off || (n && !seq)) throw std::invalid_argument("null read buffers");
+		h->set_query_sets(n, seq, seq_off, qual, names, name_off, n_sets, set_first, min_score_med, min_score_good);
+	});
+}
+
+int lqcov_n_query_sets(const lqcov_handle *h)
+{
+	if (!h) return LQCOV_E_ARG;
+	return h->have_queries ? (int)h->set_first.size() - 1 : 0;
+}
+
 int lqcov_part_begin(lqcov_handle *h)
 {
 	int id = -1;
@@ -420,6 +436,16 @@ int lqcov_write_table(lqcov_handle *h, const char *out_path)
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
 		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
 		try { h->write_table(o); } catch (...) { if (out_path) fclose(o); throw; }
+		if (out_path) fclose(o); else fflush(o);
+	});
+}
+
+int lqcov_write_table_set(lqcov_handle *h, uint32_t set, const char *out_path)
+{
+	return guard(h, [&] {
+		FILE *o = out_path ? fopen(out_path, "w") : stdout;
+		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
+		try { h->write_table_set(set, o); } catch (...) { if (out_path) fclose(o); throw; }
 		if (out_path) fclose(o); else fflush(o);
 	});
 }
@@ -735,6 +761,44 @@ int lqcov_run_files(lqcov_handle *h, const char *target, const char *query, cons
 	return lqcov_run_files_ex(h, target, query, nullptr, out_path, err_path);
 }
 
+// the effective parameters, as the reference echoes them (minimap2-coverage.c:392-404)
+static void echo_params(FILE *e, const lqcov_params &p, const char *target, const char *query)
+{
+	if (query) fprintf(e, "=== Parameters are listed below === \nInputs are target: %s, query: %s\n", target, query);
+	else fprintf(e, "=== Parameters are listed below === \nInputs is target: %s\n", target);
+	fprintf(e, "kmer %d, window %d, index loading size %llu\n", p.k, p.w, (unsigned long long)p.batch_size);
+	fprintf(e, "min-score %d, min-score-med %d, min-score-good %d, max-gap %d, min-cnt %d\n", p.min_chain_score, p.min_score_med, p.min_score_good, p.max_gap, p.min_cnt);
+	fprintf(e, "Homo-polymer compression: %d, Filtering: %d\n", p.hpc, p.filter_flag);
+	fprintf(e, "max-overhang %d, min-overlaplen %d, min-overapratio %.2f\n===\n", p.max_overhang, p.min_ovlp, p.min_ratio);
+}
+
+int lqcov_run_files_sets(lqcov_handle *h, const char *target_path, uint32_t n_sets, const char *const *query_paths,
+                         const int32_t *med, const int32_t *good, const char *const *out_paths, const char *err_path)
+{
+	return guard(h, [&] {
+		if (!target_path) throw std::invalid_argument("no target");
+		if (n_sets == 0 || !query_paths || !med || !good || !out_paths) throw std::invalid_argument("no query sets");
+		lqcov_handle::QuerySetFiles qs;
+		for (uint32_t s = 0; s < n_sets; ++s) {
+			if (!query_paths[s] || !out_paths[s]) throw std::invalid_argument("null query or output path");
+			qs.paths.push_back(query_paths[s]); qs.med.push_back(med[s]); qs.good.push_back(good[s]);
+		}
+		FILE *e = err_path ? fopen(err_path, "a") : stderr;
+		if (!e) throw std::runtime_error(std::string("failed to open file '") + err_path + "'");
+		struct Closer { std::vector<FILE *> fs; FILE *e; bool own_e; ~Closer() { for (FILE *f : fs) if (f) fclose(f); if (own_e && e) fclose(e); } } cl{{}, e, err_path != nullptr};
+		echo_params(e, h->P, target_path, query_paths[0]);
+		for (uint32_t s = 0; s < n_sets; ++s)
+			fprintf(e, "query set %u: %s, min-score-med %d, min-score-good %d -> %s\n", s, query_paths[s], med[s], good[s], out_paths[s]);
+		fflush(e);
+		for (uint32_t s = 0; s < n_sets; ++s) {
+			FILE *o = fopen(out_paths[s], "w");
+			if (!o) throw std::runtime_error(std::string("failed to open file '") + out_paths[s] + "'");
+			cl.fs.push_back(o); qs.outs.push_back(o);
+		}
+		h->run_files(target_path, nullptr, nullptr, e, nullptr, &qs);
+	});
+}
+
 int lqcov_part_dump(lqcov_handle *h, int part, const char *path, int append)
 {
 	return guard(h, [&] {
@@ -776,12 +840,7 @@ int lqcov_main(int argc, const char *const *argv, const char *out_path, const ch
 	int rc = lqcov_parse_args(argc, argv, &p, &target, &query, &dump, errbuf, sizeof(errbuf));
 	if (rc) { fprintf(e, "%s\n", errbuf); if (err_path) fclose(e); return 1; }
 	// effective parameters, as the reference echoes them (minimap2-coverage.c:392-404)
-	if (query) fprintf(e, "=== Parameters are listed below === \nInputs are target: %s, query: %s\n", target, query);
-	else fprintf(e, "=== Parameters are listed below === \nInputs is target: %s\n", target);
-	fprintf(e, "kmer %d, window %d, index loading size %llu\n", p.k, p.w, (unsigned long long)p.batch_size);
-	fprintf(e, "min-score %d, min-score-med %d, min-score-good %d, max-gap %d, min-cnt %d\n", p.min_chain_score, p.min_score_med, p.min_score_good, p.max_gap, p.min_cnt);
-	fprintf(e, "Homo-polymer compression: %d, Filtering: %d\n", p.hpc, p.filter_flag);
-	fprintf(e, "max-overhang %d, min-overlaplen %d, min-overapratio %.2f\n===\n", p.max_overhang, p.min_ovlp, p.min_ratio);
+	echo_params(e, p, target, query);
 	fflush(e);
 	{	// unopenable target: exit 1 with the reference's message (minimap2-coverage.c:276-279)
 		FILE *t = fopen(target, "rb");

@@ -642,9 +642,10 @@ static void make_q2p(double *t)
 }
 
 // == main pass 1 (minimap2-coverage.c:406-444)
-void lqcov_handle::set_queries(u32 n, const u8 *seq_in, const u64 *seq_off_in, const u8 *qual_in, const char *names_in, const u64 *name_off_in)
+void lqcov_handle::set_queries(u32 n, const u8 *seq_in, const u64 *seq_off_in, const u8 *qual_in, const char *names_in, const u64 *name_off_in, bool batch_rule)
 {
 	if (have_queries) throw std::logic_error("queries already set");
+	set_first.assign({0u, n}); have_thr = false;
 	// internal order: longest first (stable); LQCOV_QUERY_ORDER=file keeps the caller's order (A/B and test knob)
 	q_perm.resize(n); q_inv.resize(n);
 	for (u32 i = 0; i < n; ++i) q_perm[i] = i;
@@ -683,7 +684,7 @@ void lqcov_handle::set_queries(u32 n, const u8 *seq_in, const u64 *seq_off_in, c
 	const u8 *seq = pseq.data(), *qual = qual_in ? pqual.data() : nullptr;
 	const u64 *seq_off = pseq_off.data(), *name_off = pname_off.data();
 	const char *names = pnames.data();
-	if (seq_off[n] - seq_off[0] >= 500000000ULL && n > 1) {
+	if (batch_rule && seq_off[n] - seq_off[0] >= 500000000ULL && n > 1) {
 		// reference: a second 500-Mbase query mini-batch aliases the accumulator slots and crashes (lqmap.c:714,735)
 		u64 but_last = seq_off[n - 1] - seq_off[0];
 		if (but_last >= 500000000ULL) throw std::domain_error("query set spans more than one 500-Mbase mini-batch: outside the reference's domain (lqmap.c:714)");
@@ -718,6 +719,41 @@ void lqcov_handle::set_queries(u32 n, const u8 *seq_in, const u64 *seq_off_in, c
 		}
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	}
+}
+
+// Several query sets in one pass over the targets, each with its own -p / -q.  Per query, the mapping depends on the index and on
+// the query alone (minimap2-coverage.c:433-458 maps them one by one; mid_occ comes from the index, map.c:46-54), and -p / -q enter
+// only where a kept chain is scored (CovState::thr): every set's rows are those of a call of its own.
+void lqcov_handle::set_query_sets(u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, const char *names, const u64 *name_off,
+                                  u32 n_sets, const u32 *first, const i32 *med, const i32 *good)
+{
+	if (have_queries) throw std::logic_error("queries already set");
+	if (n_sets == 0 || !first || !med || !good) throw std::invalid_argument("no query sets");
+	if (first[0] != 0 || first[n_sets] != n) throw std::invalid_argument("set_first must run from 0 to the number of queries");
+	for (u32 s = 0; s < n_sets; ++s) if (first[s + 1] < first[s]) throw std::invalid_argument("set_first must not decrease");
+	for (u32 s = 0; s < n_sets; ++s) {
+		// the checks of the option parser (lqcov_parse_args) and of lqcov_create, set by set
+		if (med[s] < P.min_chain_score) throw std::invalid_argument("set " + std::to_string(s) + ": -p must be larger than or equal to -m");
+		if (good[s] < P.min_chain_score || good[s] < med[s]) throw std::invalid_argument("set " + std::to_string(s) + ": -q must be larger than or equal to -m and -p");
+		if (med[s] < 0 || good[s] < 0 || med[s] >= 65536 || good[s] >= 65536) throw std::invalid_argument("set " + std::to_string(s) + ": -p and -q must be below 65536 (lqmap.c:841 packs them into 16 bits each)");
+		// the 500-Mbase query mini-batch (lqmap.c:714) is a limit of each call, so of each set: its longest-first order ends with a shortest read
+		const u32 a = first[s], b = first[s + 1];
+		if (b - a > 1 && seq_off[b] - seq_off[a] >= 500000000ULL) {
+			u64 shortest = ~0ULL;
+			for (u32 i = a; i < b; ++i) shortest = std::min<u64>(shortest, seq_off[i + 1] - seq_off[i]);
+			if (seq_off[b] - seq_off[a] - shortest >= 500000000ULL)
+				throw std::domain_error("query set " + std::to_string(s) + " spans more than one 500-Mbase mini-batch: outside the reference's domain (lqmap.c:714)");
+		}
+	}
+	set_queries(n, seq, seq_off, qual, names, name_off, false);
+	set_first.assign(first, first + n_sets + 1);
+	std::vector<u32> thr(n + 1, 0);
+	for (u32 s = 0; s < n_sets; ++s)
+		for (u32 i = first[s]; i < first[s + 1]; ++i) thr[q_inv[i]] = (u32)med[s] << 16 | (u32)good[s];
+	q_thr.ensure((u64)(n + 1) * 4);
+	h2d(q_thr.as<u32>(), thr.data(), n + 1, stream);
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));
+	have_thr = true;
 }
 
 void lqcov_handle::reset()
@@ -960,7 +996,7 @@ void lqcov_handle::chain_stage(MapLane &L, Part &pt, const u64 *aqb, u64 a_base,
 	cs.mini_pos = mini_pos.as<u64>(); cs.mpq_off = mpq_off.as<u64>(); cs.qlen = q.d_len.as<u32>(); cs.tlen = pt.rs.d_len.as<u32>();
 	cs.ivl = L.ivl.as<Ivl>(); cs.n_ivl = L.n_ivl.as<u32>(); cs.ivl_cap = ivl_cap;
 	cs.dbg = dbg ? dbg_chains.as<ChainRec>() : nullptr; cs.n_dbg = n_dbg.as<unsigned long long>(); cs.dbg_cap = dbg_cap;
-	cs.tie_mode = tie_mode; cs.qmap = qmap;
+	cs.tie_mode = tie_mode; cs.qmap = qmap; cs.thr = have_thr ? q_thr.as<u32>() : nullptr;
 	cs.cnt_max = cnt_max;
 	cs.rec = sink ? sink->rec : nullptr; cs.n_rec = sink ? sink->n_rec : nullptr; cs.rec_cap = sink ? sink->rec_cap : 0;
 	cs.rec_at = sink ? sink->at : nullptr; cs.n_at = sink ? sink->n_at : nullptr; cs.at_cap = sink ? sink->at_cap : 0;
@@ -2266,6 +2302,14 @@ void lqcov_handle::write_table(FILE *out)
 	lq_format_rows(out, P.filter_flag, rows.data(), q.n, regs.data(), mregs.data(), [&](u32 i) { return q.names[q_inv[i]].c_str(); });
 }
 
+void lqcov_handle::write_table_set(u32 set, FILE *out)
+{
+	if (!finished) throw std::logic_error("finish() has not run");
+	if (set + 1 >= set_first.size()) throw std::invalid_argument("no such query set");
+	const u32 a = set_first[set];
+	lq_format_rows(out, P.filter_flag, rows.data() + a, set_first[set + 1] - a, regs.data(), mregs.data(), [&](u32 i) { return q.names[q_inv[a + i]].c_str(); });
+}
+
 // ---- the whole run from files (minimap2-coverage.c:406-617) -----------------------------------------
 // ---- prebuilt indexes: the reference's .mmi files (index.c:385-540) ----------------------------------
 #define LQ_MMI_MAGIC "MMI\2"
@@ -2457,8 +2501,10 @@ bool lqcov_handle::load_part(FILE *fp, Part &pt)
 	return true;
 }
 
-int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path)
+int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path, const QuerySetFiles *sets)
 {
+	if (sets) query = nullptr;
+	const bool has_query = query || sets;
 	bool is_idx = false;
 	i32 ik = 0, iw = 0, ihpc = 0;
 	{
@@ -2478,15 +2524,42 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 	// buffers, 2-bit packing, all host work; joined before anything of the targets touches the device.
 	auto load_queries = [&]() {
 		LQ_HIP_CHECK(hipSetDevice(device));
-		FastxReader fq(query);
 		ReadBatch qb;
-		while (fq.read_minibatch(INT64_MAX, qb, true) > 0) {}
+		if (!sets) {
+			FastxReader fq(query);
+			while (fq.read_minibatch(INT64_MAX, qb, true) > 0) {}
+		} else {                                                  // the files one after the other, each parsed as a call of its own parses it
+			std::vector<u32> first{0};
+			int with_qual = -1;
+			for (size_t f = 0; f < sets->paths.size(); ++f) {
+				FastxReader fq(sets->paths[f]);
+				ReadBatch b;
+				while (fq.read_minibatch(INT64_MAX, b, true) > 0) {}
+				if (b.size()) {
+					if (with_qual >= 0 && with_qual != (int)b.any_qual)
+						throw std::domain_error("query sets with qualities mixed with sets without: the mean quality column is per call (FASTQ and FASTA sets cannot share one)");
+					with_qual = (int)b.any_qual;
+				}
+				const u64 sb = qb.seq.size(), nb = qb.names.size();
+				qb.seq.insert(qb.seq.end(), b.seq.begin(), b.seq.end()); qb.qual.insert(qb.qual.end(), b.qual.begin(), b.qual.end());
+				qb.names.insert(qb.names.end(), b.names.begin(), b.names.end());
+				for (u32 i = 1; i < b.seq_off.size(); ++i) qb.seq_off.push_back(sb + b.seq_off[i]);
+				for (u32 i = 1; i < b.name_off.size(); ++i) qb.name_off.push_back(nb + b.name_off[i]);
+				qb.any_qual = qb.any_qual || b.any_qual;
+				first.push_back(qb.size());
+			}
+			const double tq = lq_now_s();
+			set_query_sets(qb.size(), qb.seq.data(), qb.seq_off.data(), qb.any_qual ? qb.qual.data() : nullptr, qb.names.data(), qb.name_off.data(),
+			               (u32)sets->paths.size(), first.data(), sets->med.data(), sets->good.data());
+			if (log) fprintf(log, "[lqcov] loaded %u query sequence(s) in %zu set(s), %" PRIu64 " bases, %" PRIu64 " minimizers (read %.3f s, upload + sketch %.3f s)\n", qb.size(), sets->paths.size(), qb.bases(), q.n_mini, tq - t_run0, lq_now_s() - tq);
+			return;
+		}
 		const double tq = lq_now_s();
 		set_queries(qb.size(), qb.seq.data(), qb.seq_off.data(), qb.any_qual ? qb.qual.data() : nullptr, qb.names.data(), qb.name_off.data());
 		if (log) fprintf(log, "[lqcov] loaded %u query sequence(s), %" PRIu64 " bases, %" PRIu64 " minimizers (read %.3f s, upload + sketch %.3f s)\n", qb.size(), qb.bases(), q.n_mini, tq - t_run0, lq_now_s() - tq);
 	};
 	std::future<void> queries_loaded;
-	if (query) {
+	if (has_query) {
 #ifndef LQ_EMU
 		if (!is_idx) queries_loaded = std::async(std::launch::async, load_queries);
 		else load_queries();
@@ -2515,7 +2588,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 			Part &pt = *parts[id];
 			if (log) fprintf(log, "[lqcov] part %d (prebuilt): %u target sequence(s), %" PRIu64 " minimizers, %" PRIu64 " distinct, mid_occ = %d\n",
 			                 n_parts, pt.rs.n, pt.rs.n_mini, pt.n_keys, mid_occ);
-			if (query) map_part(pt);
+			if (has_query) map_part(pt);
 			parts[id].reset();
 			++n_parts;
 		}
@@ -2653,7 +2726,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 			if (dump) dump_part(pt, dump);                          // mm_idx_reader_read (index.c:533)
 		};
 #ifndef LQ_EMU
-		const bool pipeline = K.pipeline && query && !dump && profiling != 1;
+		const bool pipeline = K.pipeline && has_query && !dump && profiling != 1;
 #else
 		const bool pipeline = false;                                // (the test emulator runs one kernel at a time, on the calling thread)
 #endif
@@ -2680,7 +2753,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 					return true;
 				};
 				if (pipeline) next_ready = std::async(std::launch::async, advance);
-				if (query) {
+				if (has_query) {
 					const double tm0 = lq_now_s();
 					map_part(*dev[cur]);
 					if (log) fprintf(log, "[lqcov] part %d: mapped %u queries in %.3f s, %" PRIu64 " anchors (%" PRIu64 " written; so far %" PRIu64 " runs of %" PRIu64 " queries chained in klib's order, %" PRIu64 " anchors)\n",
@@ -2694,10 +2767,11 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 		}
 		for (Part *d : dev) for (auto &up : parts) if (up.get() == d) up.reset();
 	}
-	if (!query) return 0;                                         // index only (minimap2-coverage.c:460-468)
+	if (!has_query) return 0;                                         // index only (minimap2-coverage.c:460-468)
 	const double tf0 = lq_now_s();
 	finish();
-	write_table(out);
+	if (sets) for (size_t f = 0; f < sets->outs.size(); ++f) write_table_set((u32)f, sets->outs[f]);
+	else write_table(out);
 	if (log) fprintf(log, "[lqcov] rows and table in %.3f s; the whole call %.3f s (device allocations of this process so far: %.3f s for %.1f GB)\n", lq_now_s() - tf0, lq_now_s() - t_run0,
 	                 (double)lq_alloc_ns * 1e-9, (double)lq_alloc_bytes * 1e-9);
 	// A uint16 match counter that reaches 65535 makes the reference's result depend on the order in which it processed the

@@ -222,6 +222,10 @@ struct lqcov_handle {
 	// Everything per query inside the engine (and in the accumulator exchange of the multi-GPU path) uses the internal order;
 	// rows, regions, minimizer and chain dumps are handed out in the caller's order.
 	std::vector<u32> q_perm, q_inv;
+	// Query sets (lqcov_set_query_sets): set s holds the caller's queries set_first[s] .. set_first[s + 1] - 1, mapped with its own
+	// -p / -q; q_thr holds med << 16 | good per query in the internal order (CovState::thr).  One set, no q_thr: lqcov_set_queries.
+	std::vector<u32> set_first;
+	DBuf q_thr; bool have_thr = false;
 	DBuf q_owner;                         // query of every query minimizer
 	DBuf lambda, lambda2, avg_k, cnts, qflags, qual_psum;
 	DBuf dup, qdirty, dup_table;          // k_dup_mark: minimizers / queries whose anchors can repeat an x (per part)
@@ -286,7 +290,9 @@ struct lqcov_handle {
 	bool sketch_dp_setup(ReadSetDev &rs, u64 &n_tiles);
 	void sketch_dp_launch(ReadSetDev &rs, u64 tile0, u64 tile1);
 	void export_minimizers(ReadSetDev &rs, u64 *x_dev, u64 *y_dev, u32 rid_base);
-	void set_queries(u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, const char *names, const u64 *name_off);
+	void set_queries(u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, const char *names, const u64 *name_off, bool batch_rule = true);
+	void set_query_sets(u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, const char *names, const u64 *name_off,
+	                    u32 n_sets, const u32 *first, const i32 *med, const i32 *good);
 	void build_index(Part &pt);
 	void build_part(Part &pt);
 	void open_gate();
@@ -314,7 +320,10 @@ struct lqcov_handle {
 	void reset();
 	void finish();
 	void write_table(FILE *out);
-	int run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path = nullptr);
+	void write_table_set(u32 set, FILE *out);
+	struct QuerySetFiles { std::vector<const char *> paths; std::vector<i32> med, good; std::vector<FILE *> outs; };
+	// sets != null: the queries are the files of `sets` (query and out are not used), one table per set
+	int run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path = nullptr, const QuerySetFiles *sets = nullptr);
 	void adopt_index_params(i32 k, i32 w, i32 hpc);
 	void dump_part(Part &pt, FILE *fp);                      // mm_idx_dump (index.c:390-426)
 	bool load_part(FILE *fp, Part &pt);                      // mm_idx_load (index.c:428-479); false at end of file

@@ -279,6 +279,9 @@ struct CovState {              // per-query accumulators (minimap2-coverage.c:43
 	unsigned long long *sens; u32 *n_sens; u32 sens_cap;
 	const unsigned long long *want; u32 n_want;
 	const u32 *qmap;           // not null: the batch's i-th query is query qmap[i] (a subset of the queries); else q0 + i
+	// Several query sets on one handle, each with its own -p / -q (lqcov_set_query_sets): thr[q] = med << 16 | good of query q
+	// (engine order).  Null: one pair for the handle, MapParams' min_sc_med / min_sc_good.
+	const u32 *thr;
 	// The reference's counters are uint16 and the test that should saturate them reads a[st], not a[j] (esterr.c:130,136): once a
 	// counter of a query reaches cnt_max (65535) its final counters depend on the order in which the chains were processed.
 	// The kernels count in 32 bits and flag the query; a flagged query is chained once more with `rec` set: nothing is
@@ -286,6 +289,10 @@ struct CovState {              // per-query accumulators (minimap2-coverage.c:43
 	u32 cnt_max;
 	SatRec *rec; unsigned long long *n_rec; u64 rec_cap; u32 *rec_at; unsigned long long *n_at; u64 at_cap;
 };
+
+// -p / -q of query q: the reference packs them into one word per call (min_score_med_good, lqmap.c:484); here a word per query
+__device__ __forceinline__ i32 lq_sc_med(const MapParams &P, const CovState &C, u32 q) { return C.thr ? (i32)(C.thr[q] >> 16) : (i32)(u16)P.min_sc_med; }
+__device__ __forceinline__ i32 lq_sc_good(const MapParams &P, const CovState &C, u32 q) { return C.thr ? (i32)(C.thr[q] & 0xffffu) : (i32)(u16)P.min_sc_good; }
 
 __device__ __forceinline__ bool lq_tie_wanted(const CovState &C, u32 q, u32 hi)
 {
@@ -510,6 +517,7 @@ __device__ __forceinline__ bool lq_chain_finish(AP a, const i64 n, IP f, IP p, I
 	i64 n_v = 0;
 	u32 n_rec_run = 0;
 	const i32 qlen = (i32)C.qlen[q];
+	const i32 sc_med = lq_sc_med(P, C, q), sc_good = lq_sc_good(P, C, q);
 	const u64 *mp = C.mini_pos + C.mpq_off[q];
 	const i32 n_mp = (i32)(C.mpq_off[q + 1] - C.mpq_off[q]);
 	for (i64 ui = n_u - 1; ui >= 0; --ui) {
@@ -552,7 +560,7 @@ __device__ __forceinline__ bool lq_chain_finish(AP a, const i64 n, IP f, IP p, I
 		const u32 hang3 = (u32)qlen - uqe < rl - ure ? (u32)qlen - uqe : rl - ure;
 		const bool pass = sti >= 0 && !((double)(uqe - uqs) < (double)(uqe - uqs + hang5 + hang3) * P.min_ratio || hang5 > (u32)P.max_overhang || hang3 > (u32)P.max_overhang);
 		if (C.rec) {                                               // replay of a saturated query: the chain goes to the host as it is
-			const bool good = pass && score >= (i32)(u16)P.min_sc_good;
+			const bool good = pass && score >= sc_good;
 			SatRec sr;
 			sr.first_x = first.x; sr.first_y = first.y & ~LQ_TIE_MARK; sr.f_peak = (u32)(ue >> 32); sr.run_hi = (u32)(first.x >> 32); sr.peak_j = (u32)ue; sr.seq = n_rec_run++;
 			sr.score = (u32)score; sr.cnt = (u32)cnt; sr.sti = sti; sr.n_at = 0; sr.at_off = 0; sr.good = good ? 1u : 0u; sr.span = uqe - uqs + 1;
@@ -571,12 +579,12 @@ __device__ __forceinline__ bool lq_chain_finish(AP a, const i64 n, IP f, IP p, I
 		}
 		if (!pass) continue;
 		atomicAdd(&C.lambda[q], (unsigned long long)(u32)(uqe - uqs + 1));
-		u32 flag = score >= (i32)(u16)P.min_sc_med ? 2u : 0u;
+		u32 flag = score >= sc_med ? 2u : 0u;
 		{
 			u32 s = atomicAdd(C.n_ivl, 1u);
 			if (s < C.ivl_cap) { Ivl iv; iv.q = q; iv.start = uqs << 3 | flag; iv.end = uqe << 3 | flag | 1u; C.ivl[s] = iv; }
 		}
-		if (score < (i32)(u16)P.min_sc_good) continue;
+		if (score < sc_good) continue;
 		atomicAdd(&C.lambda2[q], (unsigned long long)(u32)(uqe - uqs + 1));
 		u32 *cn = C.cnts + C.qmoff[q];
 		u32 old = atomicAdd(&cn[sti], 1u);
@@ -851,6 +859,7 @@ __device__ __forceinline__ bool lq_chain_finish_wave(const mm128 *a, const i64 n
 	LQ_BLOCK_SYNC();
 	n_keep = sh[0];
 	const i32 qlen = (i32)C.qlen[q];
+	const i32 sc_med = lq_sc_med(P, C, q), sc_good = lq_sc_good(P, C, q);
 	const u64 *mp = C.mini_pos + C.mpq_off[q];
 	const i32 n_mp = (i32)(C.mpq_off[q + 1] - C.mpq_off[q]);
 	i64 n_v0 = 0;
@@ -889,13 +898,13 @@ __device__ __forceinline__ bool lq_chain_finish_wave(const mm128 *a, const i64 n
 		const u32 hang3 = (u32)qlen - uqe < rl - ure ? (u32)qlen - uqe : rl - ure;
 		if ((double)(uqe - uqs) < (double)(uqe - uqs + hang5 + hang3) * P.min_ratio || hang5 > (u32)P.max_overhang || hang3 > (u32)P.max_overhang)
 			continue;
-		const u32 flag = score >= (i32)(u16)P.min_sc_med ? 2u : 0u;
+		const u32 flag = score >= sc_med ? 2u : 0u;
 		if (ln == 0) {
 			atomicAdd(&C.lambda[q], (unsigned long long)(u32)(uqe - uqs + 1));
 			u32 s = atomicAdd(C.n_ivl, 1u);
 			if (s < C.ivl_cap) { Ivl iv; iv.q = q; iv.start = uqs << 3 | flag; iv.end = uqe << 3 | flag | 1u; C.ivl[s] = iv; }
 		}
-		if (score < (i32)(u16)P.min_sc_good) continue;
+		if (score < sc_good) continue;
 		u32 *cn = C.cnts + C.qmoff[q];
 		if (ln == 0) {
 			atomicAdd(&C.lambda2[q], (unsigned long long)(u32)(uqe - uqs + 1));

@@ -27,7 +27,7 @@ different GPUs and be reduced: all_reduce(SUM) for the sums and counters, all_ga
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -279,6 +279,14 @@ class PartRunner:
                 c = eng.sat_replay(q, recs, at, c)
             self.sat[q] = c
 
+    def write_tables(self, outs: Sequence[str]):
+        """after finalize(): finish, and rank 0 writes the table of query set s (Engine.set_query_sets) to outs[s].  The
+        accumulators are per query, so several sets travel through the same exchange as one."""
+        self.eng.finish()
+        if self.rank == 0:
+            for s, path in enumerate(outs):
+                self.eng.write_table(path, set=s)
+
     def finalize(self):
         ivl = torch.cat(self.ivl, dim=0).contiguous() if self.ivl else torch.zeros((0, 3), dtype=torch.int32, device=self.dev)
         self._ivl_keep = ivl if ivl.shape[0] else torch.zeros((1, 3), dtype=torch.int32, device=self.dev)
@@ -337,9 +345,33 @@ class QueryShardRunner:
         """every rank passes the whole query set; the handle receives this rank's share"""
         self.n_queries = len(names)
         self.names = list(names)
+        self.set_first = [0, self.n_queries]
         self.my_queries = shard_queries([int(s.shape[0]) for s in seqs], self.world)[self.rank]
         self.eng.set_queries([names[i] for i in self.my_queries], [seqs[i] for i in self.my_queries],
                              [quals[i] for i in self.my_queries] if quals is not None else None)
+
+    def set_query_sets(self, sets):
+        """every rank passes every set, [(names, seqs, quals or None, med, good), ...] (Engine.set_query_sets); the union is
+        sharded as one query set and the handle receives this rank's share of each set with that set's -p / -q (a set may have
+        no query on a rank)"""
+        names, seqs, quals, first = [], [], [], [0]
+        with_qual = {ql is not None for nm, sq, ql, m, g in sets if len(sq)}
+        if len(with_qual) > 1:
+            from . import api as _api
+            raise _api.LqcovError(-5, "query sets with qualities mixed with sets without")
+        for nm, sq, ql, m, g in sets:
+            names += list(nm); seqs += list(sq); quals += list(ql) if ql is not None else [None] * len(sq)
+            first.append(len(seqs))
+        self.n_queries = len(names)
+        self.names = names
+        self.set_first = first
+        self.my_queries = shard_queries([int(x.shape[0]) for x in seqs], self.world)[self.rank]
+        mine = np.asarray(self.my_queries, dtype=np.int64)
+        local = []
+        for k, (nm, sq, ql, m, g) in enumerate(sets):
+            ix = mine[(mine >= first[k]) & (mine < first[k + 1])]           # (ascending: the rank's share keeps the set's order)
+            local.append(([names[i] for i in ix], [seqs[i] for i in ix], [quals[i] for i in ix] if ql is not None else None, m, g))
+        self.eng.set_query_sets(local)
 
     # ---- the parts in a pipeline (the reference's part loop, minimap2-coverage.c:449-458, overlapped) --------------------------
     # On N GPUs the front of a part -- upload and sketch of this rank's 1/N share, the all-gather, the replicated index build --
@@ -541,15 +573,28 @@ class QueryShardRunner:
             if dev.type == "cuda":
                 torch.cuda.empty_cache()                          # the exchange buffers go back to the device: the mapping sizes its work space from what is free
 
-    def gather_table(self) -> Optional[str]:
-        """finish on every rank; rank 0 returns the table of all queries in the caller's order, the others None.  What travels
+    def gather_table(self, set: Optional[int] = None) -> Optional[str]:
+        """finish on every rank; rank 0 returns the table of all queries in the caller's order, the others None (set: the rows
+        of that query set only, set_query_sets; every rank makes the same calls, each one gathers).  What travels
         is binary: every rank's `lqcov_row` array, its two region pools and its query indices, as padded uint8 tensors through
         one gather each (RCCL on the GPU box); rank 0 rebases the region offsets, orders the rows and prints them with the
         engine's own formatter (lqcov_format_rows: the reference's printf arithmetic in one place)."""
         from . import api as _api
+        gathered = self._gather_rows()
+        if self.world == 1:
+            return self.eng.table_text(set=set)
+        if self.rank != 0:
+            return None
+        rows, regs, mregs = gathered
+        a, b = (0, self.n_queries) if set is None else (self.set_first[set], self.set_first[set + 1])
+        return _api.format_rows(self.eng.lib, int(self.eng.params.filter_flag), rows[a:b], regs, mregs, self.names[a:b])
+
+    def _gather_rows(self):
+        """rank 0: every query's row in the caller's order and the two region pools the rows point into; other ranks: ()"""
+        from . import api as _api
         self.eng.finish()
         if self.world == 1:
-            return self.eng.table_text()
+            return ()
         rows, regs, mregs = self.eng.rows_binary()
         assert rows.shape[0] == len(self.my_queries)
         idx = np.asarray(self.my_queries, dtype=np.int64)
@@ -565,7 +610,7 @@ class QueryShardRunner:
                 buf[:p.shape[0]] = torch.from_numpy(np.ascontiguousarray(p)).to(dev)
             got.append(_gather(buf, self.world, self.rank, self.group))
         if self.rank != 0:
-            return None
+            return ()
         row_sz = rows.shape[1] if rows.ndim == 2 and rows.shape[0] else _api.C.sizeof(_api.Row)
         all_rows, all_regs, all_mregs, all_idx = [], [], [], []
         reg_base = mreg_base = 0
@@ -585,8 +630,7 @@ class QueryShardRunner:
         idx_cat = np.concatenate(all_idx)
         order = np.argsort(idx_cat, kind="stable")
         assert idx_cat.shape[0] == self.n_queries and np.array_equal(idx_cat[order], np.arange(self.n_queries))
-        return _api.format_rows(self.eng.lib, int(self.eng.params.filter_flag), rows_cat[order], np.concatenate(all_regs), np.concatenate(all_mregs),
-                                [self.names[i] for i in range(self.n_queries)])
+        return rows_cat[order], np.concatenate(all_regs), np.concatenate(all_mregs)
 
 
 # numpy view of lqcov_row (include/lqcov.h): the gatherer rebases the two region offsets

@@ -50,7 +50,9 @@ def coverage_argv(preset: str, fastx_path: str, sample_path: str, ncpu: int = 4,
 
 def db_build_argv(preset: str, tempdb_path: str, fastx_path: str, fast: bool = False, inds: str = "4G", short: bool = False) -> List[str]:
     """`sampleqc --db`, first call: index every read into a prebuilt .mmi (longQC.py:266-277); short=True gives the
-    t_db_minimap2_short variant (-k 12 -w 5)."""
+    t_db_minimap2_short variant (-k 12 -w 5).  With --db --short and equal index options (every preset but pb-hifi, without
+    --fast) the two .mmi files are the same: one serves both subsamples, mapped in one call with lqcov_run_files_sets
+    (Engine.run_files_sets: the main set with the preset's -p, the short set with the --short -p)."""
     params = "-k 12 -w 5 -I %s" % inds if short else db_params(preset, fast, inds)
     return shlex.split("%s -d %s %s" % (params, tempdb_path, fastx_path))
 
@@ -144,20 +146,61 @@ def _to_arrays(reads):
     return names, seqs, quals
 
 
+def short_split(s_reads, length_threshold: int = 500):
+    """longQC.py:410-413: (reads of at least length_threshold bases, shorter reads), each in the subsample's order"""
+    reads = [r for r in s_reads if r]
+    return [r for r in reads if len(r[1]) >= length_threshold], [r for r in reads if len(r[1]) < length_threshold]
+
+
 def coverage_in_memory(chunks: Iterable, s_reads, preset: str = "ont-ligation", fast: bool = False, inds: int = 4000000000,
-                       out: Optional[str] = None, device: int = 0, engine=None):
+                       out: Optional[str] = None, device: int = 0, engine=None, short: bool = False,
+                       short_threshold: Optional[int] = None):
     """The same computation as `LqExec(minimap2-coverage).exec(*coverage_argv(...))` without writing
     subsample.fastq and re-parsing both files (minimap2-coverage.c:408,471 parse the query file twice): the
     subsample goes to the device once, the input chunks (`chunks` yields (reads, n_seqs, n_bases), reads =
     [name, seq, qual]) are streamed into index parts cut by the reference's rule (index.c:244,311-316).
-    Returns the table text (also written to `out` if given)."""
-    from . import api, multigpu
-    argv = coverage_argv(preset, "-", "-", fast=fast, inds=str(inds))
-    p, _, _ = api.parse_args(argv)
+    Returns the table text (also written to `out` if given).  short=True: the --short call's argv (coverage_argv).
+
+    short_threshold (LongQC's --short, 500): s_reads is split as longQC.py:410-413 does (short_split) and both calls of
+    longQC.py:438-445,527-543 are made -> (main table, short table); `out`, if given, gets their concatenation (LongQC's
+    merged_coverage_out.txt).  Where the two calls index the targets alike (every preset but pb-hifi, without `fast`), the
+    two sets are mapped in ONE pass over `chunks`, each with its own -p; otherwise `chunks` must be re-iterable (a list)."""
+    if short_threshold is None:
+        text = _coverage_pass(chunks, [(s_reads, coverage_argv(preset, "-", "-", fast=fast, inds=str(inds), short=short))], device, engine)[0]
+    else:
+        main_reads, short_reads = short_split(s_reads, short_threshold)
+        argv_main = coverage_argv(preset, "-", "-", fast=fast, inds=str(inds))
+        argv_short = coverage_argv(preset, "-", "-", fast=fast, inds=str(inds), short=True)     # (pb-hifi: raises, as the CLI has no --short -p)
+        strip_p = lambda a: [x for i, x in enumerate(a) if x != "-p" and (i == 0 or a[i - 1] != "-p")]
+        if strip_p(argv_main) == strip_p(argv_short):
+            text = _coverage_pass(chunks, [(main_reads, argv_main), (short_reads, argv_short)], device, engine)
+        else:
+            if engine is not None:
+                raise ValueError("two passes with different index options need two handles: pass engine=None")
+            text = [_coverage_pass(chunks, [(main_reads, argv_main)], device, None)[0], _coverage_pass(chunks, [(short_reads, argv_short)], device, None)[0]]
+        text = tuple(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text if isinstance(text, str) else "".join(text))
+    return text
+
+
+def _coverage_pass(chunks: Iterable, sets, device: int, engine) -> List[str]:
+    """one pass over the target chunks for every (reads, argv) of `sets`; the argvs differ at most in -p -> one table per set"""
+    from . import api
+    p, _, _ = api.parse_args(sets[0][1])
     eng = engine or api.Engine(p, device=device)
     try:
-        qn, qs, qq = _to_arrays([r for r in s_reads if r])
-        eng.set_queries(qn, qs, qq)
+        if len(sets) == 1:
+            qn, qs, qq = _to_arrays([r for r in sets[0][0] if r])
+            eng.set_queries(qn, qs, qq)
+        else:
+            qsets = []
+            for reads, argv in sets:
+                ps, _, _ = api.parse_args(argv)
+                qn, qs, qq = _to_arrays([r for r in reads if r])
+                qsets.append((qn, qs, qq, int(ps.min_score_med), int(ps.min_score_good)))
+            eng.set_query_sets(qsets)
         batch = int(p.batch_size)
         mini = min(int(p.idx_mini_batch), batch)
         part, part_bases, pend, pend_bases = None, 0, [], 0
@@ -189,11 +232,9 @@ def coverage_in_memory(chunks: Iterable, s_reads, preset: str = "ont-ligation", 
         flush_minibatch()
         close_part()
         eng.finish()
-        text = eng.table_text()
-        if out:
-            with open(out, "w") as f:
-                f.write(text)
-        return text
+        if len(sets) == 1:
+            return [eng.table_text()]
+        return [eng.table_text(set=k) for k in range(len(sets))]
     finally:
         if engine is None:
             eng.close()
