@@ -327,6 +327,17 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 int lqsdust_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *qual, int W, int T,
                   uint32_t *masked, double *qual_psum, uint32_t *n_above_q7, char *errbuf, size_t errbuf_len);
 
+/* ---- the adapter search of sampleqc (lq_adapt.py:10-101, edlib.align(adapter, window, mode="HW", task="path")) ------ */
+/* Reads as ASCII (seq_off has n+1 entries).  For every read of at least 2 * length bases, per adapter given (pointer not NULL,
+ * length not 0), one row of four int32 in out5 / out3 [n x 4]: d (edit distance), s (start), e (first optimal end, -1 when
+ * the whole adapter is deleted) and L (length of edlib's traceback path) of the adapter against the read's first (out5) or
+ * last (out3) `length` bases, as edlib reports them; rows of shorter reads are -1.  The 3' row is that of the untrimmed read:
+ * whether the reference skips it after a 5' trim is the caller's decision.  Bytes compare exactly.  length in [1, 4096],
+ * adapters of at most 32768 bases (LQCOV_E_DOMAIN otherwise).                                                            */
+int lqadapt_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *seq_off,
+                  const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
+                  uint32_t length, int32_t *out5, int32_t *out3, char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

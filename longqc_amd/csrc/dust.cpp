@@ -4,6 +4,9 @@
 #include "engine.hpp"
 #include "kernels_dust.hpp"
 #include "fastx.hpp"
+#include "lq_cabi.hpp"
+using lq_cabi::guarded;
+using lq_cabi::select_device;
 #include <cstdio>
 #include <cstring>
 #include <cmath>
@@ -73,28 +76,6 @@ void dust_batch(DustDev &D, u32 n, const u8 *seq, const u64 *seq_off, const u8 *
 	LQ_HIP_CHECK(hipStreamSynchronize(D.stream));
 }
 
-void set_err(char *err, size_t n, const char *msg) { if (err && n) snprintf(err, n, "%s", msg); }
-
-int select_device(int device)
-{
-	int nd = 0;
-	if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) throw std::runtime_error("no HIP device available");
-	if (device < 0 || device >= nd) throw std::runtime_error("HIP device index out of range");
-	LQ_HIP_CHECK(hipSetDevice(device));
-	return device;
-}
-
-template <class F> int guarded(char *err, size_t errlen, F &&f)
-{
-	try { f(); return 0; }
-	catch (const std::domain_error &e) { set_err(err, errlen, e.what()); return LQCOV_E_DOMAIN; }
-	catch (const std::invalid_argument &e) { set_err(err, errlen, e.what()); return LQCOV_E_ARG; }
-	catch (const std::runtime_error &e) {
-		set_err(err, errlen, e.what());
-		return strstr(e.what(), "failed to open") ? LQCOV_E_IO : LQCOV_E_DEVICE;
-	}
-	catch (const std::exception &e) { set_err(err, errlen, e.what()); return LQCOV_E_STATE; }
-}
 } // namespace
 
 extern "C" {

@@ -23,6 +23,17 @@ PRESET_MED_SCORE = {
     "pb-rs2": (80, 60), "pb-sequel": (80, 60), "pb-hifi": (80, None),
     "ont-ligation": (160, 140), "ont-rapid": (160, 140), "ont-1dsq": (160, 140),
 }
+# adapters per preset: (adp5, adp3), None where the preset sets none -- longQC.py:171-216 (--adapter_5 / --adapter_3 override
+# them there); the chunk loop hands them to cut_adapter (longqc_amd/adapter.py)
+_PB_RS2_ADP = "ATCTCTCTCTTTTCCTCCTCCTCCGTTGTTGTTGTTGAGAGAGAT"
+_PB_SEQUEL_ADP = "ATCTCTCTCAACAACAACAACGGAGGAGGAGGAAAAGAGAGAGAT"
+PRESET_ADAPTERS = {
+    "pb-rs2": (_PB_RS2_ADP, _PB_RS2_ADP), "pb-sequel": (_PB_SEQUEL_ADP, _PB_SEQUEL_ADP), "pb-hifi": (_PB_SEQUEL_ADP, _PB_SEQUEL_ADP),
+    "ont-ligation": ("AATGTACTTCGTTCAGTTACGTATTGCT", "GCAATACGTAACTGAACG"),
+    "ont-rapid": ("GTTTTCGCATTTATCGTGAAACGCTTTCGCGTTTTTCGTGCGCCGCTTCA", None),
+    "ont-1dsq": ("GGCGTCTGCTTGGGTGTTTAACCTTTTTGTCAGAGAGGTTCCAAGTCAGAGAGGTTCCT",
+                 "GGAACCTCTCTGACTTGGAACCTCTCTGACAAAAAGGTTAAACACCCAAGCAGACGCCAGCAAT"),
+}
 MINIMAP2_PARAMS = "-Y -l 0 -q 160"                                      # longQC.py:177,186,194,202,209,217
 MINIMAP2_FILTERING_PARAMS = "-Y -Hk15 -w 10 -c 1 -l 0 --filter"        # longQC.py:255 (spike-in control)
 
