@@ -338,6 +338,21 @@ int lqadapt_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *se
                   const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
                   uint32_t length, int32_t *out5, int32_t *out3, char *errbuf, size_t errbuf_len);
 
+/* ---- the GC fraction step of sampleqc (lq_gcfrac.py:25-48, LqGC.calc_read_and_chunk_gc_frac) ------------------------- */
+/* Reads as ASCII (seq_off has n+1 entries).  gc[i] = the number of 'G' and 'C' bytes of read i (no other byte counts).
+ * k != NULL: read i has k[i] sampled positions (the caller computes int(1/chunk_size * l * samp_rate)), draw_off their n+1
+ * prefix sums.  The positions are pos_in's, or -- pos_in == NULL -- drawn on the device: position j of read i is the image
+ * of j under a bijection of [0, l) keyed by (seed, first_read + i), so the draw of a read depends on its
+ * ordinal in the whole input alone; pos_out, if given, receives the positions used.  kept[i] = the index, in draw order, of
+ * the first position p with p + chunk_size - 1 > l, where the reference's walk of the read ends, or k[i]; win_gc[d] = the
+ * G/C bytes of seq[p : min(p + chunk_size, l)] for the draws before kept[i], 0 for the others.  All results are integers:
+ * the fractions are the caller's divisions.  LQCOV_E_ARG: null buffers, offsets not ascending, draw_off not the prefix sums
+ * of k, k[i] > l, a pos_in outside its read; LQCOV_E_DOMAIN: chunk_size outside [1, 4096], a read of 2^32 bases or more. */
+int lqgc_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *seq_off,
+               uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,
+               uint64_t seed, uint64_t first_read, uint32_t *gc, uint32_t *pos_out, uint16_t *win_gc, uint32_t *kept,
+               char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif
