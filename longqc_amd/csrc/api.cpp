@@ -371,12 +371,13 @@ int lqcov_part_clear(lqcov_handle *h, int part)
 		rs.n = 0; rs.n_chunks = 0; rs.n_bases = 0; rs.n_mini = 0; rs.sketched = false; rs.dp_n = 0; rs.dp_tiles = 0;
 		rs.h_coff.assign(1, 0); rs.h_len.clear(); rs.names.clear();
 		pt.built = false; pt.n_keys = 0;
+		h->sat_last_valid = false;
 	});
 }
 
 int lqcov_part_build(lqcov_handle *h, int part) { return guard(h, [&] { h->build_part(h->part(part)); }); }
 int lqcov_part_map(lqcov_handle *h, int part) { return guard(h, [&] { h->map_part(h->part(part)); }); }
-int lqcov_part_release(lqcov_handle *h, int part) { return guard(h, [&] { h->part(part); h->parts[part].reset(); }); }
+int lqcov_part_release(lqcov_handle *h, int part) { return guard(h, [&] { h->part(part); h->parts[part].reset(); h->sat_last_valid = false; }); }
 int lqcov_reset(lqcov_handle *h) { return guard(h, [&] { if (!h->have_queries) throw std::logic_error("no queries"); h->reset(); }); }
 int lqcov_sync(lqcov_handle *h) { return guard(h, [&] { LQ_HIP_CHECK(hipStreamSynchronize(h->bstream)); LQ_HIP_CHECK(hipStreamSynchronize(h->stream)); }); }
 int lqcov_reserve_hbm(lqcov_handle *h, uint64_t bytes) { if (!h) return LQCOV_E_ARG; h->hbm_reserve = bytes; return 0; }

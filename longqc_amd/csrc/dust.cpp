@@ -17,7 +17,6 @@ using lq_cabi::select_device;
 #include <condition_variable>
 #include <exception>
 
-static double lq_now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static inline dim3 nblk_d(u64 n, u32 b) { return dim3((unsigned)((n + b - 1) / b)); }
 
 namespace {
@@ -27,19 +26,6 @@ struct DustDev {
 	bool tab_ready = false;
 	~DustDev() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }
 };
-
-void make_q2p_table(double *t)
-{	// lqutils.c:26-49, rebuilt as in engine.cpp (10^(-q/10) to 15 decimals, eight entries one unit higher)
-	static const int up[8] = {34, 39, 58, 62, 67, 71, 72, 82};
-	for (int q = 0; q < 127; ++q) {
-		char buf[64];
-		snprintf(buf, sizeof(buf), "%.15f", pow(10.0, -q / 10.0));
-		long long units = (long long)(buf[0] - '0') * 1000000000000000LL + strtoll(buf + 2, nullptr, 10);
-		for (int j = 0; j < 8; ++j) if (up[j] == q) ++units;
-		snprintf(buf, sizeof(buf), "%lld.%015lld", units / 1000000000000000LL, units % 1000000000000000LL);
-		t[q] = strtod(buf, nullptr);
-	}
-}
 
 void dust_batch(DustDev &D, u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, int W, int T,
                 u32 *masked, double *psum, u32 *qv)
@@ -55,7 +41,7 @@ void dust_batch(DustDev &D, u32 n, const u8 *seq, const u64 *seq_off, const u8 *
 	D.pi.ensure((u64)n_thr * LQ_DUST_PCAP * sizeof(DustPI));
 	D.masked.ensure(n * 4 + 4); D.psum.ensure(n * 8 + 8); D.qv.ensure(n * 4 + 4);
 	if (!D.tab_ready) {
-		double tab[127]; make_q2p_table(tab);
+		double tab[127]; lq_make_q2p(tab);
 		D.q2p.ensure(127 * 8);
 		LQ_HIP_CHECK(hipMemcpyAsync(D.q2p.p, tab, sizeof(tab), hipMemcpyHostToDevice, D.stream));
 		LQ_HIP_CHECK(hipStreamSynchronize(D.stream));

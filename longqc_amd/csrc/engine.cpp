@@ -40,8 +40,6 @@ template <class T> static void d2h(T *dst, const T *src, size_t n, hipStream_t s
 }
 static void dzero(void *p, size_t bytes, hipStream_t s) { if (bytes) LQ_HIP_CHECK(hipMemsetAsync(p, 0, bytes, s)); }
 static void check_launch() { LQ_HIP_CHECK(hipGetLastError()); }
-#include <chrono>
-static double lq_now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // LQCOV_TIMELINE=1: host times (ms since the handle's last reset) at the points where a thread has just waited for its stream --
 // what a step's critical path is made of, without a profiler in the way (rocprofv3 serialises dispatches and stretches the picture)
 static const bool lq_timeline = getenv("LQCOV_TIMELINE") != nullptr;
@@ -110,15 +108,8 @@ void Knobs::read_env()
 	reg_walker = !is("LQCOV_WALK", "solo");
 	ckpt = !is("LQCOV_CKPT", "0");
 	ckpt3 = num("LQCOV_CKPT3", 1) > 0;
-	prune = num("LQCOV_PRUNE", 1) > 0;
-	plan_lazy = num("LQCOV_PLAN_LAZY", 0) > 0;
-	lazy_batches = (int)std::min<long>(16, std::max<long>(1, num("LQCOV_LAZY_BATCHES", 1)));
-	sketch_grid = (u32)std::min<long long>(std::max<long long>(num("LQCOV_SKETCH_GRID", 1L << 22), 1), 1L << 22);
-	build_prio = num("LQCOV_BUILD_PRIO", 1) > 0;
-	ck_unit = (u32)std::max<long long>(num("LQCOV_CK_UNIT", 65536), 64); ck_unit_many = (u32)std::max<long long>(num("LQCOV_CK_UNIT_MANY", 8192), 64);
 	sort_tile = (u32)std::max<long>(0, num("LQCOV_SORT_TILE", 0)); if (sort_tile && sort_tile < 64) sort_tile = 64;
 	walk_shift = (u32)std::min<long>(16, std::max<long>(0, num("LQCOV_WALK_SHIFT", 0)));
-	walk_grid = (u32)std::max<long>(64, num("LQCOV_WALK_GRID", 1L << 18));
 	chain_wave_min = (int)std::max<long>(0, num("LQCOV_CHAIN_WAVE_MIN", 0));
 	chain_cap = (int)num("LQCOV_CHAIN_CAP", 128);
 	run_stage = (u32)std::max<long>(1, num("LQCOV_RUN_STAGE", LQ_RUN_STAGE));
@@ -126,9 +117,6 @@ void Knobs::read_env()
 	ps_key64 = num("LQCOV_PS_KEY64", 0) != 0;
 	sketch_wgen = num("LQCOV_SKETCH_WGEN", 0) != 0;
 	upload_amb = num("LQCOV_UPLOAD_AMB", 0) != 0;
-	sketch_key = num("LQCOV_SKETCH_KEY", 1) != 0;
-	emit_grid = (u32)std::min<long>(1L << 22, std::max<long>(1, num("LQCOV_EMIT_GRID", 1L << 22)));
-	sketch_list = num("LQCOV_SKETCH_LIST", 1) != 0;
 	sketch_fast = num("LQCOV_SKETCH_FAST", 1) != 0;
 #ifndef LQ_EMU
 	lq_trace_launches = (int)num("LQCOV_TRACE_LAUNCHES", 0);
@@ -139,11 +127,9 @@ void Knobs::read_env()
 	sketch_machine_only = is("LQCOV_SKETCH", "machine");
 	upload_slices = (u32)std::min<long>(8, std::max<long>(1, num("LQCOV_UPLOAD_SLICES", 4)));
 	upload_min_chunks = (u64)std::max<long>(1, num("LQCOV_UPLOAD_MIN_CHUNKS", 1L << 16));
-	ps_grid = (u32)std::max<long>(64, num("LQCOV_PS_GRID", 512));
 	tile_grid = (u32)std::max<long>(64, num("LQCOV_TILE_GRID", 4096));
 	ps_passes = (u32)std::min<long>(16, std::max<long>(0, num("LQCOV_PS_PASSES", 2))) & ~1u;
 	ties_klib = is("LQCOV_TIES", "klib") || all_klib;
-	walk_cu_mask = getenv("LQCOV_WALK_CU_MASK") ? (u32)strtoul(getenv("LQCOV_WALK_CU_MASK"), 0, 16) : 0x11111111u; if (!walk_cu_mask) walk_cu_mask = 0xffffffffu;
 	filter = num("LQCOV_FILTER", 1) != 0;
 	parse_threads = (int)std::min<long>(256, std::max<long>(0, num("LQCOV_PARSE_THREADS", 0)));
 	parse_piece = (u64)std::max<long>(64, num("LQCOV_PARSE_PIECE", 32L << 20));
@@ -178,9 +164,9 @@ lqcov_handle::lqcov_handle(const lqcov_params &p, int dev) : P(p), device(dev)
 		// are thousands of single-lane waves that live for milliseconds and hold every wave slot they are given.  Round 5's trace:
 		// the sketch of part 2 stretched from 33 to 164 ms under them and its plan ended after the lanes were done with part 1 -- the
 		// build side had become the critical path.  Its streams get the queue priority that lets their blocks take the slots that
-		// free up first (LQCOV_BUILD_PRIO=0: plain streams).
+		// free up first.
 		int lo = 0, hi = 0;
-		if (K.build_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo) {
+		if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi < lo) {
 			LQ_HIP_CHECK(hipStreamCreateWithPriority(&bstream, hipStreamDefault, hi));
 			LQ_HIP_CHECK(hipStreamCreateWithPriority(&cstream, hipStreamDefault, hi));
 		} else {
@@ -480,11 +466,11 @@ void lqcov_handle::sketch_dp_launch(ReadSetDev &rs, u64 tile0, u64 tile1)
 	SkParams sp; sp.k = P.k; sp.w = P.w; sp.hpc = P.hpc; sp.mask = (1ULL << 2 * P.k) - 1; sp.shift1 = 2 * (P.k - 1);
 	const u64 nt = tile1 - tile0;
 	StageTimer t(this, stream, "k_sketch_dp_mask", nt * LQ_DPT_CH * (LQ_CHUNK_WORDS * 12 + 17));
-#define LQ_DPM(HT, W) LQ_LAUNCH((k_sketch_dp_mask<HT, W>), (u32)std::min<u64>(nt, K.sketch_grid), LQ_DPT_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), rs.d_len.as<u32>(), \
+#define LQ_DPM(HT, W) LQ_LAUNCH((k_sketch_dp_mask<HT, W>), (u32)std::min<u64>(nt, LQ_DPT_GRID), LQ_DPT_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), rs.d_len.as<u32>(), \
 		sk_toff.as<u64>(), sk_trid.as<u32>(), rs.n, tile0, tile1, sp, sk_owned.as<u8>(), sk_mask.as<u32>(), sk_flag.as<u32>())
 	const int wc = K.sketch_wgen ? 0 : P.w;                       // the presets' windows as compile-time constants
 	if (K.sketch_fast && !K.sketch_wgen && P.k == 12 && (P.w == 5 || P.w == 10)) {   // LongQC's own -k 12 -w 5: k and w as constants (LQCOV_SKETCH_FAST=0: the general kernel)
-#define LQ_DPF(KK, WW) LQ_LAUNCH((k_sketch_dp_fast<KK, WW>), (u32)std::min<u64>(nt, K.sketch_grid), LQ_DPT_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), rs.d_len.as<u32>(), \
+#define LQ_DPF(KK, WW) LQ_LAUNCH((k_sketch_dp_fast<KK, WW>), (u32)std::min<u64>(nt, LQ_DPT_GRID), LQ_DPT_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), rs.d_len.as<u32>(), \
 		sk_toff.as<u64>(), sk_trid.as<u32>(), rs.n, tile0, tile1, sk_owned.as<u8>(), sk_mask.as<u32>(), sk_flag.as<u32>())
 		if (P.w == 5) LQ_DPF(12, 5); else LQ_DPF(12, 10);
 #undef LQ_DPF
@@ -558,7 +544,7 @@ void lqcov_handle::sketch(ReadSetDev &rs, bool rid_in_y)
 					fprintf(stderr, "[sketch] %llu of %llu chunks decided data-parallel\n", (unsigned long long)n_own, (unsigned long long)nc);
 				}
 			}
-			if (dp && K.sketch_list && nc < 0xffffffffULL) {
+			if (dp && nc < 0xffffffffULL) {
 				sk_ulist.ensure(nc * 4 + 4);                             // (entry nc: the count)
 				dzero(sk_ulist.as<u32>() + nc, 4, stream);
 				LQ_LAUNCH(k_sketch_unowned, nblk(nc, 256), 256, stream, dp_owned, nc, sk_ulist.as<u32>(), sk_ulist.as<u32>() + nc); check_launch();
@@ -592,8 +578,8 @@ void lqcov_handle::sketch(ReadSetDev &rs, bool rid_in_y)
 			StageTimer t(this, stream, "k_sketch_emit_mask", nc * 24 + rs.n_mini * (16 + 4));
 			// (a part's minimizers: the hash alone as well, where it fits 32 bits -- the index sort's key, which k_sort_keys otherwise makes from x)
 			u32 *okey = nullptr;
-			if (rid_in_y && 2 * P.k <= 32 && K.sketch_key) { ix_key.ensure(rs.n_mini * 8); okey = ix_key.as<u32>(); rs.key_stamp = ix_key_stamp = ++ix_key_seq; }
-			LQ_LAUNCH(k_sketch_emit_mask, (u32)std::min<u64>((nc + LQ_EM_CH - 1) / LQ_EM_CH, K.emit_grid), LQ_EM_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), sk_grid.as<u32>(), rs.n, nc, sp, (int)rid_in_y,
+			if (rid_in_y && 2 * P.k <= 32) { ix_key.ensure(rs.n_mini * 8); okey = ix_key.as<u32>(); rs.key_stamp = ix_key_stamp = ++ix_key_seq; }
+			LQ_LAUNCH(k_sketch_emit_mask, (u32)std::min<u64>((nc + LQ_EM_CH - 1) / LQ_EM_CH, LQ_EM_GRID), LQ_EM_THREADS, stream, rs.codes.as<u64>(), rs.amb.as<u32>(), rs.d_coff.as<u64>(), sk_grid.as<u32>(), rs.n, nc, sp, (int)rid_in_y,
 			          sk_mask.as<u32>(), off.as<u64>(), rs.mx.as<u64>(), rs.my.as<u64>(), okey);
 			check_launch();
 		} else {
@@ -628,7 +614,7 @@ void lqcov_handle::export_minimizers(ReadSetDev &rs, u64 *x_dev, u64 *y_dev, u32
 // meanQ's table (lqutils.c:26-49): 127 15-decimal literals for 10^(-q/10), Q0..Q126.  They are 10^(-q/10)
 // rounded to 15 decimals, except that eight entries (Q34, 39, 58, 62, 67, 71, 72, 82) are one unit of the
 // 15th decimal higher in the reference; rebuilt here from that description.
-static void make_q2p(double *t)
+void lq_make_q2p(double *t)
 {
 	static const int up[8] = {34, 39, 58, 62, 67, 71, 72, 82};
 	for (int q = 0; q < 127; ++q) {
@@ -708,7 +694,7 @@ void lqcov_handle::set_queries(u32 n, const u8 *seq_in, const u64 *seq_off_in, c
 		dq.ensure(nb + 16); dso.ensure((n + 1) * 8); dtab.ensure(127 * 8);
 		std::vector<u64> soff(n + 1);
 		for (u32 i = 0; i <= n; ++i) soff[i] = seq_off[i] - seq_off[0];
-		double tab[127]; make_q2p(tab);
+		double tab[127]; lq_make_q2p(tab);
 		h2d(dq.as<u8>(), qual + seq_off[0], nb, stream);
 		h2d(dso.as<u64>(), soff.data(), n + 1, stream);
 		h2d(dtab.as<double>(), tab, 127, stream);
@@ -766,7 +752,7 @@ void lqcov_handle::reset()
 	if (!distributed) mid_occ = -1;
 	stat_sens_runs = 0; stat_p2_queries = 0; stat_p2_anchors = 0;
 	for (auto &v : stat_tie_why) v = 0;
-	sat_cnt.clear(); stat_sat_chains = 0;
+	sat_cnt.clear(); stat_sat_chains = 0; sat_last_valid = false;
 	finished = false;
 	LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	if (lq_timeline) { lq_timeline_t0 = lq_now_s(); lq_tl("main", 0, "reset"); }
@@ -781,6 +767,7 @@ void lqcov_handle::build_index(Part &pt)
 	ReadSetDev &rs = pt.rs;
 	const u64 M = rs.n_mini;
 	ix_owner = &pt;
+	sat_last_valid = false;
 	pt.n_keys = 0; pt.cap_bits = 4;
 	pt.pos.ensure(M * 8 + 8);
 	// same-name targets per query (self diagonal, lqmap.c:180-186) and -X's name ranks: host work on the read names, done while
@@ -896,9 +883,7 @@ void lqcov_handle::build_index(Part &pt)
 	pt.plan.valid = false;
 	// the part's seed plan right away, on the build stream: under the mapping of the part before when parts are pipelined
 	lq_tl("build", 0, "index done");
-	// (with the lanes idle -- the first part of a job -- nothing hides the filter, the plan's longest stage: it is left to the lanes,
-	// each of which decides its own batch of queries and starts mapping while the next lane decides its batch: map_part)
-	if (K.plan_ahead && have_queries && mid_occ > 0 && !distributed) plan_part(pt, stream, prim, K.plan_lazy && active_maps.load() == 0);
+	if (K.plan_ahead && have_queries && mid_occ > 0 && !distributed) plan_part(pt, stream, prim);
 	// (the build workspaces stay with the handle: repeated builds do not re-allocate, and the mapping lanes size their work
 	// space from what is free once the first part stands -- map_part)
 }
@@ -1132,7 +1117,7 @@ void lqcov_handle::part_sat_records(Part &pt, u32 qi, std::vector<SatRec> &recs,
 {
 	if (qi >= q.n) throw std::invalid_argument("no such query");
 	if (!pt.built) throw std::logic_error("part not built");
-	if (!pt.plan.valid || pt.plan.mid_occ != mid_occ || pt.plan.n_q != q.n || pt.plan.n_qm != q.n_mini || (pt.plan.bucketed && pt.plan.q_begin != 0)) plan_part(pt, stream, prim);   // (as map_part does)
+	if (!plan_usable(pt.plan)) plan_part(pt, stream, prim);   // (as map_part does)
 	swap_plan(pt.plan);
 	struct PlanGuard { lqcov_handle *h; SeedPlan &S; ~PlanGuard() { h->swap_plan(S); } } plan_guard{this, pt.plan};
 	sat_chains(pt, qi, pt.plan.h_aq, pt.plan.h_qmoff, recs, at);
@@ -1214,7 +1199,7 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	if (nj && opt && pt.plan.bucketed) {
 		if (nA) {                                                 // the survivors of the batch's queries (the part's seed plan holds them as records)
 			StageTimer t(this, L.stream, "k_seed_emit_s", nA * 24);
-			LQ_LAUNCH(k_seed_emit_s, nblk(nA, 256), 256, L.stream, L.use_surv ? L.use_surv : surv.as<u64>(), a_base, nA, L.use_aqf ? L.use_aqf : aqf_off.as<u64>(), q0, q1, SeedBits{pt.plan.rec_jb, pt.plan.rec_db},
+			LQ_LAUNCH(k_seed_emit_s, nblk(nA, 256), 256, L.stream, surv.as<u64>(), a_base, nA, aqf_off.as<u64>(), q0, q1, SeedBits{pt.plan.rec_jb, pt.plan.rec_db},
 			          q.mx.as<u64>(), q.my.as<u64>(), q.moff.as<u64>(), q.d_len.as<u32>(), dup.as<u32>(), L.A.as<mm128>());
 			check_launch();
 		}
@@ -1231,7 +1216,7 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	L.ivl.ensure((u64)ivl_cap * sizeof(Ivl));
 	dzero(L.n_ivl.p, 4, L.stream); dzero(L.n_sens.p, 32, L.stream);
 	if (nA) {
-		const u64 *aqb = (opt ? (L.use_aqf ? L.use_aqf : aqf_off.as<u64>()) : aq_off.as<u64>()) + q0;          // batch view of the per-query anchor offsets
+		const u64 *aqb = (opt ? aqf_off : aq_off).as<u64>() + q0;          // batch view of the per-query anchor offsets
 		const u32 *qkb = opt ? qzero.as<u32>() : qklib.as<u32>() + q0;               // (first pass: nobody goes through klib's passes)
 		std::vector<u64> rel; std::vector<u32> hk;
 		if (K.debug_sort) {
@@ -1332,7 +1317,7 @@ static void ps_pass(lqcov_handle *h, MapLane &L, int set, hipStream_t s, u64 nA,
 	const u32 cap_cnt = (u32)std::min<u64>(W.gcnt.cap / 4, 0xfffffff0ULL);
 	// grids: a few blocks per CU striding over the device-side lists.  Most passes of a batch find their list short or empty,
 	// and a launch sized for the worst case still has every one of its blocks placed (LDS and wave slots included) to find that out
-	const u32 g_tiles = (u32)std::min<u64>((nA + LQ_PS_TILE - 1) / LQ_PS_TILE + 1, h->K.ps_grid);
+	const u32 g_tiles = (u32)std::min<u64>((nA + LQ_PS_TILE - 1) / LQ_PS_TILE + 1, LQ_PS_GRID);
 	const u32 g_segs = (u32)std::min<u64>(Ls.cap_big, 256);
 	const u32 nxt = cur ^ 1;
 	const u32 cap_tiles = (u32)std::min<u64>(W.tmap.cap / 4, 0xfffffff0ULL);
@@ -1359,7 +1344,7 @@ static void ps_finish(lqcov_handle *h, MapLane &L, int set, hipStream_t s, u64 n
 	{
 		StageTimer t(h, s, "k_ps_finish<8192>");
 		unsigned long long *tl = (unsigned long long*)(L.sort_cnt.as<u32>() + (set ? LQ_C_FINB1 : LQ_C_FINB0));
-		const u32 g = (u32)std::min<u64>(std::min<u64>(Ls.cap_fin, nA / LQ_PS_FIN_SMALL + 64), h->K.ps_grid / 4);
+		const u32 g = (u32)std::min<u64>(std::min<u64>(Ls.cap_fin, nA / LQ_PS_FIN_SMALL + 64), LQ_PS_GRID / 4);
 		// 1024 threads (measured at configs[2], 4 lanes, round 2: 256-thread blocks 2.40 s per step, 512: 2.25, 1024: 2.1-2.2; round 3: 512 = 1024).
 		// Beside the other lanes' kernels a launch of this kernel takes ~3x its time alone, most of it waiting: with the class
 		// emptied (everything partitioned down to 1024) the empty launches still took 367 ms per step and the step was the same.
@@ -1370,7 +1355,7 @@ static void ps_finish(lqcov_handle *h, MapLane &L, int set, hipStream_t s, u64 n
 	{
 		StageTimer t(h, s, "k_ps_finish<1024>");
 		unsigned long long *tl = (unsigned long long*)(L.sort_cnt.as<u32>() + (set ? LQ_C_FINS1 : LQ_C_FINS0));
-		const u32 g = (u32)std::min<u64>(std::min<u64>(Ls.cap_fin, nA / 16 + 256), h->K.ps_grid * 2);
+		const u32 g = (u32)std::min<u64>(std::min<u64>(Ls.cap_fin, nA / 16 + 256), LQ_PS_GRID * 2);
 		if (k32) LQ_LAUNCH((k_ps_finish<LQ_PS_FIN_SMALL, 256, 8, u32>), g, 256, s, Ls.fin_s, cnt + LQ_P_FIN_S, pd, km, tl);
 		else LQ_LAUNCH((k_ps_finish<LQ_PS_FIN_SMALL, 256, 8, u64>), g, 256, s, Ls.fin_s, cnt + LQ_P_FIN_S, pd, km, tl);
 		check_launch();
@@ -1482,7 +1467,7 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 	if (ns) {
 		u32 *hx = (u32*)L.scr.p, *py = (u32*)((u8*)L.scr.p + nA4);
 		const u32 tile = K.sort_tile ? K.sort_tile : LQ_SORT_TILE;
-		const u32 wgrid = K.walk_grid;
+		const u32 wgrid = LQ_WALK_GRID;
 		L.sort_d.ensure(nA + 256); L.sort_dst.ensure((nA + 1) * 4);
 		L.ck_n.ensure(16);
 		SortSeg *cur = L.segs0.as<SortSeg>(), *nxt = L.segs1.as<SortSeg>();
@@ -1561,7 +1546,7 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 				bool w1 = false, w2 = false;                          // which walker streams got work
 				// (the checkpoint buffers are sized before the fork: a block that the lane's stream allocates after the event the walker
 				// streams wait for would not be ordered before their kernels)
-				const u32 ck_unit = std::max<u32>((ck_small ? K.ck_unit : K.ck_unit_many) >> K.walk_shift, 8);
+				const u32 ck_unit = std::max<u32>((ck_small ? LQ_CK_UNIT : LQ_CK_UNIT_MANY) >> K.walk_shift, 8);
 				const u32 ck_quantum = ck_small ? 1u : (u32)LQ_CKM_Q;   // many buckets: checkpoints come in sub-chains of LQ_CKM_Q (k_ck_chain256)
 				const u32 ck_min_len = wcaps.c[ck3 ? 2 : 3] + 1;
 				const u64 cks_max = std::min<u64>(std::min<u64>(nA / ck_min_len + 1, ns), n_ck_segs), ck_max = nA / ck_unit + (2 + ck_quantum) * cks_max, tiles_max = nA / LQ_CK_TILE + cks_max;
@@ -1636,7 +1621,7 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 				StageTimer t(this, sD, "k_rs_children");
 				LQ_LAUNCH(k_rs_children, (u32)std::min<u64>((u64)ns * 4, 1u << 20), LQ_CHILD_THREADS, sD, cur, cnt + cur_slot, R[rb ^ 1], rb ^ 1, dB, dA, L.hist.as<u32>(), L.mhist.as<u32>(), L.begs.as<u32>(),
 				          nxt, cnt + nxt_slot, const_levels, lists(1), km, (int)K.all_klib, cnt + LQ_C_TILES, cnt + LQ_C_LEN0, wcaps,
-			          L.prune && !K.debug_sort && K.prune ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0});
+			          L.prune && !K.debug_sort ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0});
 				check_launch();
 			}
 			d2h(hl, cnt, LQ_C_N, sD);
@@ -1800,7 +1785,7 @@ bool lqcov_handle::seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u
 		                      c.q_lo, c.q_hi, (unsigned long long)c.hits, (unsigned long long)c.nb, (unsigned long long)c.ne, n_c, (unsigned long long)n_surv, SV.cap / 8);
 		if ((n_surv + n_c) * 8 > SV.cap) {
 			try { grow_keep(SV, n_surv * 8, (n_surv + n_c) * 8, s); }
-			catch (const std::runtime_error &) { (void)hipGetLastError(); SV.release(); return false; }   // (no room for the survivors: the part is mapped without the filter)
+			catch (const LqOutOfMemory &) { (void)hipGetLastError(); SV.release(); return false; }   // (no room for the survivors: the part is mapped without the filter)
 		}
 		LQ_LAUNCH(k_seed_collect, (u32)c.nb, 64, s, W.bd.as<SeedBk>(), W.rec.as<u64>(), W.scnt.as<u32>(), W.soff.as<u32>(), n_surv, J.base, SV.as<u64>(), J.aqf_off); check_launch();
 		add_stage_bytes("k_seed_decide", (u64)n_c * 8);
@@ -1836,10 +1821,10 @@ bool lqcov_handle::seed_group(Part &pt, SeedPlan &S, bool swapped, hipStream_t s
 
 // ---- map every query against one part (lqmap.c:207-326) -----------------------------------------
 // a part's seed plan (SeedPlan, engine.hpp) on stream s with scan scratch pr
-void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr, bool defer_filter)
+void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr)
 {
 	SeedPlan &S = pt.plan;
-	S.valid = false; S.lazy = false;
+	S.valid = false;
 	const u32 n_q = q.n;
 	const u64 n_qm = q.n_mini;
 	S.n_q = n_q; S.n_qm = n_qm; S.mid_occ = mid_occ; S.nA_total = 0; S.n_mp_total = 0; S.n_written = 0;
@@ -1907,13 +1892,14 @@ void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr, bool defer_filte
 		if (n_min >= 2 && n_min <= 15 && nA_total && jb + db + 1 + rb <= 64 && db <= 31 && jb <= 31 && max_hits < 0x7fff0000ULL) {
 			S.rec_nmin = n_min; S.rec_jb = jb; S.rec_db = db;
 			// (measured and dropped, round 5: the filter run batch by batch inside map_part, each lane starting as soon as its batch is
-			// decided -- 586-588 ms per step at configs[2] against 576: beside the lanes' kernels the filter's take three times as long)
-			// (an allocation that fails inside the filter -- its bucket buffer is up to 8 GB -- leaves the part without one: every hit is written)
-			if (defer_filter) { S.lazy = true; S.bucketed = true; S.q_begin = 0; S.q_end = n_q; S.h_aqf = S.h_aq; S.n_written = 0; }
-			else {
-				try { S.bucketed = seed_group(pt, S, false, s, pr, 0); }
-				catch (const std::runtime_error &) { (void)hipGetLastError(); S.surv.release(); for (DBuf *b : { &seed_ws.rec, &seed_ws.cnt, &seed_ws.off, &seed_ws.bd }) b->release(); S.bucketed = false; }
-			}
+			// decided -- 586-588 ms per step at configs[2] against 576: beside the lanes' kernels the filter's take three times as long.
+			// Round 6, for the first part of a job only, whose plan nothing else could hide -- every lane ran the filter for its own batch
+			// of queries on its own stream, the next lane deciding under this one's mapping: 425 ms per step against 399.  Beside a mapping
+			// lane and the next part's sketch the filter's kernels take twice as long (60 + 55 + 56 ms for the three batches, 85 ms for all
+			// of them alone) and the last lane starts later than it does after a whole plan; two / three batches per lane: 449 / 483 ms)
+			// (running out of memory inside the filter -- its bucket buffer is up to 8 GB -- leaves the part without one: every hit is written)
+			try { S.bucketed = seed_group(pt, S, false, s, pr, 0); }
+			catch (const LqOutOfMemory &) { (void)hipGetLastError(); S.surv.release(); seed_ws.release_large(); S.bucketed = false; }
 		}
 		if (!S.bucketed) {
 			S.q_begin = 0; S.q_end = n_q;
@@ -1924,6 +1910,11 @@ void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr, bool defer_filte
 	}
 	LQ_HIP_CHECK(hipStreamSynchronize(s));
 	S.valid = true;
+}
+
+bool lqcov_handle::plan_usable(const SeedPlan &S) const
+{
+	return S.valid && S.mid_occ == mid_occ && S.n_q == q.n && S.n_qm == q.n_mini && S.h_aqf.empty() == K.ties_klib && !(S.bucketed && S.q_begin != 0);
 }
 
 // the plan's buffers <-> the handle's work buffers of the same names
@@ -1937,7 +1928,7 @@ void lqcov_handle::swap_plan(SeedPlan &S)
 void lqcov_handle::map_part(Part &pt)
 {
 	if (!pt.built) throw std::logic_error("part not built");
-	finished = false;
+	finished = false; sat_last_valid = false;
 	const u32 n_q = q.n;
 	const u64 n_qm = q.n_mini;
 	last_n_anchors = 0;
@@ -1945,12 +1936,10 @@ void lqcov_handle::map_part(Part &pt)
 	if (n_q == 0) return;
 	// the part's seed plan: made with its index (build_index), or here if it was not (no queries then) or no longer fits (mid_occ
 	// set afterwards: the parts of a round of PartRunner are built before part 0's mid_occ arrives)
-	if (!pt.plan.valid || pt.plan.mid_occ != mid_occ || pt.plan.n_q != n_q || pt.plan.n_qm != n_qm || pt.plan.h_aqf.empty() != K.ties_klib || (pt.plan.bucketed && pt.plan.q_begin != 0)) plan_part(pt, stream, prim);
+	if (!plan_usable(pt.plan)) plan_part(pt, stream, prim);
 	lq_tl("main", 0, "map_part begins");
 	swap_plan(pt.plan);
 	struct PlanGuard { lqcov_handle *h; SeedPlan &S; ~PlanGuard() { h->swap_plan(S); } } plan_guard{this, pt.plan};
-	++active_maps;
-	struct ActiveGuard { lqcov_handle *h; ~ActiveGuard() { --h->active_maps; } } active_guard{this};
 	const std::vector<u64> &h_aq = pt.plan.h_aq, &h_qmoff = pt.plan.h_qmoff, &h_aqf = pt.plan.h_aqf;
 	const u64 nA_total = pt.plan.nA_total, n_mp_total = pt.plan.n_mp_total;
 	last_n_anchors = nA_total;
@@ -1997,7 +1986,7 @@ void lqcov_handle::map_part(Part &pt)
 			// (Round 3: a different quarter of the CUs per lane, or 128 / 192 CUs instead of 64: no change, 1.69-1.71 s per step whatever
 			// the mask; no mask at all: 2.03 s.)
 			uint32_t mask[8];
-			for (int i = 0; i < 8; ++i) mask[i] = K.walk_cu_mask;
+			for (int i = 0; i < 8; ++i) mask[i] = LQ_WALK_CU_MASK;
 			if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW)); }
 			if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW2, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW2)); }
 		}
@@ -2027,7 +2016,7 @@ void lqcov_handle::map_part(Part &pt)
 			lq_alloc_stream = stream;
 			struct AllocGuard { ~AllocGuard() { lq_alloc_stream = nullptr; } } alloc_guard;
 			try { Lp->arena_buf.ensure(need); Lp->arena.base = Lp->arena_buf.as<char>(); Lp->arena.size = Lp->arena_buf.cap; }
-			catch (const std::runtime_error &) { (void)hipGetLastError(); }   // (no room for it in one piece: the lane allocates buffer by buffer)
+			catch (const LqOutOfMemory &) { (void)hipGetLastError(); }   // (no room for it in one piece: the lane allocates buffer by buffer)
 		}
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	}
@@ -2049,44 +2038,11 @@ void lqcov_handle::map_part(Part &pt)
 		false;
 #endif
 	// runs the batches on the lanes
-	const bool lazy = opt && pt.plan.lazy && pt.plan.bucketed;
-	std::atomic<u64> lazy_written{0};
-	// one batch on one lane.  A lazy plan (the first part of a job): the lane first decides which of its queries' seed hits can reach
-	// a chain -- the filter of kernels_seed.hpp on the lane's own stream, one lane at a time (they share its work space) -- into a
-	// survivor list of its own, then maps them; the next lane decides its batch under this one's mapping.
-	auto one_batch = [&](MapLane &L, u32 q0, u32 q1) {
-		if (!lazy) { map_batch(L, pt, q0, q1, h_aq, h_aqf, h_qmoff, dbg); return; }
-		int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_;
-		L.aqf_l.ensure(((u64)n_q + 1) * 8);
-		for (u32 qb = q0; qb < q1; ) {
-			SeedJob J;
-			J.hit_start = hit_start.as<u64>(); J.hit_n = hit_n.as<u32>(); J.keep = keep.as<u32>();
-			J.aqf_off = L.aqf_l.as<u64>(); J.h_qmoff = &h_qmoff; J.h_aqf = &L.h_aqf_l;
-			J.surv = &L.surv_l; J.base = 0; J.room_hint = (h_aq[q1] - h_aq[qb]) / 16;
-			J.q_begin = qb; J.q_stop = q1;
-			bool ok = false;
-			try { ok = seed_filter(pt, L.stream, L.prim, seed_ws, pt.plan.rec_nmin, pt.plan.rec_jb, pt.plan.rec_db, J); }
-			catch (const std::runtime_error &) { (void)hipGetLastError(); ok = false; }
-			if (!ok) throw std::runtime_error("seed filter: no room for a batch's survivors (LQCOV_PLAN_LAZY=0 maps the part without the filter instead)");
-			lq_tl("lane", lane_id, "batch decided, survivors", (double)J.n_surv);
-			lazy_written += J.n_surv;
-			L.use_surv = L.surv_l.as<u64>(); L.use_aqf = L.aqf_l.as<u64>();
-			struct UseGuard { MapLane &L; ~UseGuard() { L.use_surv = nullptr; L.use_aqf = nullptr; } } use_guard{L};
-			// (what the filter left of [qb, q_end), in pieces the lane's work space holds)
-			for (u32 a = qb; a < J.q_end; ) {
-				u32 b = a + 1;
-				while (b < J.q_end && L.h_aqf_l[b + 1] - L.h_aqf_l[a] <= anchor_budget) ++b;
-				map_batch(L, pt, a, b, h_aq, L.h_aqf_l, h_qmoff, dbg);
-				a = b;
-			}
-			qb = J.q_end;
-		}
-	};
 	auto run_batches = [&](const std::vector<std::pair<u32, u32>> &batches) {
 		const bool concurrent = can_thread && n_lanes > 1 && batches.size() > 1;
 		if (!concurrent) {
 			for (size_t i = 0; i < batches.size(); ++i) {
-				one_batch(*lanes[i % n_lanes], batches[i].first, batches[i].second);
+				map_batch(*lanes[i % n_lanes], pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
 			}
 			for (auto &L : lanes) LQ_HIP_CHECK(hipStreamSynchronize(L->stream));
 			return;
@@ -2113,7 +2069,7 @@ void lqcov_handle::map_part(Part &pt)
 					for (;;) {
 						const size_t i = next.fetch_add(1);
 						if (i >= batches.size()) break;
-						one_batch(L, batches[i].first, batches[i].second);
+						map_batch(L, pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
 					}
 					LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
 				} catch (...) { errs[li] = std::current_exception(); next.store(batches.size()); gate_cv.notify_all(); }
@@ -2124,7 +2080,8 @@ void lqcov_handle::map_part(Part &pt)
 	// as few batches as the work space allows, a multiple of the lane count, of about equal totals of `off` (the anchors the first
 	// pass writes, or the seed hits): every batch has a serial critical path that does not shrink with the batch.  (Cutting the
 	// last round finer was measured on MI355X at configs[2] in round 3: 1.75-1.78 s per step against 1.68-1.70 s; round 4: the
-	// queries in six chunks with the survivors of a chunk decided under the mapping of the chunk before: 1160 ms per step against 888.)
+	// queries in six chunks with the survivors of a chunk decided under the mapping of the chunk before: 1160 ms per step against 888;
+	// round 6: one batch per lane cut by the seed hits, each lane running the filter for its own batch -- see plan_part.)
 	auto cut_batches = [&](const std::vector<u64> &off, u32 g_begin, u32 g_end) {
 		std::vector<std::pair<u32, u32>> batches;
 		const u64 total = off[g_end] - off[g_begin];
@@ -2145,24 +2102,6 @@ void lqcov_handle::map_part(Part &pt)
 		return batches;
 	};
 	bool regrouped = false;
-	if (lazy) {
-		// batches of about equal seed hits, one per lane (the filter's cost and the second pass go by the hits)
-		std::vector<std::pair<u32, u32>> batches;
-		const u64 total = h_aq[n_q] - h_aq[0];
-		const u32 nb = (u32)std::max<int>(1, n_lanes * K.lazy_batches);
-		u32 q0 = 0;
-		for (u32 b = 0; b < nb && q0 < n_q; ++b) {
-			const u64 lim = h_aq[q0] + (total - (h_aq[q0] - h_aq[0])) / (nb - b);
-			u32 q1 = q0 + 1;
-			while (q1 < n_q && h_aq[q1 + 1] <= lim) ++q1;
-			if (b + 1 == nb) q1 = n_q;
-			batches.emplace_back(q0, q1);
-			q0 = q1;
-		}
-		run_batches(batches);
-		pt.plan.n_written = lazy_written.load(); last_n_written = pt.plan.n_written;
-		pt.plan.valid = false;                                      // (no survivor list to map the part from again: the next map_part plans anew)
-	} else
 	// The plan holds the survivors of a group of queries (all of them, unless survivors abound: SeedPlan::q_end); the group's batches
 	// are mapped, then the next group is planned -- with every lane drained, on the handle's own stream.
 	for (u32 g_begin = 0, g_end = n_q; ; ) {
@@ -2172,7 +2111,7 @@ void lqcov_handle::map_part(Part &pt)
 		regrouped = true;
 		bool ok = false;
 		try { ok = seed_group(pt, pt.plan, true, stream, prim, g_end); }
-		catch (const std::runtime_error &) { (void)hipGetLastError(); for (DBuf *b : { &seed_ws.rec, &seed_ws.cnt, &seed_ws.off, &seed_ws.bd }) b->release(); ok = false; }
+		catch (const LqOutOfMemory &) { (void)hipGetLastError(); seed_ws.release_large(); ok = false; }
 		if (!ok) {                                                  // (no room: the rest of the part without the filter)
 			pt.plan.bucketed = false;
 			pt.plan.h_aqf = pt.plan.h_aq;

@@ -33,21 +33,10 @@ struct Knobs {
 	u32 ps_shift = 0;                     // LQCOV_PS_SHIFT: shrinks the size classes of the parallel sort (tests)
 	bool reg_walker = true;               // LQCOV_WALK=solo: no register-lane walker
 	bool ckpt = true, ckpt3 = true;       // LQCOV_CKPT=0: no checkpointed walks; LQCOV_CKPT3=0: the 65-160 k class is walked whole
-	int lazy_batches = 1;                 // LQCOV_LAZY_BATCHES: batches per lane of a lazy plan
-	bool plan_lazy = false;               // LQCOV_PLAN_LAZY=1: the first part's seed filter is left to the mapping lanes, each deciding its own batch of queries before it maps them (the next lane decides under this one's mapping).  Measured in round 6 at configs[2]: 425 ms per step against 399 -- beside a mapping lane and the next part's sketch the filter's kernels take twice as long (60 + 55 + 56 ms for the three batches, 85 ms for all of them alone) and the last lane starts later than it does after a whole plan; two / three batches per lane: 449 / 483 ms.  Round 5 had found the same with the filter inside map_part (586 vs 576 ms)
-	bool prune = true;                    // LQCOV_PRUNE=0: the second pass sorts every bucket of its queries (rounds 4-5), not only those that hold a listed run
-	u32 sketch_grid = 1u << 22;           // LQCOV_SKETCH_GRID: blocks of k_sketch_dp_mask (a block strides over the tiles)
-	bool build_prio = true;               // LQCOV_BUILD_PRIO=0: the build side's streams without the higher queue priority
-	u32 ck_unit = 65536, ck_unit_many = 8192;   // LQCOV_CK_UNIT / LQCOV_CK_UNIT_MANY: elements per checkpoint, passes of up to 16 / up to 256 buckets (configs[2], ms per step: 16384 / 4096: 502, 65536 / 4096: 502, 65536 / 8192: 491, 65536 / 16384: 491, 131072 / 8192: 494)
 	u32 sort_tile = 0;                    // LQCOV_SORT_TILE: anchors per tile of the sort's streaming kernels (0 = LQ_SORT_TILE)
 	u32 walk_shift = 0;                   // LQCOV_WALK_SHIFT: shrinks the walker size classes and the checkpoint spacing (tests)
-	u32 walk_grid = 1u << 18;             // LQCOV_WALK_GRID: cap on resident walker waves
-	u32 walk_cu_mask = 0x11111111u;       // LQCOV_WALK_CU_MASK (hex, repeated over the 256 CUs): the CUs the walkers' streams may use
 	int chain_wave_min = 0, chain_cap = 128;   // LQCOV_CHAIN_WAVE_MIN (0 = LQ_CHAIN_WAVE_MIN), LQCOV_CHAIN_CAP
 	bool sketch_fast = true;              // LQCOV_SKETCH_FAST=0: k_sketch_dp_mask although k_sketch_dp_fast applies (-k 12 with -w 5 or 10; tests, A/B)
-	bool sketch_list = true;              // LQCOV_SKETCH_LIST=0: the state machine looks for the chunks the data-parallel kernel left in every wave of 64 consecutive chunks (rounds 3-5) instead of taking them from a list
-	bool sketch_key = true;               // LQCOV_SKETCH_KEY=0: the index sort's keys by k_sort_keys from x instead of by k_sketch_emit_mask
-	u32 emit_grid = 1u << 22;             // LQCOV_EMIT_GRID: blocks of k_sketch_emit_mask (a block strides over the groups of 32 chunks)
 	bool upload_amb = false;              // LQCOV_UPLOAD_AMB=1: lqcov_run_files uploads the ambiguity words of a part although none of its reads holds an ambiguous base (rounds 2-5)
 	bool sketch_wgen = false;             // LQCOV_SKETCH_WGEN=1: k_sketch_dp_mask with the window read at run time although it is 5 or 10 (tests, A/B)
 	bool ps_key64 = false;                // LQCOV_PS_KEY64=1: the finishing kernels' 64-bit key shape although 32 bits would do (tests: parts with more than 2^40 (target, position) pairs are out of their reach)
@@ -58,7 +47,6 @@ struct Knobs {
 	u32 sketch_kpt = 4;                   // LQCOV_SKETCH_KPT: chunks per thread of the sketch state machine
 	u32 ps_passes = 2;                    // LQCOV_PS_PASSES: partition passes issued without looking (even; the tail looks at the counter and does the rest).  Two cover queries of up to ~500 M anchors against 65 536 targets; measured 4 vs 2 at configs[2]: 1.71-1.77 vs 1.69-1.71 s per step
 	u32 tile_grid = 4096;                 // LQCOV_TILE_GRID: blocks of klib's tile kernels (histogram, scatter)
-	u32 ps_grid = 512;                   // LQCOV_PS_GRID: blocks of the parallel sort's tile kernels (the finishing kernels: a quarter / twice that; twice as many blocks for them: no change, measured with the 64-register kernels)
 	u64 upload_min_chunks = 1u << 16;     // LQCOV_UPLOAD_MIN_CHUNKS: only read sets of that many 128-base chunks go up in slices (tests lower it)
 	u32 upload_slices = 4;                // LQCOV_UPLOAD_SLICES (1..8): packed reads go up in slices, the data-parallel sketch kernel takes a slice while the next one is on its way (1: one copy, then the sketch)
 	bool sketch_machine_only = false;     // LQCOV_SKETCH=machine: the state machine decides every chunk (no data-parallel kernel)
@@ -115,8 +103,6 @@ struct SeedPlan {
 	i32 mid_occ = -2; u32 n_q = 0; u64 n_qm = 0;
 	u32 rec_jb = 0, rec_db = 0, rec_nmin = 0;   // the records' bit layout (SeedBits); the filter's n_min
 	u32 q_begin = 0, q_end = 0;           // the queries whose survivors the plan holds right now (a group of chunks; all of them unless survivors abound)
-	bool lazy = false;                    // the survivors are not made yet: every mapping lane runs the filter for its own batch of queries before it maps
-	                                      // them (map_part) -- the first part of a job, whose plan nothing else could hide (round 6)
 	bool bucketed = false;                // false: the first pass writes every hit (no filter asked for, or the records do not fit 64 bits): h_aqf == h_aq
 	bool valid = false;
 };
@@ -134,7 +120,10 @@ struct SeedJob {
 };
 
 // work space of the seed filter: one plan is made at a time
-struct SeedWork { DBuf hlen, h_off, hq_off, qg, segs, bq, cnt, off, scnt, soff, rec, has, bd, big; };
+struct SeedWork {
+	DBuf hlen, h_off, hq_off, qg, segs, bq, cnt, off, scnt, soff, rec, has, bd, big;
+	void release_large() { for (DBuf *b : { &rec, &cnt, &off, &bd }) b->release(); }   // the buffers that go by the hits of a chunk (rec: up to 8 GB): handed back when the filter ran out of memory
+};
 
 struct Part {
 	bool live = false, built = false;
@@ -165,8 +154,6 @@ struct MapLane {
 	PsWork ps[2];
 	Prim prim;
 	bool gate_passed = false;             // this batch has reached its long walks (see map_part)
-	DBuf surv_l, aqf_l; std::vector<u64> h_aqf_l;   // a lazy plan (SeedPlan::lazy): the survivors of the lane's own batch and their per-query offsets
-	const u64 *use_surv = nullptr, *use_aqf = nullptr;   // ... which map_batch then reads instead of the plan's
 	bool prune = false; u32 prune_n_want = 0, prune_n_sub = 0;   // second pass: klib's levels drop the buckets without a listed run (k_rs_children; L.want, L.sub_off, L.sub_q)
 	DBuf sens, n_sens, want, sub_q, sub_off, sub_klib;   // runs left to the second pass (map_batch), its queries
 	DBuf A, B, R0, segs0, segs1, n_segs, hist, begs;     // A: anchors (final home), B: originals of the klib queries / other buffer of the parallel sort, R0: records (R1 lives in scr)
@@ -241,7 +228,8 @@ struct lqcov_handle {
 	DBuf sat_rec, sat_at, sat_n;
 	u64 stat_sat_chains = 0;
 	std::vector<SatRec> sat_last_recs; std::vector<u32> sat_last_at;   // lqcov_part_sat_records: the records between the sizing call and the copying one
-	int sat_last_part = -1; u32 sat_last_query = 0; bool sat_last_valid = false;
+	int sat_last_part = -1; u32 sat_last_query = 0;
+	std::atomic<bool> sat_last_valid{false};   // ... which describe the part as it was: dropped by reset() and whenever a part is cleared, released, built or mapped (the build thread may be the one)
 	u64 last_n_written = 0;               // anchors the first pass wrote against the last part
 	std::atomic<u64> stat_tie_why[6] = {};   // listed runs by the first reason that listed them (lq_tie_list: skip pending, member counts as a skip, top score twice, scan broke off, peak tie, other), since reset()
 	std::atomic<u64> stat_sens_runs{0}, stat_p2_queries{0}, stat_p2_anchors{0};   // second pass, since reset(): runs, queries, anchors
@@ -296,8 +284,8 @@ struct lqcov_handle {
 	void build_index(Part &pt);
 	void build_part(Part &pt);
 	void open_gate();
-	void plan_part(Part &pt, hipStream_t s, Prim &pr, bool defer_filter = false);
-	std::atomic<int> active_maps{0};      // map_part calls in progress: a part built meanwhile gets its whole plan ahead of time, a part built with the lanes idle a lazy one
+	void plan_part(Part &pt, hipStream_t s, Prim &pr);
+	bool plan_usable(const SeedPlan &S) const;   // the plan was made for these queries, this mid_occ and tie order, and holds its first group of survivors: the part can be mapped from it
 	bool seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u32 n_min, u32 jb, u32 db, SeedJob &J);
 	bool seed_group(Part &pt, SeedPlan &S, bool swapped, hipStream_t s, Prim &pr, u32 q_begin);
 	void swap_plan(SeedPlan &S);
@@ -338,6 +326,7 @@ void lq_format_rows(FILE *out, int filter_flag, const lqcov_row *rows, u32 n_row
                     const std::function<const char *(u32)> &name_of);
 void lq_pack_host(u32 n, const u8 *seq, const u64 *seq_off, u64 *codes, u32 *amb, int n_threads);
 bool lq_packed_read_ambiguous(const u32 *aw, u64 len);
+void lq_make_q2p(double *t);                              // meanQ's table of 127 error probabilities (lqutils.c:26-49)
 
 struct StageTimer {
 	lqcov_handle *h; hipStream_t s; const char *name; u64 bytes;

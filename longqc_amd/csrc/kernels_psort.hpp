@@ -59,6 +59,7 @@ __device__ __forceinline__ u64 lq_ps_load_x(const PSeg &sg, const PsData &P, u32
 #endif
 #define LQ_PS_CHILD     4096      // aimed child size of a partition pass: half of what the finish takes
 #define LQ_PS_THREADS   256
+#define LQ_PS_GRID      512       // blocks of the tile kernels at most (the finishing kernels: a quarter / twice that; twice as many blocks for them: no change, measured with the 64-register kernels)
 
 // counters of one batch's sort (device): indices into L.sort_cnt.  Two sets of psort lists: set 0 takes whole queries
 // (k_sort_init) and is sorted on its own stream while klib's passes run; set 1 collects the buckets that leave them.

@@ -376,6 +376,7 @@ __global__ void k_sketch_unowned(const u8 *owned, u64 n_chunks, u32 *list, u32 *
 #define LQ_DPT_N (LQ_DPT_CH * LQ_CHUNK + LQ_DP_HALO)          // 1600 positions
 #define LQ_DPT_THREADS (LQ_DPT_N / LQ_DPT_PER)                // 320
 #define LQ_DPT_WAVES (LQ_DPT_THREADS / 64)
+#define LQ_DPT_GRID (1u << 22)                                // blocks of k_sketch_dp_mask / k_sketch_dp_fast at most (a block strides over the tiles)
 __device__ __forceinline__ u64 lq_rev2(u64 x)
 {	// the 2-bit groups of x in reverse order
 	x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
@@ -704,6 +705,7 @@ __global__ void k_mask_count(const u32 *mask, u64 n_chunks, u32 *cnt)
 // thread per list entry rebuilds the k-mer from the packed codes, hashes it and writes x and y at offset + rank: all lanes
 // busy with a hash, the 16-byte outputs contiguous.
 #define LQ_EM_THREADS 256
+#define LQ_EM_GRID (1u << 22)                                 // blocks of k_sketch_emit_mask at most (a block strides over the groups of LQ_EM_CH chunks)
 #define LQ_EM_WORDS (LQ_EM_CH * LQ_CHUNK_WORDS)                // mask words of a group: at most one per thread of the first half of the block
 __global__ void __launch_bounds__(LQ_EM_THREADS)
 k_sketch_emit_mask(const u64 *codes, const u32 *amb, const u64 *coff, const u32 *group_rid, u32 n_reads, u64 n_chunks, SkParams P, int rid_in_y,

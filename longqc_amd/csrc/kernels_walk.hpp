@@ -19,6 +19,9 @@
 #include "kernels_sort.hpp"
 #include "kernels_ckpt.hpp"
 
+#define LQ_WALK_GRID (1u << 18)          // cap on resident walker waves
+#define LQ_WALK_CU_MASK 0x11111111u      // the CUs the walkers' streams may use (repeated over the 256 CUs): every fourth one -- see map_part
+
 #ifndef LQ_EMU
 #define LQ_RL(v, lane) ((u32)__builtin_amdgcn_readlane((int)(v), (int)(lane)))
 // (clang has no builtin for it; the LLVM intrinsic is reached by its name, and the compiler routes the lane select through M0)

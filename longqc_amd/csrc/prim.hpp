@@ -9,16 +9,23 @@
 #include <utility>
 #include <string>
 
+// Every HIP error is a std::runtime_error (LQCOV_E_DEVICE at the C ABI); hipErrorOutOfMemory alone is an LqOutOfMemory, the one
+// error the engine may answer by doing without a buffer (the seed filter's fallbacks, a lane's arena): after any other one the
+// context may be lost, and carrying on would hide it.
+struct LqOutOfMemory : std::runtime_error { using std::runtime_error::runtime_error; };
+[[noreturn]] inline void lq_hip_throw(hipError_t e, const std::string &what)
+{
+	if (e == hipErrorOutOfMemory) throw LqOutOfMemory(what);
+	throw std::runtime_error(what);
+}
 #ifndef LQ_EMU
 #include <cstring>
-#define LQ_HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-	throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#define LQ_HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) lq_hip_throw(e_, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 #else
 #include <vector>
 #include <algorithm>
 #include <numeric>
-#define LQ_HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-	throw std::runtime_error(std::string(#expr) + ": emu error"); } while (0)
+#define LQ_HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) lq_hip_throw(e_, std::string(#expr) + ": emu error"); } while (0)
 #endif
 
 // grow-only device buffer.  Inside the mapping lanes growth must not stall the device: hipFree / hipMalloc wait for every
@@ -52,6 +59,7 @@ inline void lq_pool_keep_memory(int) {}
 #include <atomic>
 #include <chrono>
 #include <algorithm>
+inline double lq_now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 inline std::atomic<uint64_t> lq_alloc_ns{0}, lq_alloc_bytes{0};
 struct LqAllocTimer { std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); size_t bytes; explicit LqAllocTimer(size_t b) : bytes(b) {}
 	~LqAllocTimer() { lq_alloc_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); lq_alloc_bytes += bytes; } };

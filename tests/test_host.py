@@ -274,3 +274,54 @@ def test_replay_side_sort_equals_klibs_order_ties_included(tmp_path):
             ora.lqo_sort_128x(b.ctypes.data_as(C.c_void_p), n)
             assert np.array_equal(a, b), (n, shape)
             assert np.all(a[0::2][1:] >= a[0::2][:-1])
+
+
+_HIP_CHECK_SHIM = r"""
+#include "prim.hpp"
+#include "lq_cabi.hpp"
+// what LQ_HIP_CHECK throws for an error code, as a catch site of the engine's fallbacks sees it -- 0: nothing, 1: LqOutOfMemory,
+// 2: a std::runtime_error that is no LqOutOfMemory, 3: anything else
+template <class F> static int thrown_by(F &&f)
+{
+	try {
+		try { f(); return 0; }
+		catch (const LqOutOfMemory &) { return 1; }
+	}
+	catch (const std::runtime_error &) { return 2; }
+	catch (...) { return 3; }
+}
+extern "C" int shim_hip_check(int code) { return thrown_by([&] { LQ_HIP_CHECK((hipError_t)code); }); }
+extern "C" int shim_ensure(size_t bytes) { return thrown_by([&] { DBuf b; b.ensure(bytes); }); }
+extern "C" int shim_guarded(int code, char *err, size_t n) { return lq_cabi::guarded(err, n, [&] { LQ_HIP_CHECK((hipError_t)code); }); }
+extern "C" int shim_code(int which) { return which == 0 ? (int)hipErrorOutOfMemory : (int)hipErrorInvalidValue; }
+"""
+
+
+def test_only_out_of_memory_takes_the_fallbacks(tmp_path):
+    """The engine's fallbacks (the seed filter without its survivors or its bucket buffer, a lane without an arena) catch
+    LqOutOfMemory and nothing wider.  LQ_HIP_CHECK (prim.hpp) throws that type for hipErrorOutOfMemory alone; every other code is a
+    plain std::runtime_error, which those catch sites do not match and the C ABI reports as LQCOV_E_DEVICE -- as it does the
+    out-of-memory error that nobody caught.  Held here on the macro itself and on a DBuf whose allocation the emulator's
+    hipMalloc refuses (the emulator cannot make one chosen allocation of a run fail)."""
+    import ctypes as C
+    import subprocess
+    src, so = str(tmp_path / "hip_check_shim.cpp"), str(tmp_path / "hip_check_shim.so")
+    with open(src, "w") as f:
+        f.write(_HIP_CHECK_SHIM)
+    csrc = os.path.join(ROOT, "longqc_amd", "csrc")
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-DLQ_EMU", "-include", os.path.join(ROOT, "tests", "emu", "hipemu.hpp"),
+                        "-I", csrc, "-Wno-unknown-pragmas", src, "-o", so], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-3000:]
+    shim = C.CDLL(so)
+    shim.shim_ensure.argtypes = [C.c_size_t]
+    shim.shim_guarded.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+    oom, invalid = shim.shim_code(0), shim.shim_code(1)
+    assert shim.shim_hip_check(0) == 0                       # hipSuccess
+    assert shim.shim_hip_check(oom) == 1                     # the new type
+    assert shim.shim_hip_check(invalid) == 2                 # a runtime_error the fallbacks' catch does not match
+    assert shim.shim_ensure(1 << 20) == 0
+    assert shim.shim_ensure(1 << 60) == 1                    # a refused allocation is out of memory
+    E_DEVICE = -3                                            # LQCOV_E_DEVICE (include/lqcov.h)
+    for code in (oom, invalid):                              # uncaught, both stay LQCOV_E_DEVICE with the failing call in the message
+        err = C.create_string_buffer(256)
+        assert shim.shim_guarded(code, err, 256) == E_DEVICE and b"(hipError_t)code" in err.value
