@@ -175,7 +175,9 @@ int lqcov_packed_ambiguous_reads(uint32_t n, const uint32_t *amb, const uint32_t
  * i * stride_chunks of codes_dev (4 x u64 per chunk) / amb_dev (4 x u32 per chunk); the shares are copied back to back in
  * share order = read order.  For a host that received the packed reads of a part from its peers (the query-sharded multi-GPU
  * split all-gathers 0.375 B per base over RCCL instead of 16 B per minimizer): lens / names describe every read of the part.
- * amb_dev == NULL: as amb == NULL above.  No counterpart in the reference (its parts come from one file, bseq.c:68-102). */
+ * amb_dev == NULL: as amb == NULL above.  A part may be filled by several calls, each appending its reads behind those already there
+ * and each with an amb_dev or without (lqstore_run: the pieces of the stored chunks a part is made of).  No counterpart in the
+ * reference (its parts come from one file, bseq.c:68-102). */
 int lqcov_part_add_packed_shares_dev(lqcov_handle *h, int part, const uint64_t *codes_dev, const uint32_t *amb_dev, uint64_t stride_chunks,
                                      uint32_t n_shares, const uint64_t *share_chunks, uint32_t n, const uint32_t *lens,
                                      const char *names, const uint64_t *name_off);
@@ -352,6 +354,42 @@ int lqgc_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *seq_o
                uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,
                uint64_t seed, uint64_t first_read, uint32_t *gc, uint32_t *pos_out, uint16_t *win_gc, uint32_t *kept,
                char *errbuf, size_t errbuf_len);
+
+/* ---- one upload per chunk: the chunk loop of sampleqc (longQC.py:299-360) and the coverage call on the same device bytes ---------- */
+/* A resident chunk: lqchunk_load uploads the reads (ASCII, seq_off with n+1 ascending entries, qual NULL or parallel to seq as in
+ * lqsdust_reads) once into device buffers the handle owns and reuses, growing, from chunk to chunk.  lqchunk_sdust, lqchunk_adapt and
+ * lqchunk_gc are lqsdust_reads, lqadapt_reads and lqgc_reads on those buffers: the same arguments behind the reads, the same checks
+ * and codes, the same results (those three are the same code on a chunk that lives for one call).  lqchunk_pack writes, on the device,
+ * the packed form documented at lqcov_pack_reads, byte for byte what that call writes on the host, and per read the flag of
+ * lqcov_packed_ambiguous_reads; lqchunk_get_packed copies the three arrays to the host (lqcov_packed_chunks(n, seq_off) chunks of 32
+ * / 16 bytes, n flags).  A handle owns one stream and its calls are ordered on it; handles are not thread-safe.  LQCOV_E_STATE: no
+ * chunk loaded, or not packed.  The message of a failed call is lqchunk_last_error's (c == NULL: why lqchunk_create failed). */
+typedef struct lqchunk lqchunk;
+lqchunk *lqchunk_create(int device);                 /* NULL without a HIP device */
+void     lqchunk_destroy(lqchunk *c);
+const char *lqchunk_last_error(const lqchunk *c);
+int lqchunk_load(lqchunk *c, uint32_t n, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *qual);
+int lqchunk_sdust(lqchunk *c, int W, int T, uint32_t *masked, double *qual_psum, uint32_t *n_above_q7);
+int lqchunk_adapt(lqchunk *c, const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
+                  uint32_t length, int32_t *out5, int32_t *out3);
+int lqchunk_gc(lqchunk *c, uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,
+               uint64_t seed, uint64_t first_read, uint32_t *gc, uint32_t *pos_out, uint16_t *win_gc, uint32_t *kept);
+int lqchunk_pack(lqchunk *c);
+int lqchunk_get_packed(lqchunk *c, uint64_t *codes, uint32_t *amb, uint8_t *amb_flags);
+
+/* The packed chunks of a whole input, kept in device memory (0.25 B per base, 0.375 for a chunk with an ambiguous base; one
+ * allocation per array and appended chunk), with lengths, names and flags on the host.  lqstore_append copies the packed form of a
+ * chunk (after lqchunk_pack; names as in lqcov_set_queries, NULL: empty names) -- the chunk handle is free for the next chunk
+ * afterwards.  If the device memory cannot be had the call fails with LQCOV_E_DEVICE (message on the chunk handle) and the store is
+ * unchanged.  lqstore_run cuts the stored reads into index parts by the reference's rule (index.c:244,311-316, from the lengths
+ * alone) and, part by part, fills a part of `h` from the stored chunks' pieces, builds, maps and releases it; the queries are those
+ * set on `h`, lqcov_finish and the tables stay the caller's.  A failing engine call ends it with that call's code (lqcov_last_error). */
+typedef struct lqstore lqstore;
+lqstore *lqstore_create(int device);                 /* NULL without a HIP device */
+void     lqstore_destroy(lqstore *s);
+int      lqstore_append(lqstore *s, lqchunk *c, const char *names, const uint64_t *name_off);
+uint64_t lqstore_bytes(const lqstore *s);            /* device bytes held */
+int      lqstore_run(lqstore *s, lqcov_handle *h);
 
 #ifdef __cplusplus
 }

@@ -103,22 +103,32 @@ def _cut(reads, rows, th, r, three, len_list, lens):
     return (iden_max, int(hit.size), cut_pos)
 
 
-def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=150, device=0, lib=None):
+def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=150, device=0, lib=None, chunk=None):
     """== lq_adapt.cut_adapter (lq_adapt.py:80-101): reads are LongQC's mutable [name, seq, qual, ...] records, trimmed in
-    place; returns (iden_max, match_num, cut_pos) for one adapter, ((...5'), (...3')) for two, None (logged) for none."""
+    place; returns (iden_max, match_num, cut_pos) for one adapter, ((...5'), (...3')) for two, None (logged) for none.
+    chunk: a chunkpass.ReadChunk made of these (untrimmed) reads: the search runs on its device copy, which stays as it is;
+    nothing is gathered or uploaded."""
     if not adp_t and not adp_b:
         logger.error("No adapter sequence is given.")
         return None
-    seqs = [rd[1] for rd in reads]
-    o5, o3 = _hits(seqs, adp_t, adp_b, length, device, lib)
-    lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
+    if chunk is not None:
+        if not 1 <= length <= 4096:
+            raise ValueError("length must lie in [1, 4096]")
+        if len(reads) != chunk.n:
+            raise ValueError("the chunk does not hold these reads")
+        o5, o3 = chunk.adapt(_bytes(adp_t) if adp_t else None, _bytes(adp_b) if adp_b else None, length)
+        lens = chunk.lens.copy()
+    else:
+        seqs = [rd[1] for rd in reads]
+        o5, o3 = _hits(seqs, adp_t, adp_b, length, device, lib)
+        lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
     t5 = t3 = None
     if adp_t:
         t5 = _cut(reads, o5, th, length, False, len_list, lens)
         logger.info("Adapter Sequence: %s, max identity:%f and the number of trimmed reads: %d" % (adp_t, t5[0], t5[1]))
         if adp_b:                                                  # the 3' skip test sees the 5'-trimmed length
             lens = lens.copy()
-            hit5 = np.zeros(len(seqs), dtype=bool)
+            hit5 = np.zeros(len(reads), dtype=bool)
             ok5 = lens >= 2 * length
             hit5[ok5] = _identity(o5[ok5]) > th
             lens[hit5] -= o5[hit5, 2].astype(np.int64) + 1

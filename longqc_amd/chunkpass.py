@@ -1,0 +1,249 @@
+"""One upload per chunk: the chunk loop of `longQC.py sampleqc` (longQC.py:299-360) and the coverage call (:438-445) on the same
+device bytes, over the lqchunk_* / lqstore_* calls of include/lqcov.h.
+
+ReadChunk gathers a chunk's [name, seq, qual] records into flat arrays once and uploads them once; sdust.sdust_rows,
+adapter.cut_adapter and LqGCMI355X.calc_read_and_chunk_gc_frac take it as `chunk=` and then run on the device copy.
+SampleQCPass is the loop's body and the coverage call: add_chunk(reads) per chunk -- low-complexity rows, adapter search,
+subsample, GC fractions, then the chunk is 2-bit packed on the device and kept there -- and coverage(), which maps the subsample
+against the kept chunks without touching the input again.  No CPU fallback: without liblqcov.so or a HIP device the calls raise."""
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import adapter, api, gcfrac, sampleqc, sdust
+
+
+def _lib(lib=None):
+    lib = lib or api.load_library()
+    if not getattr(lib, "_lqchunk_bound", False):
+        H, P = C.c_void_p, C.c_void_p
+        sig = {
+            "lqchunk_create": (H, [C.c_int]),
+            "lqchunk_destroy": (None, [H]),
+            "lqchunk_last_error": (C.c_char_p, [H]),
+            "lqchunk_load": (C.c_int, [H, C.c_uint32, P, P, P]),
+            "lqchunk_sdust": (C.c_int, [H, C.c_int, C.c_int, P, P, P]),
+            "lqchunk_adapt": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32, P, P]),
+            "lqchunk_gc": (C.c_int, [H, C.c_uint32, P, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
+            "lqchunk_pack": (C.c_int, [H]),
+            "lqchunk_get_packed": (C.c_int, [H, P, P, P]),
+            "lqstore_create": (H, [C.c_int]),
+            "lqstore_destroy": (None, [H]),
+            "lqstore_append": (C.c_int, [H, H, C.c_char_p, P]),
+            "lqstore_bytes": (C.c_uint64, [H]),
+            "lqstore_run": (C.c_int, [H, H]),
+        }
+        for name, (res, args) in sig.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        lib._lqchunk_bound = True
+    return lib
+
+
+def _join(items, n):
+    """one buffer of all items (all str or all bytes) and their lengths"""
+    lens = np.fromiter((len(s) for s in items), dtype=np.int64, count=n)
+    flat = "".join(items).encode("latin-1") if n and isinstance(items[0], str) else b"".join(items)
+    if len(flat) != int(lens.sum()):
+        raise ValueError("reads must be all str or all bytes")
+    return flat, lens
+
+
+class ReadChunk:
+    """A chunk of LongQC's [name, seq, qual, ...] records on the device.  n, names, lens (int64), off (uint64, n + 1) describe it on
+    the host; the records themselves are not kept.  load(reads) puts another chunk into the same handle, whose device buffers
+    are used again and grow."""
+
+    def __init__(self, reads, device: int = 0, lib=None):
+        self.lib = _lib(lib)
+        self.device = device
+        self.h = self.lib.lqchunk_create(device)
+        if not self.h:
+            raise api.LqcovError(-3, self.lib.lqchunk_last_error(None).decode() or "lqchunk_create failed (no HIP device?)")
+        self.load(reads)
+
+    def load(self, reads):
+        n = self.n = len(reads)
+        self.packed = False
+        self.names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
+        self.flat, self.lens = _join([r[1] for r in reads], n)
+        self.off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(self.lens, out=self.off[1:])
+        self.qflat = None
+        quals = [r[2] if len(r) > 2 and r[2] else None for r in reads]
+        if any(q is not None for q in quals):                      # reads without qualities: zero bytes, as lqsdust_reads takes them
+            zero = "\0" if isinstance(next(q for q in quals if q is not None), str) else b"\0"
+            self.qflat, qlens = _join([q if q is not None else zero * int(l) for q, l in zip(quals, self.lens)], n)
+            if (qlens != self.lens).any():
+                raise ValueError("a quality string differs in length from its read")
+        self._ck(self.lib.lqchunk_load(self.h, n, self.flat if len(self.flat) else None, self.off.ctypes.data, self.qflat))
+
+    def _ck(self, rc: int):
+        if rc != 0:
+            raise api.LqcovError(rc, self.lib.lqchunk_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lqchunk_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def qual_array(self) -> Optional[np.ndarray]:
+        return None if self.qflat is None else np.frombuffer(self.qflat, dtype=np.uint8)
+
+    # -- the steps, as arrays --
+    def sdust(self, w: int = 64, t: int = 20):
+        """-> (masked bases, sums of 10^(-q/10), qualities above Q7) per read: lqchunk_sdust"""
+        n = self.n
+        masked, psum, qv = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint32)
+        self._ck(self.lib.lqchunk_sdust(self.h, w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data))
+        return masked, psum, qv
+
+    def adapt(self, adp5: Optional[bytes], adp3: Optional[bytes], length: int = 150):
+        """-> (n x 4 int32 of d, s, e, L for the 5' windows, the same for the 3' windows), None for an adapter not given: lqchunk_adapt"""
+        n = self.n
+        o5 = np.empty((max(n, 1), 4), dtype=np.int32) if adp5 else None
+        o3 = np.empty((max(n, 1), 4), dtype=np.int32) if adp3 else None
+        self._ck(self.lib.lqchunk_adapt(self.h, adp5, len(adp5) if adp5 else 0, adp3, len(adp3) if adp3 else 0, length,
+                                        o5.ctypes.data if adp5 else None, o3.ctypes.data if adp3 else None))
+        return (o5[:n] if adp5 else None), (o3[:n] if adp3 else None)
+
+    def gc(self, chunk_size, k, draw_off, pos_in, seed, first_read, gc, pos_out, win_gc, kept):
+        """lqchunk_gc on caller-owned arrays (addresses or None), as gcfrac._call hands them over"""
+        self._ck(self.lib.lqchunk_gc(self.h, chunk_size, k, draw_off, pos_in, seed, first_read, gc, pos_out, win_gc, kept))
+
+    def pack(self):
+        """2-bit pack the device copy on the device (k_chunk_pack): the layout of lqcov_pack_reads"""
+        self._ck(self.lib.lqchunk_pack(self.h))
+        self.packed = True
+
+    def get_packed(self):
+        """-> (codes uint64[4 * chunks], amb uint32[4 * chunks], flags uint8[n]) on the host"""
+        if not self.packed:
+            self.pack()
+        nc = int(((self.lens + 127) // 128).sum())
+        codes, amb, flags = np.zeros(max(nc, 1) * 4, np.uint64), np.zeros(max(nc, 1) * 4, np.uint32), np.zeros(max(self.n, 1), np.uint8)
+        self._ck(self.lib.lqchunk_get_packed(self.h, codes.ctypes.data, amb.ctypes.data, flags.ctypes.data))
+        return codes[:nc * 4], amb[:nc * 4], flags[:self.n]
+
+
+class PackedStore:
+    """The packed chunks of the whole input in device memory (lqstore_*)."""
+
+    def __init__(self, device: int = 0, lib=None):
+        self.lib = _lib(lib)
+        self.h = self.lib.lqstore_create(device)
+        if not self.h:
+            raise api.LqcovError(-3, "lqstore_create failed (no HIP device?)")
+
+    def append(self, chunk: ReadChunk):
+        if not chunk.packed:
+            chunk.pack()
+        nb, noff = api.encode_names(chunk.names)
+        chunk._ck(self.lib.lqstore_append(self.h, chunk.h, nb, noff.ctypes.data))
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.lib.lqstore_bytes(self.h))
+
+    def run(self, eng: "api.Engine"):
+        eng._ck(self.lib.lqstore_run(self.h, eng.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lqstore_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SampleQCPass:
+    """The body of LongQC's chunk loop and its coverage call with every chunk uploaded once.
+
+    add_chunk(reads) does steps 2-5 of longQC.py:305-328 on one ReadChunk: the sdust rows go to `mask` (an LqMaskMI355X: close_pool()
+    writes longqc_sdust<suffix>.txt), the adapter search trims a copy of the records (kept in `trimmed`, for --trim; `adapters` is the
+    AdapterStats) as the reference's pool does, the subsample (`s_reads`, seed-7 reservoir of `nsample`) and the GC fractions (`gc`, an
+    LqGCMI355X) see the untrimmed reads; then the chunk is packed on the device and appended to `store`.
+    coverage() maps the subsample against the stored chunks."""
+
+    def __init__(self, work_dir: str, preset: str, adp5=None, adp3=None, nsample=5000, gc_draw: str = "device", device: int = 0,
+                 fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None):
+        if preset not in sampleqc.PRESET_MED_SCORE:
+            raise ValueError("unknown preset %r" % preset)
+        self.preset, self.fast, self.inds, self.device, self.lib = preset, fast, inds, device, lib
+        self.adp5, self.adp3, self.nsample = adp5, adp3, nsample
+        self.mask = sdust.LqMaskMI355X(work_dir, suffix, device=device, lib=lib)
+        self.adapters = adapter.AdapterStats(adp5, adp3)
+        self.gc = gcfrac.LqGCMI355X(chunk_size=150, draw=gc_draw, seed=gc_seed, device=device, lib=lib)
+        self.store = PackedStore(device, lib)
+        self.s_reads, self.cum_n_seq, self.chunk_n, self.n_bases = [], 0, 0, 0
+        self.trimmed = None
+
+    def add_chunk(self, reads):
+        chunk = ReadChunk(reads, device=self.device, lib=self.lib)
+        try:
+            self.mask.submit_sdust(reads, self.chunk_n, chunk=chunk)                                    # longQC.py:307
+            result = None
+            if self.adp5 or self.adp3:                                                                  # :310-320, on a copy as the pool's pickling makes one
+                self.trimmed = [list(r) for r in reads]
+                result = adapter.cut_adapter(self.trimmed, adp_t=self.adp5, adp_b=self.adp3, chunk=chunk)
+                self.adapters.add(result)                                                               # :348-357
+            self.s_reads = sampleqc.subsample_from_chunk(reads, self.cum_n_seq, self.s_reads, self.nsample)    # :323
+            self.gc.calc_read_and_chunk_gc_frac(reads, chunk=chunk)                                     # :328
+            self.store.append(chunk)
+        finally:
+            chunk.close()
+        self.chunk_n += 1
+        self.cum_n_seq += len(reads)
+        self.n_bases += int(chunk.lens.sum())
+        return result
+
+    def coverage(self, s_reads=None, short_threshold: Optional[int] = None, out: Optional[str] = None, exclude_seqs=None, chunks=None):
+        """The coverage table of the subsample (s_reads: another query set) against every chunk added, as
+        sampleqc.coverage_in_memory(chunks, s_reads, preset, ...) gives it: the text, or with short_threshold (LongQC's --short) the
+        (main, short) pair mapped in one pass; `out` gets the text (the pair: concatenated).  exclude_seqs (with `chunks`, the re-iterable
+        input): sampleqc.replace_masked first, longQC.py:369-406 -- the one step that reads the input again, as the reference does."""
+        reads = self.s_reads if s_reads is None else s_reads
+        if exclude_seqs:
+            reads = sampleqc.replace_masked(reads, exclude_seqs, chunks if chunks is not None else [])
+        inds = str(self.inds)
+        if short_threshold is None:
+            text = self._pass([(reads, sampleqc.coverage_argv(self.preset, "-", "-", fast=self.fast, inds=inds))])[0]
+        else:
+            main_reads, short_reads = sampleqc.short_split(reads, short_threshold)
+            argv_main = sampleqc.coverage_argv(self.preset, "-", "-", fast=self.fast, inds=inds)
+            argv_short = sampleqc.coverage_argv(self.preset, "-", "-", fast=self.fast, inds=inds, short=True)
+            strip_p = lambda a: [x for i, x in enumerate(a) if x != "-p" and (i == 0 or a[i - 1] != "-p")]
+            if strip_p(argv_main) == strip_p(argv_short):
+                text = tuple(self._pass([(main_reads, argv_main), (short_reads, argv_short)]))
+            else:                                                  # other index options: a pass of its own over the same stored chunks
+                text = (self._pass([(main_reads, argv_main)])[0], self._pass([(short_reads, argv_short)])[0])
+        if out:
+            with open(out, "w") as f:
+                f.write(text if isinstance(text, str) else "".join(text))
+        return text
+
+    def _pass(self, sets):
+        """one run over the stored chunks for every (reads, argv) of `sets` -> one table per set"""
+        p, _, _ = api.parse_args(sets[0][1])
+        eng = api.Engine(p, device=self.device, lib=self.lib)
+        try:
+            sampleqc.set_query_reads(eng, sets)
+            self.store.run(eng)
+            eng.finish()
+            return [eng.table_text()] if len(sets) == 1 else [eng.table_text(set=k) for k in range(len(sets))]
+        finally:
+            eng.close()
+
+    def close(self):
+        self.store.close()

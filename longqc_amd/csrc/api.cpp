@@ -356,7 +356,6 @@ int lqcov_part_add_packed_shares_dev(lqcov_handle *h, int part, const uint64_t *
 		if (n && (!codes_dev || !lens || !share_chunks)) throw std::invalid_argument("null read buffers");   // (amb_dev == NULL: no read holds an ambiguous base)
 		Part &pt = h->part(part);
 		if (pt.built) throw std::logic_error("part already built");
-		if (pt.rs.n) throw std::logic_error("packed shares go into an empty part");
 		std::vector<u64> sc(share_chunks, share_chunks + n_shares);
 		for (u64 v : sc) if (v > stride_chunks) throw std::invalid_argument("a share is longer than the stride");
 		h->add_reads_packed(pt.rs, n, nullptr, nullptr, lens, names, name_off, codes_dev, amb_dev, stride_chunks, &sc);

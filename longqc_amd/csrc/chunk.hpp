@@ -1,0 +1,41 @@
+// longqc_amd/csrc/chunk.hpp -- a chunk of reads resident on the device (lqchunk of include/lqcov.h): the bases, the offsets and, if
+// given, the qualities go up once; the low-complexity scan (dust.cpp), the adapter search (adapt.cpp), the GC counts (gc.cpp) and
+// the packing for the coverage engine (chunk.cpp) run on those buffers.  The buffer-level entry points lqsdust_reads,
+// lqadapt_reads and lqgc_reads are the same steps on a chunk that lives for one call.
+#pragma once
+#include "lq_cabi.hpp"
+#include <string>
+#include <vector>
+
+#define LQ_CHUNK_SEQ_TILE 4096u      // the sequence buffer is allocated in whole tiles of k_gc_reads (LQ_GC_TILE)
+
+struct lqchunk {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	std::string err;
+	// the reads: read i = bases off[i] .. off[i + 1] of the buffer (offsets relative to the first base)
+	u32 n = 0, first_desc = 0;                                // first_desc: the first i with seq_off[i + 1] < seq_off[i], n if none
+	u64 total = 0;
+	std::vector<u64> off;
+	bool resident = false;                                    // the reads lq_chunk_set described are on the device
+	const u8 *h_seq = nullptr, *h_qual = nullptr;             // the caller's bases / qualities (at the first base), until lq_chunk_ready has uploaded them
+	bool has_qual = false;
+	DBuf seq, qual, d_off;
+	DBuf pi, masked, psum, qv, q2p; bool tab_ready = false;   // sdust: scratch, results, meanQ's table
+	DBuf woff, adp5, adp3, out;                               // adapter search: window offsets, adapters, result rows
+	DBuf draw_off, gc, pos, win, kept;                        // GC counts
+	DBuf coff, tile_read, codes, amb, flags;                  // packed form
+	std::vector<u64> h_coff;                                  // packed chunks before read i
+	u64 n_chunks = 0; bool packed = false;
+	~lqchunk() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }
+};
+
+// describe the reads (nothing goes to the device and nothing is checked but the order of the offsets: each step keeps its own checks,
+// in its own order, and uploads when it first needs the device)
+void lq_chunk_set(lqchunk &c, u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual);
+// select the device, make the stream, upload what lq_chunk_set described (once)
+void lq_chunk_ready(lqchunk &c);
+void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
+void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
+void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,
+                 u32 *gc, u32 *pos_out, u16 *win_gc, u32 *kept);

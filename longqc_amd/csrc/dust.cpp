@@ -1,10 +1,10 @@
 // longqc_amd/csrc/dust.cpp -- host side of the low-complexity table: the reference's `sdust` binary
-// (sdust.c:181-222) behind the C ABI of include/lqcov.h (lqsdust_*).  Reads go to the device as ASCII, one thread
-// walks one read (kernels_dust.hpp); rows are formatted on the host with libc/libm like the reference.
+// (sdust.c:181-222) behind the C ABI of include/lqcov.h (lqsdust_*).  Reads go to the device as ASCII (a resident chunk, chunk.hpp), one
+// thread walks one read (kernels_dust.hpp); rows are formatted on the host with libc/libm like the reference.
 #include "engine.hpp"
 #include "kernels_dust.hpp"
 #include "fastx.hpp"
-#include "lq_cabi.hpp"
+#include "chunk.hpp"
 using lq_cabi::guarded;
 using lq_cabi::select_device;
 #include <cstdio>
@@ -19,50 +19,32 @@ using lq_cabi::select_device;
 
 static inline dim3 nblk_d(u64 n, u32 b) { return dim3((unsigned)((n + b - 1) / b)); }
 
-namespace {
-struct DustDev {
-	hipStream_t stream = nullptr;
-	DBuf seq, qual, off, pi, masked, psum, qv, q2p;
-	bool tab_ready = false;
-	~DustDev() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }
-};
-
-void dust_batch(DustDev &D, u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual, int W, int T,
-                u32 *masked, double *psum, u32 *qv)
+// the scan on a chunk's resident buffers (chunk.hpp): one thread walks one read
+void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv)
 {
 	if (W < 3 || W > 66) throw std::domain_error("sdust window outside [3, 66] (the window ring holds 64 words; the reference's default is 64)");
+	const u32 n = c.n;
 	if (n == 0) return;
-	for (u32 i = 0; i < n; ++i) if (seq_off[i + 1] - seq_off[i] > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases");
-	if (!D.stream) LQ_HIP_CHECK(hipStreamCreate(&D.stream));
-	const u64 nb = seq_off[n] - seq_off[0];
-	std::vector<u64> off(n + 1);
-	for (u32 i = 0; i <= n; ++i) off[i] = seq_off[i] - seq_off[0];
-	D.seq.ensure(nb + 16); D.off.ensure((n + 1) * 8); const u32 n_thr = (u32)std::min<u64>(((u64)n + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_MAX_THREADS);
-	D.pi.ensure((u64)n_thr * LQ_DUST_PCAP * sizeof(DustPI));
-	D.masked.ensure(n * 4 + 4); D.psum.ensure(n * 8 + 8); D.qv.ensure(n * 4 + 4);
-	if (!D.tab_ready) {
+	for (u32 i = 0; i < n; ++i) if (c.off[i + 1] - c.off[i] > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases");
+	lq_chunk_ready(c);
+	const u32 n_thr = (u32)std::min<u64>(((u64)n + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_MAX_THREADS);
+	c.pi.ensure((u64)n_thr * LQ_DUST_PCAP * sizeof(DustPI));
+	c.masked.ensure(n * 4 + 4); c.psum.ensure(n * 8 + 8); c.qv.ensure(n * 4 + 4);
+	if (!c.tab_ready) {
 		double tab[127]; lq_make_q2p(tab);
-		D.q2p.ensure(127 * 8);
-		LQ_HIP_CHECK(hipMemcpyAsync(D.q2p.p, tab, sizeof(tab), hipMemcpyHostToDevice, D.stream));
-		LQ_HIP_CHECK(hipStreamSynchronize(D.stream));
-		D.tab_ready = true;
+		c.q2p.ensure(127 * 8);
+		LQ_HIP_CHECK(hipMemcpyAsync(c.q2p.p, tab, sizeof(tab), hipMemcpyHostToDevice, c.stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+		c.tab_ready = true;
 	}
-	LQ_HIP_CHECK(hipMemcpyAsync(D.seq.p, seq + seq_off[0], nb, hipMemcpyHostToDevice, D.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(D.off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, D.stream));
-	if (qual) {
-		D.qual.ensure(nb + 16);
-		LQ_HIP_CHECK(hipMemcpyAsync(D.qual.p, qual + seq_off[0], nb, hipMemcpyHostToDevice, D.stream));
-	}
-	LQ_LAUNCH(k_sdust, nblk_d(n_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, D.stream, D.seq.as<u8>(), qual ? D.qual.as<u8>() : (const u8*)nullptr,
-	          D.off.as<u64>(), n, (i32)W, (i32)T, D.q2p.as<double>(), D.pi.as<DustPI>(), D.masked.as<u32>(), D.psum.as<double>(), D.qv.as<u32>());
+	LQ_LAUNCH(k_sdust, nblk_d(n_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, c.stream, c.seq.as<u8>(), c.has_qual ? c.qual.as<u8>() : (const u8*)nullptr,
+	          c.d_off.as<u64>(), n, (i32)W, (i32)T, c.q2p.as<double>(), c.pi.as<DustPI>(), c.masked.as<u32>(), c.psum.as<double>(), c.qv.as<u32>());
 	LQ_HIP_CHECK(hipGetLastError());
-	LQ_HIP_CHECK(hipMemcpyAsync(masked, D.masked.p, n * 4, hipMemcpyDeviceToHost, D.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(psum, D.psum.p, n * 8, hipMemcpyDeviceToHost, D.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(qv, D.qv.p, n * 4, hipMemcpyDeviceToHost, D.stream));
-	LQ_HIP_CHECK(hipStreamSynchronize(D.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
 }
-
-} // namespace
 
 extern "C" {
 
@@ -72,8 +54,10 @@ int lqsdust_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *se
 	return guarded(errbuf, errbuf_len, [&] {
 		if (!seq_off || (n && (!seq || !masked || !qual_psum || !n_above_q7))) throw std::invalid_argument("null buffers");
 		select_device(device);
-		DustDev D;
-		dust_batch(D, n, seq, seq_off, qual, W, T, masked, qual_psum, n_above_q7);
+		lqchunk c;
+		c.device = device;
+		lq_chunk_set(c, n, seq, seq_off, qual);
+		lq_chunk_sdust(c, W, T, masked, qual_psum, n_above_q7);
 	});
 }
 
@@ -105,7 +89,8 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
 		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
 		struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); else if (f) fflush(f); } } oc{o, out_path != nullptr};
-		DustDev D;
+		lqchunk D;                                              // one chunk object for every mini-batch: its buffers grow and stay
+		D.device = device;
 		FastxReader fr(in);
 		std::vector<u32> masked, qv;
 		std::vector<double> psum;
@@ -141,7 +126,8 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 			const u32 n = rb.size();
 			masked.resize(n); qv.resize(n); psum.resize(n);
 			double t1 = lq_now_s(); t_wait += t1 - t0;
-			dust_batch(D, n, rb.seq.data(), rb.seq_off.data(), rb.any_qual ? rb.qual.data() : nullptr, W, T, masked.data(), psum.data(), qv.data());
+			lq_chunk_set(D, n, rb.seq.data(), rb.seq_off.data(), rb.any_qual ? rb.qual.data() : nullptr);
+			lq_chunk_sdust(D, W, T, masked.data(), psum.data(), qv.data());
 			t0 = lq_now_s(); t_dev += t0 - t1;
 			for (u32 i = 0; i < n; ++i) {
 				const int len = (int)(rb.seq_off[i + 1] - rb.seq_off[i]);

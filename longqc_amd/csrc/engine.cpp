@@ -2569,17 +2569,8 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 			flat.reserve(recs.n_recs);
 			for (MemPiece &pc : recs.pieces) for (MemRec &r : pc.recs)
 				flat.push_back(FlatRec{mf.data() + r.name_off, r.name_len, (r.own ? pc.side.data() : mf.data()) + r.seq_off, r.seq_len});
-			size_t r0 = 0;
-			while (r0 < flat.size()) {                                 // index.c:244,311-316 and bseq.c:86-98 on the record lengths
-				u64 sum_len = 0; size_t r1 = r0;
-				while (r1 < flat.size() && sum_len <= P.batch_size) {
-					i64 size = 0;
-					while (r1 < flat.size()) { size += flat[r1].seq_len; ++r1; if (size >= chunk) break; }
-					sum_len += (u64)size;
-				}
-				ranges.emplace_back(r0, r1);
-				r0 = r1;
-			}
+			for (const auto &rg : lq_part_ranges(flat.size(), [&](size_t i) { return (u64)flat[i].seq_len; }, P.batch_size, (u64)P.idx_mini_batch))
+				ranges.emplace_back(rg);                                // index.c:244,311-316 and bseq.c:86-98 on the record lengths
 			if (log) fprintf(log, "[lqcov] parsed %zu target sequence(s) from the mapped file in %.3f s (%zu pieces, %u parsed again in order), %zu part(s)\n",
 			                 flat.size(), lq_now_s() - t0, recs.pieces.size(), recs.reparsed, ranges.size());
 		} else ft.reset(new FastxReader(target));

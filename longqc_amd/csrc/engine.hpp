@@ -322,6 +322,27 @@ struct lqcov_handle {
 
 u64 lq_packed_chunks(u32 n, const u64 *seq_off);
 #include <functional>
+// The reference's rule for cutting n target reads into index parts, from their lengths alone (index.c:244,311-316 and bseq.c:86-98):
+// reads are taken in mini-batches, each ending with the read that brings it to min(idx_mini_batch, -I) bases, and a part takes
+// mini-batches while its running total is <= -I.  -> [first, last) read of every part.
+template <class LenAt>
+std::vector<std::pair<size_t, size_t>> lq_part_ranges(size_t n, LenAt len_at, u64 batch_size, u64 idx_mini_batch)
+{
+	const i64 chunk = (int)(idx_mini_batch < batch_size ? idx_mini_batch : batch_size);   // index.c:316
+	std::vector<std::pair<size_t, size_t>> ranges;
+	size_t r0 = 0;
+	while (r0 < n) {
+		u64 sum_len = 0; size_t r1 = r0;
+		while (r1 < n && sum_len <= batch_size) {
+			i64 size = 0;
+			while (r1 < n) { size += (i64)len_at(r1); ++r1; if (size >= chunk) break; }
+			sum_len += (u64)size;
+		}
+		ranges.emplace_back(r0, r1);
+		r0 = r1;
+	}
+	return ranges;
+}
 void lq_format_rows(FILE *out, int filter_flag, const lqcov_row *rows, u32 n_rows, const lqcov_region *regs, const lqcov_region *mregs,
                     const std::function<const char *(u32)> &name_of);
 void lq_pack_host(u32 n, const u8 *seq, const u64 *seq_off, u64 *codes, u32 *amb, int n_threads);

@@ -27,16 +27,17 @@
 #define LQ_ADAPT_MAXADP 32768        // adapter length (LongQC's presets: 18-64)
 #define LQ_ADAPT_MAX_BLOCKS 16384    // read ends are strided over the blocks of a launch
 
-// out[4k .. 4k+3] = d, s, e, L of window k (win + k * wlen) against adp[0..m); e = -1 (the whole adapter deleted) gives s = 0, L = m
+// out[4k .. 4k+3] = d, s, e, L of window k (the wlen bytes at seq + woff[k]: a read end inside the resident chunk) against adp[0..m);
+// e = -1 (the whole adapter deleted) gives s = 0, L = m
 template <bool BANDED>
 __global__ void __launch_bounds__(LQ_ADAPT_THREADS)
-k_adapt(const u8 *win, u32 n_ends, u32 wlen, const u8 *adp, u32 m, i32 *out)
+k_adapt(const u8 *seq, const u64 *woff, u32 n_ends, u32 wlen, const u8 *adp, u32 m, i32 *out)
 {
 	LQ_SHARED u32 s_row[BANDED ? LQ_ADAPT_MAXLEN + 1 : 1];      // row 64b of the current band: the last row of the band before
 	const i32 lane = (i32)threadIdx.x;
 	const u32 n_bands = BANDED ? (m + 63) / 64 : 1;
 	for (u32 k = blockIdx.x; k < n_ends; k += gridDim.x) {
-		const u8 *w = win + (u64)k * wlen;
+		const u8 *w = seq + woff[k];
 		// ---- sweep 1: HW, cells D << 16 | S ----
 		u32 best = m << 16;                                  // row m, column 0 (e = -1, s = 0)
 		i32 best_e = -1;

@@ -4,8 +4,8 @@
 // and the float32 roundings are the host's (longqc_amd/gcfrac.py), so they are the reference's own IEEE operations.
 //
 // The host hands the kernels one span [b0, b1) of the chunk's concatenated ASCII sequence at a time (b0 a multiple of
-// LQ_GC_TILE), uploaded with a margin of LQ_GC_MAXCS bytes behind b1 so that a window which starts inside the span can be read
-// to its end.  A read may lie in several spans: gc[] and kept[] live on the device for the whole call and are updated with
+// LQ_GC_TILE; buf points at byte b0 of the resident chunk, chunk.hpp, which holds whole tiles), so that a window which starts
+// inside the span can be read to its end behind b1.  A read may lie in several spans: gc[] and kept[] live on the device for the whole call and are updated with
 // integer atomics, which makes the result independent of the spans and of the order of the waves.
 //   k_gc_reads    a wave takes one aligned tile of LQ_GC_TILE bytes of the span (4 x 16-byte loads per lane) and then visits
 //                 the reads that overlap the tile, one (read, tile) item after the other: bytes outside the read are masked
@@ -101,7 +101,7 @@ __device__ __forceinline__ u32 lq_gc_count16_masked(const uint4 &v, u32 a, u32 l
 }
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------
-// buf holds bytes [b0, b1 + margin) of the sequence, allocated up to a multiple of LQ_GC_TILE; off[0..n] are the reads' offsets
+// buf holds the sequence from byte b0 on, allocated up to a multiple of LQ_GC_TILE; off[0..n] are the reads' offsets
 // in the whole sequence.  gc[r] += G/C bytes of read r inside [b0, b1).
 __global__ void __launch_bounds__(LQ_GC_THREADS)
 k_gc_reads(const u8 *buf, u64 b0, u64 b1, const u64 *off, u32 n, u32 *gc)

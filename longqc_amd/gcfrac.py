@@ -46,10 +46,10 @@ def _flatten(seqs: Sequence) -> Tuple[bytes, np.ndarray]:
     return flat, off
 
 
-def _call(lib, device, flat, off, chunk_size, k, pos_in, seed, first_read):
-    """lqgc_reads on flat buffers -> (gc, pos, win_gc, kept); pos / win_gc / kept are None when k is None"""
-    lib = _lib(lib)
-    n = int(off.shape[0] - 1)
+def _call(lib, device, flat, off, chunk_size, k, pos_in, seed, first_read, chunk=None):
+    """lqgc_reads on flat buffers -- or lqchunk_gc on a chunkpass.ReadChunk, flat and off then unused -- -> (gc, pos, win_gc, kept);
+    pos / win_gc / kept are None when k is None"""
+    n = chunk.n if chunk is not None else int(off.shape[0] - 1)
     gc = np.zeros(max(n, 1), dtype=np.uint32)
     doff = pos = win = kept = None
     if k is not None:
@@ -64,14 +64,17 @@ def _call(lib, device, flat, off, chunk_size, k, pos_in, seed, first_read):
         pos = np.zeros(max(nd, 1), dtype=np.uint32)
         win = np.zeros(max(nd, 1), dtype=np.uint16)
         kept = np.zeros(max(n, 1), dtype=np.uint32)
-    err = C.create_string_buffer(512)
-    rc = lib.lqgc_reads(device, n, flat if len(flat) else None, off.ctypes.data, chunk_size,
-                        k.ctypes.data if k is not None else None, doff.ctypes.data if k is not None else None,
-                        pos_in.ctypes.data if pos_in is not None else None, seed, first_read, gc.ctypes.data,
-                        pos.ctypes.data if k is not None else None, win.ctypes.data if k is not None else None,
-                        kept.ctypes.data if k is not None else None, err, 512)
-    if rc != 0:
-        raise api.LqcovError(rc, err.value.decode())
+    tail = (k.ctypes.data if k is not None else None, doff.ctypes.data if k is not None else None,
+            pos_in.ctypes.data if pos_in is not None else None, seed, first_read, gc.ctypes.data,
+            pos.ctypes.data if k is not None else None, win.ctypes.data if k is not None else None,
+            kept.ctypes.data if k is not None else None)
+    if chunk is not None:
+        chunk.gc(chunk_size, *tail)
+    else:
+        err = C.create_string_buffer(512)
+        rc = _lib(lib).lqgc_reads(device, n, flat if len(flat) else None, off.ctypes.data, chunk_size, *tail, err, 512)
+        if rc != 0:
+            raise api.LqcovError(rc, err.value.decode())
     if k is None:
         return gc[:n], None, None, None
     return gc[:n], pos[:nd], win[:nd], kept[:n]
@@ -105,11 +108,14 @@ class LqGCMI355X:
         self.n_reads = 0                                           # reads seen so far: the ordinal of the next chunk's first read
         self.last_pos = None                                       # the last call's positions, read after read in draw order
 
-    def calc_read_and_chunk_gc_frac(self, reads, samp_rate=0.2):
+    def calc_read_and_chunk_gc_frac(self, reads, samp_rate=0.2, chunk=None):
         """reads: LongQC's [name, seq, ...] records (seq str or bytes, upper case as the reference expects).  A read without
         bases raises ZeroDivisionError and one with more draws than bases ValueError, where the reference does, with the reads
-        before it (and, for ValueError, its own read-level numbers) accumulated as the reference leaves them."""
+        before it (and, for ValueError, its own read-level numbers) accumulated as the reference leaves them.
+        chunk: the chunkpass.ReadChunk made of `reads`: the counts come from its device copy, nothing is gathered or uploaded."""
         cs = self.chunk_size
+        if chunk is not None:
+            return self._calc_on_chunk(chunk, samp_rate)
         seqs = [r[1] for r in reads]
         n = len(seqs)
         lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=n)
@@ -125,6 +131,27 @@ class LqGCMI355X:
             drawn = [np.random.choice(int(lens[i]), int(k[i]), replace=False) for i in range(stop)]
             pos_in = np.concatenate(drawn).astype(np.uint32) if drawn else np.zeros(0, dtype=np.uint32)
         gc, self.last_pos, win, kept = _call(self.lib, self.device, flat, off, cs, k.astype(np.uint32), pos_in, self.seed, self.n_reads)
+        self._accumulate(n, stop, n_read_level, lens, k, gc, win, kept, samp_rate)
+
+    def _calc_on_chunk(self, chunk, samp_rate):
+        """the same on a resident chunk: every read of the chunk is counted, the reads behind the one the reference's loop ends in
+        draw nothing and are left out of the sums"""
+        cs, n, lens = self.chunk_size, chunk.n, chunk.lens
+        k = draws_per_read(lens, cs, samp_rate)
+        bad = np.flatnonzero((lens == 0) | (k > lens) | (k < 0))
+        stop = int(bad[0]) if bad.size else n
+        n_read_level = stop + 1 if stop < n and lens[stop] > 0 else stop
+        k = k.copy()
+        k[stop:] = 0
+        pos_in = None
+        if self.draw == "numpy":
+            drawn = [np.random.choice(int(lens[i]), int(k[i]), replace=False) for i in range(stop)]
+            pos_in = np.concatenate(drawn).astype(np.uint32) if drawn else np.zeros(0, dtype=np.uint32)
+        gc, self.last_pos, win, kept = _call(self.lib, self.device, None, None, cs, k.astype(np.uint32), pos_in, self.seed, self.n_reads, chunk=chunk)
+        self._accumulate(n, stop, n_read_level, lens[:n_read_level], k[:n_read_level], gc[:n_read_level], win, kept[:n_read_level], samp_rate)
+
+    def _accumulate(self, n, stop, n_read_level, lens, k, gc, win, kept, samp_rate):
+        cs = self.chunk_size
         self.n_reads += stop
         # gc_n / l: the correctly rounded float64 quotient of two integers, rounded once more by array('f')
         self.r_frac.frombytes((gc.astype(np.float64) / lens.astype(np.float64)).astype(np.float32).tobytes())

@@ -196,22 +196,29 @@ def coverage_in_memory(chunks: Iterable, s_reads, preset: str = "ont-ligation", 
     return text
 
 
+def set_query_reads(eng, sets) -> None:
+    """the queries of one pass over the targets: the reads of the one (reads, argv) of `sets`, or one query set per entry, each with
+    the -p / -q of its argv"""
+    from . import api
+    if len(sets) == 1:
+        qn, qs, qq = _to_arrays([r for r in sets[0][0] if r])
+        eng.set_queries(qn, qs, qq)
+        return
+    qsets = []
+    for reads, argv in sets:
+        ps, _, _ = api.parse_args(argv)
+        qn, qs, qq = _to_arrays([r for r in reads if r])
+        qsets.append((qn, qs, qq, int(ps.min_score_med), int(ps.min_score_good)))
+    eng.set_query_sets(qsets)
+
+
 def _coverage_pass(chunks: Iterable, sets, device: int, engine) -> List[str]:
     """one pass over the target chunks for every (reads, argv) of `sets`; the argvs differ at most in -p -> one table per set"""
     from . import api
     p, _, _ = api.parse_args(sets[0][1])
     eng = engine or api.Engine(p, device=device)
     try:
-        if len(sets) == 1:
-            qn, qs, qq = _to_arrays([r for r in sets[0][0] if r])
-            eng.set_queries(qn, qs, qq)
-        else:
-            qsets = []
-            for reads, argv in sets:
-                ps, _, _ = api.parse_args(argv)
-                qn, qs, qq = _to_arrays([r for r in reads if r])
-                qsets.append((qn, qs, qq, int(ps.min_score_med), int(ps.min_score_good)))
-            eng.set_query_sets(qsets)
+        set_query_reads(eng, sets)
         batch = int(p.batch_size)
         mini = min(int(p.idx_mini_batch), batch)
         part, part_bases, pend, pend_bases = None, 0, [], 0

@@ -46,8 +46,12 @@ def run_sdust(fin: str, fout: str, device: int = 0, w: Optional[int] = None, t: 
 
 
 def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional[Sequence[Optional[np.ndarray]]] = None,
-               device: int = 0, w: int = 64, t: int = 20, lib=None) -> List[str]:
-    """Reads in memory (no temporary FASTQ as in lq_mask.py:108-114) -> the rows `sdust` would print for them."""
+               device: int = 0, w: int = 64, t: int = 20, lib=None, chunk=None) -> List[str]:
+    """Reads in memory (no temporary FASTQ as in lq_mask.py:108-114) -> the rows `sdust` would print for them.
+    chunk: a chunkpass.ReadChunk that holds these reads on the device already -- seqs and quals are not looked at, nothing is
+    gathered or uploaded."""
+    if chunk is not None:
+        return _rows(names, chunk.n, chunk.off, chunk.qual_array(), *chunk.sdust(w, t))
     lib = _lib(lib)
     n = len(seqs)
     off = np.zeros(n + 1, dtype=np.uint64)
@@ -68,6 +72,10 @@ def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional
                            w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data, err, 512)
     if rc != 0:
         raise api.LqcovError(rc, err.value.decode())
+    return _rows(names, n, off, qflat, masked, psum, qv)
+
+
+def _rows(names, n, off, qflat, masked, psum, qv) -> List[str]:
     rows = []
     for i in range(n):
         ln = int(off[i + 1] - off[i])
@@ -99,7 +107,11 @@ class LqMaskMI355X:
             v = v.encode()
         return np.frombuffer(bytes(v), dtype=np.uint8)
 
-    def submit_sdust(self, reads, chunk_n):
+    def submit_sdust(self, reads, chunk_n, chunk=None):
+        """chunk: the chunkpass.ReadChunk made of `reads` (its device copy is scanned; `reads` is not gathered again)"""
+        if chunk is not None:
+            self._chunks[chunk_n] = sdust_rows(chunk.names, None, None, chunk=chunk)
+            return
         names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
         seqs = [self._arr(r[1]) for r in reads]
         quals = [self._arr(r[2]) if len(r) > 2 and r[2] else None for r in reads]
