@@ -391,6 +391,27 @@ int      lqstore_append(lqstore *s, lqchunk *c, const char *names, const uint64_
 uint64_t lqstore_bytes(const lqstore *s);            /* device bytes held */
 int      lqstore_run(lqstore *s, lqcov_handle *h);
 
+/* ---- the chunk loop's source: a plain or gzip FASTA/FASTQ file as resident chunks (lq_utils.py:263-289, parse_fastx_chunk) ---------- */
+/* lqreader_next fills `c` (a handle of the reader's device) with the next chunk of the file: the records are kseq's (the name up to
+ * the first whitespace, sequence lines concatenated, one trailing '\r' per line dropped, a truncated quality string ends the stream
+ * after the records before it); a record without a quality string gets '!' for every base; is_upper turns a-z of the sequences into
+ * A-Z on the device.  The chunk rule is the reference's: per record size += 3 * str_overhead + len(name) + 2 * len(seq)
+ * (sys.getsizeof of the three str objects; str_overhead = sys.getsizeof("")), the chunk ends with the record that makes
+ * size >= chunk_size.  *last = 1: the file has ended and this (possibly empty) chunk is the last one -- one such chunk always comes.
+ * n_seqs_cum / n_bases_cum count the whole file so far.  The chunk is as after lqchunk_load (with qualities); lqreader_names points
+ * at the names (NUL-terminated, name_off with n + 1 entries: the arguments of lqstore_append) and the lengths of the chunk made last,
+ * valid until the next lqreader_next.  lqchunk_get_reads copies the bases (and, qual_out != NULL, the qualities) of the reads
+ * idx[0 .. n_idx) -- idx == NULL: of all reads -- back to back to the host.  Errors: LQCOV_E_IO (the file cannot be opened: NULL from
+ * lqreader_open, the message is lqreader_last_error(NULL)'s), LQCOV_E_DOMAIN (a name byte of 0x80 or more, a read of 2^31 bases),
+ * LQCOV_E_STATE (lqreader_next after the last chunk).  n_threads <= 0: the default (at most 16). */
+typedef struct lqreader lqreader;
+lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int is_upper, uint32_t str_overhead, int n_threads);
+int  lqreader_next(lqreader *r, lqchunk *c, uint32_t *n, uint64_t *n_seqs_cum, uint64_t *n_bases_cum, int *last);
+int  lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens);
+void lqreader_close(lqreader *r);
+const char *lqreader_last_error(const lqreader *r);
+int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,7 +74,8 @@ def _identity(rows: np.ndarray) -> np.ndarray:
 
 
 def _cut(reads, rows, th, r, three, len_list, lens):
-    """_cutf (three=False, lq_adapt.py:45-78) / _cutr (three=True, :10-43) on rows computed for the untrimmed reads."""
+    """_cutf (three=False, lq_adapt.py:45-78) / _cutr (three=True, :10-43) on rows computed for the untrimmed reads.
+    reads None: nothing to trim, the tuple alone (it needs the rows and the lengths only)."""
     has_qual = len(reads[0]) > 2 if reads else False
     if len_list:                                                   # (only a non-empty list is appended to)
         len_list.extend(int(x) for x in lens)
@@ -84,6 +85,9 @@ def _cut(reads, rows, th, r, three, len_list, lens):
     hit = np.flatnonzero(ok & (ident > th))
     iden_max = float(ident[hit].max()) if hit.size else -1
     cut_pos = []
+    if reads is None:
+        cut_pos = (r - rows[hit, 1].astype(np.int64)).tolist() if three else rows[hit, 2].astype(np.int64).tolist()
+        hit = hit[:0]
     for i in hit.tolist():
         read = reads[i]
         if three:
@@ -100,21 +104,21 @@ def _cut(reads, rows, th, r, three, len_list, lens):
             if has_qual:
                 read[2] = read[2][e + 1:]
     logger.info("%d reads were skipped due to their short lengths." % skip_num)
-    return (iden_max, int(hit.size), cut_pos)
+    return (iden_max, len(cut_pos), cut_pos)
 
 
 def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=150, device=0, lib=None, chunk=None):
     """== lq_adapt.cut_adapter (lq_adapt.py:80-101): reads are LongQC's mutable [name, seq, qual, ...] records, trimmed in
     place; returns (iden_max, match_num, cut_pos) for one adapter, ((...5'), (...3')) for two, None (logged) for none.
     chunk: a chunkpass.ReadChunk made of these (untrimmed) reads: the search runs on its device copy, which stays as it is;
-    nothing is gathered or uploaded."""
+    nothing is gathered or uploaded.  With a chunk, reads may be None: the tuples alone, no record is trimmed."""
     if not adp_t and not adp_b:
         logger.error("No adapter sequence is given.")
         return None
     if chunk is not None:
         if not 1 <= length <= 4096:
             raise ValueError("length must lie in [1, 4096]")
-        if len(reads) != chunk.n:
+        if reads is not None and len(reads) != chunk.n:
             raise ValueError("the chunk does not hold these reads")
         o5, o3 = chunk.adapt(_bytes(adp_t) if adp_t else None, _bytes(adp_b) if adp_b else None, length)
         lens = chunk.lens.copy()
@@ -128,7 +132,7 @@ def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=15
         logger.info("Adapter Sequence: %s, max identity:%f and the number of trimmed reads: %d" % (adp_t, t5[0], t5[1]))
         if adp_b:                                                  # the 3' skip test sees the 5'-trimmed length
             lens = lens.copy()
-            hit5 = np.zeros(len(reads), dtype=bool)
+            hit5 = np.zeros(lens.shape[0], dtype=bool)
             ok5 = lens >= 2 * length
             hit5[ok5] = _identity(o5[ok5]) > th
             lens[hit5] -= o5[hit5, 2].astype(np.int64) + 1

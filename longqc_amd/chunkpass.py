@@ -1,12 +1,18 @@
 """One upload per chunk: the chunk loop of `longQC.py sampleqc` (longQC.py:299-360) and the coverage call (:438-445) on the same
 device bytes, over the lqchunk_* / lqstore_* calls of include/lqcov.h.
 
+FileChunks is the loop's source, lq_utils.open_seq_chunk for a plain or gzip FASTA/FASTQ file (lqreader_*): it yields
+(chunk, n_seqs, n_bases) with `chunk` a ReadChunk that the library filled on the device straight from the file -- no read is a Python
+object, the bases are never on the host.  SampleQCPass.run_file(path) is the whole loop on such chunks.
+
 ReadChunk gathers a chunk's [name, seq, qual] records into flat arrays once and uploads them once; sdust.sdust_rows,
 adapter.cut_adapter and LqGCMI355X.calc_read_and_chunk_gc_frac take it as `chunk=` and then run on the device copy.
 SampleQCPass is the loop's body and the coverage call: add_chunk(reads) per chunk -- low-complexity rows, adapter search,
 subsample, GC fractions, then the chunk is 2-bit packed on the device and kept there -- and coverage(), which maps the subsample
 against the kept chunks without touching the input again.  No CPU fallback: without liblqcov.so or a HIP device the calls raise."""
 import ctypes as C
+import math
+import sys
 from typing import Optional
 
 import numpy as np
@@ -33,6 +39,12 @@ def _lib(lib=None):
             "lqstore_append": (C.c_int, [H, H, C.c_char_p, P]),
             "lqstore_bytes": (C.c_uint64, [H]),
             "lqstore_run": (C.c_int, [H, H]),
+            "lqchunk_get_reads": (C.c_int, [H, C.c_uint32, P, P, P]),
+            "lqreader_open": (H, [C.c_char_p, C.c_int, C.c_uint64, C.c_int, C.c_uint32, C.c_int]),
+            "lqreader_next": (C.c_int, [H, H, P, P, P, P]),
+            "lqreader_names": (C.c_int, [H, P, P, P]),
+            "lqreader_close": (None, [H]),
+            "lqreader_last_error": (C.c_char_p, [H]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -53,7 +65,7 @@ def _join(items, n):
 class ReadChunk:
     """A chunk of LongQC's [name, seq, qual, ...] records on the device.  n, names, lens (int64), off (uint64, n + 1) describe it on
     the host; the records themselves are not kept.  load(reads) puts another chunk into the same handle, whose device buffers
-    are used again and grow."""
+    are used again and grow.  reads=None: an empty handle, for FileChunks to fill.  records(idx) brings reads back as lists."""
 
     def __init__(self, reads, device: int = 0, lib=None):
         self.lib = _lib(lib)
@@ -61,11 +73,14 @@ class ReadChunk:
         self.h = self.lib.lqchunk_create(device)
         if not self.h:
             raise api.LqcovError(-3, self.lib.lqchunk_last_error(None).decode() or "lqchunk_create failed (no HIP device?)")
-        self.load(reads)
+        self.n, self.names, self.lens, self.off = 0, [], np.zeros(0, np.int64), np.zeros(1, np.uint64)
+        self.qflat, self.packed, self.from_file, self._name_blob = None, False, False, None
+        if reads is not None:
+            self.load(reads)
 
     def load(self, reads):
         n = self.n = len(reads)
-        self.packed = False
+        self.packed, self.from_file, self._name_blob = False, False, None
         self.names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
         self.flat, self.lens = _join([r[1] for r in reads], n)
         self.off = np.zeros(n + 1, dtype=np.uint64)
@@ -78,6 +93,9 @@ class ReadChunk:
             if (qlens != self.lens).any():
                 raise ValueError("a quality string differs in length from its read")
         self._ck(self.lib.lqchunk_load(self.h, n, self.flat if len(self.flat) else None, self.off.ctypes.data, self.qflat))
+
+    def __len__(self):
+        return self.n
 
     def _ck(self, rc: int):
         if rc != 0:
@@ -94,8 +112,47 @@ class ReadChunk:
         except Exception:
             pass
 
+    def _from_reader(self, reader, n: int):
+        """the chunk lqreader_next has just put into the handle: names, lengths and offsets from lqreader_names"""
+        names, noff, lens = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self.lib.lqreader_names(reader, C.byref(names), C.byref(noff), C.byref(lens)) != 0:
+            raise api.LqcovError(-1, "lqreader_names failed")
+        self.n, self.packed, self.from_file, self.flat, self.qflat = n, False, True, None, None
+        name_off = np.ctypeslib.as_array(C.cast(noff, C.POINTER(C.c_uint64)), (n + 1,)).copy()
+        blob = C.string_at(names, int(name_off[n]))
+        self._name_blob = (blob, name_off)                          # as lqstore_append takes them
+        self.names = blob.decode("ascii").split("\0")[:n]
+        self.lens = np.ctypeslib.as_array(C.cast(lens, C.POINTER(C.c_uint32)), (n,)).astype(np.int64) if n else np.zeros(0, np.int64)
+        self.off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(self.lens, out=self.off[1:])
+
     def qual_array(self) -> Optional[np.ndarray]:
         return None if self.qflat is None else np.frombuffer(self.qflat, dtype=np.uint8)
+
+    def qual_first(self):
+        """what sdust._rows asks the qualities: the host copy (its first byte per read tells whether the read has any), None without
+        qualities, True for a chunk read from a file -- there every read with bases has qualities ('!' where the file had none), and
+        they are on the device only"""
+        return True if self.from_file else self.qual_array()
+
+    def records(self, idx=None):
+        """-> [name, seq, qual] lists (str; [name, seq] for a chunk loaded without qualities) of the reads `idx` (default: all), copied
+        back from the device: lqchunk_get_reads"""
+        idx = np.arange(self.n, dtype=np.uint32) if idx is None else np.ascontiguousarray(idx, dtype=np.uint32)
+        with_qual = self.from_file or self.qflat is not None
+        lens = self.lens[idx.astype(np.int64)] if idx.size else np.zeros(0, np.int64)
+        total = int(lens.sum())
+        seq = np.empty(max(total, 1), np.uint8)
+        qual = np.empty(max(total, 1), np.uint8) if with_qual else None
+        self._ck(self.lib.lqchunk_get_reads(self.h, idx.size, idx.ctypes.data if idx.size else None, seq.ctypes.data,
+                                            qual.ctypes.data if with_qual else None) if idx.size else 0)
+        s = seq[:total].tobytes().decode("latin-1")
+        q = qual[:total].tobytes().decode("latin-1") if with_qual else None
+        out, a = [], 0
+        for i, l in zip(idx.tolist(), lens.tolist()):
+            out.append([self.names[i], s[a:a + l], q[a:a + l]] if with_qual else [self.names[i], s[a:a + l]])
+            a += l
+        return out
 
     # -- the steps, as arrays --
     def sdust(self, w: int = 64, t: int = 20):
@@ -133,6 +190,42 @@ class ReadChunk:
         return codes[:nc * 4], amb[:nc * 4], flags[:self.n]
 
 
+class FileChunks:
+    """lq_utils.open_seq_chunk(path, ..., is_upper, chunk_size) for a plain or gzip FASTA/FASTQ file, on the device: iterating yields
+    (chunk, n_seqs, n_bases) -- chunk a ReadChunk filled from the file (n, names, lens, off, len(); records(idx) for the lists), n_seqs
+    and n_bases cumulative over the file, and after the last record one more chunk, empty if the last record ended a chunk.  The chunk
+    is the same object every time and valid until the next iteration: its handle's buffers are used again.  Every iteration starts
+    the file anew.  str_overhead: sys.getsizeof("") of the interpreter whose chunk borders are wanted (49 or 41, by the CPython
+    version; default: this interpreter's)."""
+
+    def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
+                 lib=None, n_threads: int = 0):
+        self.lib = _lib(lib)
+        self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
+        self.chunk_size = max(0, int(math.ceil(chunk_size)))        # size >= chunk_size for an integer size
+        self.str_overhead = sys.getsizeof("") if str_overhead is None else int(str_overhead)
+
+    def __iter__(self):
+        lib = self.lib
+        r = lib.lqreader_open(self.path.encode(), self.device, self.chunk_size, int(bool(self.is_upper)), self.str_overhead, self.n_threads)
+        if not r:
+            raise api.LqcovError(-2, lib.lqreader_last_error(None).decode() or "lqreader_open failed")
+        chunk = None
+        try:
+            chunk = ReadChunk(None, device=self.device, lib=lib)
+            n, n_seqs, n_bases, last = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int()
+            while not last.value:
+                rc = lib.lqreader_next(r, chunk.h, C.byref(n), C.byref(n_seqs), C.byref(n_bases), C.byref(last))
+                if rc != 0:
+                    raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
+                chunk._from_reader(r, n.value)
+                yield chunk, n_seqs.value, n_bases.value
+        finally:
+            lib.lqreader_close(r)
+            if chunk is not None:
+                chunk.close()
+
+
 class PackedStore:
     """The packed chunks of the whole input in device memory (lqstore_*)."""
 
@@ -145,7 +238,7 @@ class PackedStore:
     def append(self, chunk: ReadChunk):
         if not chunk.packed:
             chunk.pack()
-        nb, noff = api.encode_names(chunk.names)
+        nb, noff = chunk._name_blob or api.encode_names(chunk.names)
         chunk._ck(self.lib.lqstore_append(self.h, chunk.h, nb, noff.ctypes.data))
 
     @property
@@ -192,21 +285,42 @@ class SampleQCPass:
     def add_chunk(self, reads):
         chunk = ReadChunk(reads, device=self.device, lib=self.lib)
         try:
-            self.mask.submit_sdust(reads, self.chunk_n, chunk=chunk)                                    # longQC.py:307
-            result = None
-            if self.adp5 or self.adp3:                                                                  # :310-320, on a copy as the pool's pickling makes one
-                self.trimmed = [list(r) for r in reads]
-                result = adapter.cut_adapter(self.trimmed, adp_t=self.adp5, adp_b=self.adp3, chunk=chunk)
-                self.adapters.add(result)                                                               # :348-357
-            self.s_reads = sampleqc.subsample_from_chunk(reads, self.cum_n_seq, self.s_reads, self.nsample)    # :323
-            self.gc.calc_read_and_chunk_gc_frac(reads, chunk=chunk)                                     # :328
-            self.store.append(chunk)
+            return self._add(chunk, reads, True)
         finally:
             chunk.close()
+
+    def add_resident(self, chunk: ReadChunk, trim: bool = False):
+        """add_chunk on a chunk that is on the device already (FileChunks'): nothing is gathered or uploaded, and of the reads only
+        the subsample's winners come to the host -- with trim=True (--trim) all of them, for `trimmed`"""
+        return self._add(chunk, None, trim)
+
+    def _add(self, chunk, reads, trim):
+        self.mask.submit_sdust(reads, self.chunk_n, chunk=chunk)                                        # longQC.py:307
+        result = None
+        if self.adp5 or self.adp3:                                                                      # :310-320, on a copy as the pool's pickling makes one
+            self.trimmed = ([list(r) for r in reads] if reads is not None else chunk.records()) if trim else None
+            result = adapter.cut_adapter(self.trimmed, adp_t=self.adp5, adp_b=self.adp3, chunk=chunk)
+            self.adapters.add(result)                                                                   # :348-357
+        if reads is not None:
+            self.s_reads = sampleqc.subsample_from_chunk(reads, self.cum_n_seq, self.s_reads, self.nsample)    # :323
+        else:
+            self.s_reads = sampleqc.subsample_from_resident(chunk, self.cum_n_seq, self.s_reads, self.nsample)
+        self.gc.calc_read_and_chunk_gc_frac(reads, chunk=chunk)                                         # :328
+        self.store.append(chunk)
         self.chunk_n += 1
-        self.cum_n_seq += len(reads)
+        self.cum_n_seq += chunk.n
         self.n_bases += int(chunk.lens.sum())
         return result
+
+    def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim: bool = False, is_upper: bool = True, str_overhead: Optional[int] = None):
+        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file: FileChunks + add_resident.  -> the per-chunk
+        adapter results; with trim=True `trimmed_chunks` holds every chunk's trimmed records (longQC.py:330-338 writes them out)"""
+        results, self.trimmed_chunks = [], []
+        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib):
+            results.append(self.add_resident(chunk, trim=trim))
+            if trim:
+                self.trimmed_chunks.append(self.trimmed)
+        return results
 
     def coverage(self, s_reads=None, short_threshold: Optional[int] = None, out: Optional[str] = None, exclude_seqs=None, chunks=None):
         """The coverage table of the subsample (s_reads: another query set) against every chunk added, as

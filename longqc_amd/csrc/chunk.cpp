@@ -7,6 +7,7 @@
 #include "engine.hpp"
 #include "chunk.hpp"
 #include "kernels_chunk.hpp"
+#include "kernels_gather.hpp"
 #include <algorithm>
 #include <memory>
 
@@ -41,6 +42,50 @@ void lq_chunk_ready(lqchunk &c)
 	}
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // the caller's buffers are free again
 	c.h_seq = c.h_qual = nullptr;
+	c.resident = true;
+}
+
+static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &segs, u8 *dst, bool upper)
+{
+	const u64 total = c.total;
+	if (!total) return;
+	const u64 n_segs = segs.size(), n_tiles = (total + LQ_GATHER_TILE - 1) / LQ_GATHER_TILE;
+	if (n_segs > 0xffffffffULL) throw std::domain_error("more than 2^32-1 lines in one chunk");
+	segs.push_back({0, total});
+	std::vector<u32> tile_seg((size_t)n_tiles + 1);           // the work list: the segment that holds the first byte of every tile
+	{
+		u64 s = 0;
+		for (u64 t = 0; t < n_tiles; ++t) {
+			while (s + 1 < n_segs && segs[s + 1].dst <= t * LQ_GATHER_TILE) ++s;
+			tile_seg[t] = (u32)s;
+		}
+		tile_seg[n_tiles] = (u32)(n_segs - 1);
+	}
+	c.gseg.ensure((n_segs + 1) * sizeof(GatherSeg)); c.gtile.ensure((n_tiles + 1) * 4);
+	LQ_HIP_CHECK(hipMemcpyAsync(c.gseg.p, segs.data(), (n_segs + 1) * sizeof(GatherSeg), hipMemcpyHostToDevice, c.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(c.gtile.p, tile_seg.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, c.stream));
+	const u32 grid = (u32)std::min<u64>(n_tiles, LQ_GATHER_MAX_BLOCKS);
+	LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
+	LQ_HIP_CHECK(hipGetLastError());
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (tile_seg dies here, and the two device lists serve the next launch)
+}
+
+void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper)
+{
+	lq_cabi::select_device(c.device);
+	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
+	const u32 n = (u32)(off.size() - 1);
+	c.resident = false; c.packed = false; c.n_chunks = 0;
+	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
+	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
+	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
+	const u64 words = (total + 15) / 16 * 16;
+	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + 16); c.d_off.ensure(((size_t)n + 1) * 8);
+	LQ_HIP_CHECK(hipMemsetAsync(c.seq.as<u8>() + words, 0, (size_t)(alloc - words), c.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+	gather_launch(c, raw, sseg, c.seq.as<u8>(), upper);
+	gather_launch(c, raw, qseg, c.qual.as<u8>(), false);
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
 	c.resident = true;
 }
 
@@ -171,6 +216,31 @@ int lqchunk_get_packed(lqchunk *c, uint64_t *codes, uint32_t *amb, uint8_t *amb_
 		LQ_HIP_CHECK(hipMemcpyAsync(codes, c->codes.p, n_words * 8, hipMemcpyDeviceToHost, c->stream));
 		LQ_HIP_CHECK(hipMemcpyAsync(amb, c->amb.p, n_words * 4, hipMemcpyDeviceToHost, c->stream));
 		LQ_HIP_CHECK(hipMemcpyAsync(amb_flags, c->flags.p, c->n, hipMemcpyDeviceToHost, c->stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(c->stream));
+	});
+}
+
+int lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out)
+{
+	return chunk_guard(c, [&] {
+		need_loaded(*c);
+		if (qual_out && !c->has_qual) throw std::invalid_argument("the chunk holds no qualities");
+		const u32 n = idx ? n_idx : c->n;
+		for (u32 i = 0; idx && i < n; ++i) if (idx[i] >= c->n) throw std::invalid_argument("a read index outside the chunk");
+		lq_cabi::select_device(c->device);
+		u64 at = 0;
+		for (u32 i = 0; i < n;) {                                 // runs of consecutive reads travel in one copy
+			const u32 r0 = idx ? idx[i] : 0;
+			u32 j = idx ? i + 1 : n;
+			while (idx && j < n && idx[j] == idx[j - 1] + 1) ++j;
+			const u64 a = c->off[r0], b = c->off[r0 + (j - i)];
+			if (b > a) {
+				if (!seq_out) throw std::invalid_argument("null buffers");
+				LQ_HIP_CHECK(hipMemcpyAsync(seq_out + at, c->seq.as<u8>() + a, (size_t)(b - a), hipMemcpyDeviceToHost, c->stream));
+				if (qual_out) LQ_HIP_CHECK(hipMemcpyAsync(qual_out + at, c->qual.as<u8>() + a, (size_t)(b - a), hipMemcpyDeviceToHost, c->stream));
+			}
+			at += b - a; i = j;
+		}
 		LQ_HIP_CHECK(hipStreamSynchronize(c->stream));
 	});
 }

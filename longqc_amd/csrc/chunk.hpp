@@ -9,6 +9,12 @@
 
 #define LQ_CHUNK_SEQ_TILE 4096u      // the sequence buffer is allocated in whole tiles of k_gc_reads (LQ_GC_TILE)
 
+// what the file reader (reader.cpp) hands to k_chunk_gather (kernels_gather.hpp): a run of the file's raw bytes on the device that
+// lands at one place of the chunk's sequence or quality buffer
+struct alignas(16) GatherSeg { u64 src, dst; };        // source byte, destination byte of the segment's first byte
+#define LQ_GATHER_FILL LQ_U64MAX     // src of a segment without source bytes: '!' (a record without a quality string)
+#define LQ_GATHER_SRC_PAD 32u        // bytes the raw buffer extends past its last byte
+
 struct lqchunk {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -25,6 +31,7 @@ struct lqchunk {
 	DBuf woff, adp5, adp3, out;                               // adapter search: window offsets, adapters, result rows
 	DBuf draw_off, gc, pos, win, kept;                        // GC counts
 	DBuf coff, tile_read, codes, amb, flags;                  // packed form
+	DBuf gseg, gtile;                                         // k_chunk_gather's segments and work list
 	std::vector<u64> h_coff;                                  // packed chunks before read i
 	u64 n_chunks = 0; bool packed = false;
 	~lqchunk() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }
@@ -35,6 +42,10 @@ struct lqchunk {
 void lq_chunk_set(lqchunk &c, u32 n, const u8 *seq, const u64 *seq_off, const u8 *qual);
 // select the device, make the stream, upload what lq_chunk_set described (once)
 void lq_chunk_ready(lqchunk &c);
+// a chunk made on the device from the raw bytes of a file (reader.cpp): read i = bases off[i] .. off[i + 1]; sseg / qseg: the segments
+// of the sequence and of the quality buffer, in destination order and without gaps (one entry is appended to each).  Leaves the chunk
+// as lq_chunk_set + lq_chunk_ready leave one that has qualities.
+void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper);
 void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
 void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
 void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,

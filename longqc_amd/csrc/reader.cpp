@@ -1,0 +1,310 @@
+// longqc_amd/csrc/reader.cpp -- the chunk loop's source behind the C ABI of include/lqcov.h (lqreader_*): what lq_utils.open_seq_chunk /
+// parse_fastx_chunk (lq_utils.py:263-289, pysam.FastxFile = kseq) yield for a plain or gzip FASTA/FASTQ file, as resident chunks.
+// The file is read (pread) or inflated (zlib) into a page-locked piece; the piece is parsed in place, record by record, into
+// descriptors -- the name, the line segments of the sequence and of the quality string -- and uploaded as it is: the host looks at
+// every byte once and copies none of the bases (what is copied is the one record that straddles the end of a piece: it moves to the
+// front of the piece before the next read fills the rest).  k_chunk_gather (kernels_gather.hpp) then makes the chunk's flat sequence
+// and quality buffers on the device, upper-casing the sequence if asked and giving records without a quality string '!'.
+//
+// The record grammar is kseq's, as fastx.hpp and fastx_mem.hpp state it; here the parser may stand at the end of what has been read
+// so far and not at the end of the file, so it parses one record at a time and gives up (to be called again with more bytes) wherever
+// kseq would have read on.  The chunk rule is parse_fastx_chunk's: size += getsizeof(name) + getsizeof(seq) + getsizeof(qual), a
+// chunk ends with the record that makes size >= chunk_size; for an ASCII str getsizeof is str_overhead + len.
+#include "chunk.hpp"
+#include "fastx_mem.hpp"
+#include <zlib.h>
+#include <cstdlib>
+#include <memory>
+
+namespace {
+thread_local std::string g_reader_open_error;
+
+struct Line { u64 at; u64 len; };                             // bytes of the piece
+
+struct Record {
+	u64 name_at = 0, name_len = 0, seq_len = 0;
+	bool has_qual = false;
+	std::vector<Line> seq, qual;
+};
+
+enum { REC = 0, NEED_MORE = 1, END = 2 };
+} // namespace
+
+struct lqreader {
+	std::string path, err;
+	int device = 0;
+	u64 chunk_size = 0, overhead = 49;
+	bool upper = true;
+	int n_threads = 1;
+	// the file
+	int fd = -1; gzFile gz = nullptr; u64 file_pos = 0;
+	bool eof = false;                                         // nothing more to read
+	bool over = false;                                        // no more records: the end of the file, or a truncated quality string (kseq: -2)
+	bool done = false;                                        // the last chunk has been handed out
+	// the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet
+	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
+	int last_char = 0;                                        // kseq's: the header character at pos - 1 has been consumed
+	u64 n_seqs = 0, n_bases = 0;
+	// the chunk being made
+	DBuf raw; u64 raw_used = 0;
+	std::vector<GatherSeg> sseg, qseg;
+	std::vector<char> names; std::vector<u64> name_off, off; std::vector<u32> lens;
+	Record rec;
+
+	~lqreader()
+	{
+		if (gz) gzclose(gz);
+		if (fd >= 0) ::close(fd);
+		if (buf) lqcov_host_free(buf);
+	}
+
+	void open_file()
+	{
+		fd = ::open(path.c_str(), O_RDONLY);
+		if (fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
+		u8 magic[2] = {0, 0};
+		const bool is_gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+		if (is_gz) {
+			gz = gzdopen(fd, "r");
+			if (!gz) throw std::runtime_error("failed to open file '" + path + "'");
+			fd = -1;                                              // (the stream owns it now)
+			gzbuffer(gz, 1 << 20);
+		}
+	}
+
+	void set_piece(u64 bytes)
+	{
+		u8 *nb = (u8*)lqcov_host_alloc(bytes);
+		if (!nb) throw std::runtime_error("no page-locked memory for a piece of the file");
+		if (fill) memcpy(nb, buf, fill);
+		if (buf) lqcov_host_free(buf);
+		buf = nb; cap = bytes;
+	}
+
+	// more bytes behind buf[fill); false: the file has ended
+	bool read_more()
+	{
+		while (!eof && fill < cap) {
+			const u64 want = std::min<u64>(cap - fill, 1u << 30);
+			i64 got;
+			if (gz) {
+				got = gzread(gz, buf + fill, (unsigned)want);
+				if (got < 0) throw std::runtime_error("failed to open file '" + path + "': not a complete gzip stream");
+			} else {
+				got = ::pread(fd, buf + fill, want, (off_t)file_pos);
+				if (got < 0) throw std::runtime_error("failed to open file '" + path + "': read error");
+			}
+			if (got == 0) { eof = true; break; }
+			fill += (u64)got; file_pos += (u64)got;
+			return true;
+		}
+		return false;
+	}
+
+	// kseq_read (kseq.h:184-224) on buf[pos .. fill): one record into `rec`.  NEED_MORE: the record may go on behind what has been
+	// read, nothing is consumed but bytes in front of a header character; END: kseq returns -1 or -2.
+	int parse_one()
+	{
+		const u8 *p = buf; const u64 n = fill;
+		u64 q = pos; int lc = last_char;
+		Record &r = rec;
+		r.seq.clear(); r.qual.clear(); r.seq_len = 0; r.has_qual = false;
+		if (lc == 0) {
+			const u8 *h = MemFastx::next_header(p, q, n);
+			if (!h) { pos = n; return eof ? END : NEED_MORE; }
+			pos = (u64)(h - p);                                   // (what lies in front of a header character is never looked at again)
+			q = pos + 1; lc = *h;
+		}
+		if (q >= n) { if (!eof) return NEED_MORE; pos = n; last_char = 0; return END; }      // the stream ends behind a header character: no record
+		r.name_at = q;
+		while (q < n && !MemFastx::is_space(p[q])) ++q;
+		if (q == n && !eof) return NEED_MORE;
+		r.name_len = q - r.name_at;
+		if (q < n && p[q] != '\n') {                              // the comment
+			const u8 *e = (const u8*)memchr(p + q, '\n', n - q);
+			if (!e && !eof) return NEED_MORE;
+			q = e ? (u64)(e - p) : n;
+		}
+		q = q < n ? q + 1 : n;
+		int c = -1;
+		for (;;) {                                                // sequence lines until a line that starts with '>', '@' or '+'
+			if (q >= n) { if (!eof) return NEED_MORE; c = -1; break; }
+			c = p[q++];
+			if (c == '>' || c == '+' || c == '@') break;
+			if (c == '\n') continue;
+			const u64 l0 = q - 1;
+			const u8 *e = (const u8*)memchr(p + q, '\n', n - q);
+			if (!e && !eof) return NEED_MORE;
+			const u64 l1 = e ? (u64)(e - p) : n;
+			q = e ? l1 + 1 : n;
+			r.seq.push_back({l0, l1 - l0}); r.seq_len += l1 - l0;
+			// one trailing '\r' of the sequence so far is dropped after every line -- but for a line that is the file's last byte: kseq's
+			// ks_getuntil2 returns at the end of the stream before it looks for the '\r' (kseq.h:98; fastx_mem.hpp has the same note)
+			if (r.seq_len > 1 && p[l1 - 1] == '\r' && l0 + 1 != n) { --r.seq.back().len; --r.seq_len; }
+		}
+		if (r.seq_len > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases (bseq.c:80)");
+		if (c == '>' || c == '@') { pos = q; last_char = c; return REC; }
+		if (c != '+') { pos = n; last_char = 0; return REC; }      // the end of the file: the last record (FASTA)
+		{	// '+': the rest of that line is skipped
+			const u8 *e = q < n ? (const u8*)memchr(p + q, '\n', n - q) : nullptr;
+			if (!e) { if (!eof) return NEED_MORE; pos = n; last_char = 0; over = true; return END; }      // no quality string: kseq returns -2
+			q = (u64)(e - p) + 1;
+		}
+		u64 qlen = 0;
+		for (;;) {                                                // while (ks_getuntil2(qual, append) >= 0 && qual.l < seq.l)
+			if (q >= n) { if (!eof) return NEED_MORE; break; }
+			const u8 *e = (const u8*)memchr(p + q, '\n', n - q);
+			if (!e && !eof) return NEED_MORE;
+			const u64 l1 = e ? (u64)(e - p) : n;
+			if (l1 > q) { r.qual.push_back({q, l1 - q}); qlen += l1 - q; }
+			// kseq drops one trailing '\r' of the whole string so far, if that is longer than one character, after every line it appends
+			// (an empty line after a line that ended in "\r\r" drops the second one)
+			if (qlen > 1 && p[r.qual.back().at + r.qual.back().len - 1] == '\r') {
+				if (--r.qual.back().len == 0) r.qual.pop_back();
+				--qlen;
+			}
+			q = e ? l1 + 1 : n;
+			if (qlen >= r.seq_len) break;
+		}
+		if (qlen != r.seq_len) { pos = n; last_char = 0; over = true; return END; }      // truncated quality: kseq returns -2, the stream ends
+		pos = q; last_char = 0; r.has_qual = true;
+		return REC;
+	}
+
+	// device room for `more` raw bytes behind raw_used, what is there kept
+	void raw_reserve(hipStream_t stream, u64 more)
+	{
+		const u64 need = raw_used + more + LQ_GATHER_SRC_PAD;
+		if (need <= raw.cap) return;
+		DBuf nb;
+		nb.ensure((size_t)std::max<u64>(need, 2 * raw_used + LQ_GATHER_SRC_PAD));
+		if (raw_used) {
+			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, raw.p, (size_t)raw_used, hipMemcpyDeviceToDevice, stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		}
+		raw.swap(nb);
+		nb.release();
+	}
+
+	// buf[up_from .. pos) goes behind the raw bytes of the chunk (the descriptors made so far already point there)
+	void upload(hipStream_t stream)
+	{
+		const u64 len = pos - up_from;
+		if (len) {
+			raw_reserve(stream, len);
+			LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used, buf + up_from, (size_t)len, hipMemcpyHostToDevice, stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(stream));           // the piece is free again
+			raw_used += len;
+		}
+		up_from = pos;
+	}
+
+	// the record that straddles the piece's end moves to its front, the file goes on behind it
+	void refill(hipStream_t stream)
+	{
+		upload(stream);
+		if (pos) memmove(buf, buf + pos, (size_t)(fill - pos));
+		fill -= pos; pos = 0; up_from = 0;
+		if (fill == cap) set_piece(cap * 2);                      // a record longer than the piece
+		read_more();
+	}
+
+	void add_record()
+	{
+		const Record &r = rec;
+		const u8 *nm = buf + r.name_at;
+		for (u64 i = 0; i < r.name_len; ++i) if (nm[i] >= 0x80)
+			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
+		names.insert(names.end(), nm, nm + r.name_len); names.push_back('\0');
+		name_off.push_back(names.size());
+		// where a byte of the piece lies in the chunk's raw bytes: up_from is the first byte of the next upload, which lands at raw_used
+		u64 d = off.back();
+		for (const Line &l : r.seq) if (l.len) { sseg.push_back({raw_used + (l.at - up_from), d}); d += l.len; }
+		d = off.back();
+		if (r.has_qual) { for (const Line &l : r.qual) { qseg.push_back({raw_used + (l.at - up_from), d}); d += l.len; } }
+		else if (r.seq_len) qseg.push_back({LQ_GATHER_FILL, d});
+		off.push_back(off.back() + r.seq_len);
+		lens.push_back((u32)r.seq_len);
+		++n_seqs; n_bases += r.seq_len;
+	}
+
+	// the next chunk into c: records until the chunk rule ends it, or until the file does (*last)
+	void next(lqchunk &c, u32 *n_out, u64 *n_seqs_cum, u64 *n_bases_cum, int *last)
+	{
+		if (done) throw std::logic_error("the reader has handed out its last chunk");
+		if (c.device != device) throw std::invalid_argument("the chunk lives on another device than the reader");
+		lq_cabi::select_device(device);
+		if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
+		c.resident = false; c.packed = false; c.n_chunks = 0;
+		raw_used = 0; sseg.clear(); qseg.clear(); names.clear(); name_off.assign(1, 0); off.assign(1, 0); lens.clear();
+		if (!buf) { set_piece(piece_bytes()); read_more(); }
+		u64 size = 0; bool ended = false;
+		while (!over) {
+			const int st = parse_one();
+			if (st == NEED_MORE) { refill(c.stream); continue; }
+			if (st == END) { over = true; break; }
+			if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
+			add_record();
+			size += 3 * overhead + rec.name_len + 2 * rec.seq_len;
+			if (size >= chunk_size) { ended = true; break; }
+		}
+		upload(c.stream);
+		done = !ended;
+		lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper);
+		const u32 n = c.n;
+		*n_out = n; *n_seqs_cum = n_seqs; *n_bases_cum = n_bases; *last = done ? 1 : 0;
+	}
+
+	// LQREADER_PIECE_BYTES: the size of a piece (tests: pieces shorter than a record)
+	static u64 piece_bytes()
+	{
+		const char *e = getenv("LQREADER_PIECE_BYTES");
+		const u64 v = e ? strtoull(e, nullptr, 10) : 0;
+		return v ? std::max<u64>(v, 16) : (u64)16 << 20;
+	}
+};
+
+extern "C" {
+
+lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int is_upper, uint32_t str_overhead, int n_threads)
+{
+	try {
+		if (!path) throw std::invalid_argument("null path");
+		lq_cabi::select_device(device);
+		std::unique_ptr<lqreader> r(new lqreader());
+		r->path = path; r->device = device; r->chunk_size = chunk_size; r->upper = is_upper != 0; r->overhead = str_overhead;
+		r->n_threads = n_threads <= 0 ? 16 : std::min(n_threads, 16);
+		r->open_file();
+		return r.release();
+	} catch (const std::exception &e) { g_reader_open_error = e.what(); return nullptr; }
+}
+
+void lqreader_close(lqreader *r)
+{
+	if (!r) return;
+	(void)hipSetDevice(r->device);
+	delete r;
+}
+
+const char *lqreader_last_error(const lqreader *r) { return r ? r->err.c_str() : g_reader_open_error.c_str(); }
+
+int lqreader_next(lqreader *r, lqchunk *c, uint32_t *n, uint64_t *n_seqs_cum, uint64_t *n_bases_cum, int *last)
+{
+	if (!r) return LQCOV_E_ARG;
+	char buf[512] = {0};
+	const int rc = lq_cabi::guarded(buf, sizeof(buf), [&] {
+		if (!c || !n || !n_seqs_cum || !n_bases_cum || !last) throw std::invalid_argument("null arguments");
+		r->next(*c, n, n_seqs_cum, n_bases_cum, last);
+	});
+	if (rc) { r->err = buf; r->done = true; }                 // (a reader that failed hands out nothing more)
+	return rc;
+}
+
+int lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens)
+{
+	if (!r || !names || !name_off || !lens) return LQCOV_E_ARG;
+	*names = r->names.data(); *name_off = r->name_off.data(); *lens = r->lens.data();
+	return 0;
+}
+
+} // extern "C"

@@ -110,11 +110,32 @@ def subsample_from_chunk(chunk, cum_n_seq, s_reads, param, s_seed=7, elist=None)
     return s_reads
 
 
+def subsample_from_resident(chunk, cum_n_seq, s_reads, param, s_seed=7, elist=None):
+    """subsample_from_chunk on a chunkpass.ReadChunk that lives on the device: the same slots from chunk.n, cum_n_seq and the same
+    uniforms, `elist` applied to chunk.names; only the reads that end up in a slot are fetched (chunk.records(idx))."""
+    names = chunk.names
+    take = np.array([i for i in range(chunk.n) if not (elist and names[i] in elist)], dtype=np.int64)
+    u = np.random.RandomState(s_seed).uniform(size=chunk.n + 1)[:take.shape[0]]
+    if param < 1.:
+        return s_reads + chunk.records(take[np.flatnonzero(u < param)])
+    size = int(param)
+    if not s_reads:
+        s_reads = [0] * size
+    nth = cum_n_seq + 1 + np.arange(take.shape[0], dtype=np.int64)
+    slot = np.where(nth - 1 < size, nth - 1, (u * nth).astype(np.int64))
+    hit = np.flatnonzero(slot < size)
+    _, first_from_back = np.unique(slot[hit][::-1], return_index=True)
+    win = hit[::-1][first_from_back]
+    for i, r in zip(win.tolist(), chunk.records(take[win])):
+        s_reads[int(slot[i])] = r
+    return s_reads
+
+
 def replace_masked(s_reads, exclude_seqs: Sequence[str], chunks: Iterable, logger=None):
     """longQC.py:369-406.  Reads of the subsample that sit on the highly-masked list are swapped for a second reservoir draw
     over the input -- one slot per masked read, skipping every read that was already picked or is masked itself.  The draw stops
     at the first chunk after which every slot is taken; if the input runs out first, the masked reads are dropped instead.
-    `chunks` yields (reads, n_seqs, n_bases)."""
+    `chunks` yields (reads, n_seqs, n_bases); reads: a list of records, or a chunkpass.ReadChunk on the device (a FileChunks)."""
     picked = [r for r in s_reads if r != 0]
     masked = set(exclude_seqs)
     where = [i for i, r in enumerate(picked) if r[0] in masked]
@@ -124,7 +145,7 @@ def replace_masked(s_reads, exclude_seqs: Sequence[str], chunks: Iterable, logge
     spare = [0] * len(where)
     seen = 0
     for reads, n_seqs, _n_bases in chunks:
-        subsample_from_chunk(reads, seen, spare, len(where), elist=avoid)
+        (subsample_from_resident if hasattr(reads, "records") else subsample_from_chunk)(reads, seen, spare, len(where), elist=avoid)
         seen += n_seqs
         if all(spare):
             break

@@ -51,7 +51,7 @@ def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional
     chunk: a chunkpass.ReadChunk that holds these reads on the device already -- seqs and quals are not looked at, nothing is
     gathered or uploaded."""
     if chunk is not None:
-        return _rows(names, chunk.n, chunk.off, chunk.qual_array(), *chunk.sdust(w, t))
+        return _rows(names, chunk.n, chunk.off, chunk.qual_first(), *chunk.sdust(w, t))
     lib = _lib(lib)
     n = len(seqs)
     off = np.zeros(n + 1, dtype=np.uint64)
@@ -76,10 +76,11 @@ def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional
 
 
 def _rows(names, n, off, qflat, masked, psum, qv) -> List[str]:
+    """qflat: the qualities on the host (None: none), or True: every read with bases has qualities (a chunk read from a file)"""
     rows = []
     for i in range(n):
         ln = int(off[i + 1] - off[i])
-        has_q = qflat is not None and ln > 0 and qflat[int(off[i])] != 0
+        has_q = ln > 0 and (qflat is True or (qflat is not None and qflat[int(off[i])] != 0))
         frac = _c_div(float(masked[i]), ln)
         mq = -10 * _c_log10(_c_div(float(psum[i]) if has_q else 0.0, ln if has_q else 0))
         rows.append("%s\t%d\t%d\t%s\t%s\t%d" % (names[i], int(masked[i]), ln, _c_fmt3(frac), _c_fmt3(mq), int(qv[i])))

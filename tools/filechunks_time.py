@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""File to finished chunk loop, on configs[2]-shaped synthetic reads (longqc_amd/synth.py: PacBio Sequel CLR ~10 kb) written as a
+one-line FASTQ: (a) chunkpass.SampleQCPass.run_file(path) -- the file read, parsed and gathered by the library (lqreader_*,
+k_chunk_gather) -- against the add_chunk(reads) loop fed by a pure-Python reader (the file's lines in strides of four: nothing faster
+exists in Python for a one-line FASTQ), the reader's time reported apart; --reps alternated repetitions, medians and the spread
+(min .. max).  Both loops cut the chunks at the same borders and must leave the same sdust table and subsample.
+(b) --only gather: FileChunks alone, --reps times over the file, for a `rocprofv3 --kernel-trace --stats` run around this script
+(k_chunk_gather's time comes from its statistics), and a device-to-device copy of the bytes the two launches move (torch, same
+process, wall time of copy + synchronize; under rocprofv3 its kernel is in the same statistics).  One JSON line (also written to $OUT/filechunks_time.json when OUT is set).
+Usage: python tools/filechunks_time.py [--reads 500000] [--chunk-mb 512] [--nsample 5000] [--reps 3] [--workers 16] [--only loop|gather]"""
+import argparse
+import dataclasses
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from longqc_amd import chunkpass, sampleqc, synth  # noqa: E402
+
+PRESET = "pb-sequel"
+ADP5, ADP3 = sampleqc.PRESET_ADAPTERS[PRESET]
+
+
+def python_chunks(path, cs):
+    """lq_utils.parse_fastx_chunk for a one-line FASTQ without pysam: -> the chunks as lists of [name, seq, qual]"""
+    ov = sys.getsizeof("")
+    with open(path) as f:
+        lines = f.read().split("\n")
+    out, cur, size = [], [], 0
+    for i in range(0, len(lines) - 3, 4):
+        name, seq, qual = lines[i][1:].split(None, 1)[0], lines[i + 1].upper(), lines[i + 3]
+        cur.append([name, seq, qual])
+        size += 3 * ov + len(name) + len(seq) + len(qual)
+        if size >= cs:
+            out.append(cur)
+            size, cur = 0, []
+    out.append(cur)
+    return out
+
+
+def new_loop(path, cs, nsample, wdir):
+    t0 = time.time()
+    sp = chunkpass.SampleQCPass(wdir, PRESET, adp5=ADP5, adp3=ADP3, nsample=nsample, suffix="new")
+    sp.run_file(path, chunk_size=cs)
+    sp.mask.close_pool()
+    t1 = time.time()
+    out = (open(sp.mask.get_outfile_path()).read(), sp.s_reads, sp.chunk_n)
+    sp.close()
+    return {"wall_s": t1 - t0}, out
+
+
+def old_loop(path, cs, nsample, wdir):
+    t0 = time.time()
+    chunks = python_chunks(path, cs)
+    t1 = time.time()
+    sp = chunkpass.SampleQCPass(wdir, PRESET, adp5=ADP5, adp3=ADP3, nsample=nsample, suffix="old")
+    for c in chunks:
+        sp.add_chunk(c)
+    sp.mask.close_pool()
+    t2 = time.time()
+    out = (open(sp.mask.get_outfile_path()).read(), sp.s_reads, sp.chunk_n)
+    sp.close()
+    return {"reader_s": t1 - t0, "loop_s": t2 - t1, "wall_s": t2 - t0}, out
+
+
+def summary(runs):
+    return {k: {"median": round(statistics.median(r[k] for r in runs), 3), "min": round(min(r[k] for r in runs), 3),
+                "max": round(max(r[k] for r in runs), 3)} for k in runs[0]}
+
+
+def gather_only(path, cs, reps, n_bases):
+    import torch
+    ts = []
+    for _ in range(reps + 1):
+        t = time.perf_counter()
+        n = sum(ch.n for ch, _, _ in chunkpass.FileChunks(path, chunk_size=cs))
+        ts.append(time.perf_counter() - t)
+    a = torch.empty(2 * n_bases, dtype=torch.uint8, device="cuda")     # the two launches read and write n_bases each: a copy of 2 n_bases moves as much
+    b = torch.empty_like(a)
+    b.copy_(a)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(max(reps, 5)):
+        t = time.perf_counter()
+        b.copy_(a)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t) * 1e3)
+    med = statistics.median(ms)
+    return {"reads": n, "file_to_chunks_s": [round(x, 3) for x in ts[1:]], "file_to_chunks_first_s": round(ts[0], 3), "bytes_moved": 4 * n_bases,
+            "copy_ms_median": round(med, 3), "copy_ms_min": round(min(ms), 3), "copy_gb_per_s": round(4 * n_bases / med / 1e6, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=500000)
+    ap.add_argument("--chunk-mb", type=float, default=512)
+    ap.add_argument("--nsample", type=int, default=5000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--only", choices=("loop", "gather"), default=None)
+    a = ap.parse_args()
+    cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
+    cs = int(a.chunk_mb * 1024 ** 2)
+    t0 = time.time()
+    F = synth.make_reads_flat(cfg, synth.make_genome(cfg), workers=a.workers)
+    flat, off, n_bases = F.flat.tobytes(), F.off, int(F.n_bases)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "all.fq")
+        with open(path, "wb") as f:
+            for i in range(len(F)):
+                s = flat[int(off[i]):int(off[i + 1])]
+                f.write(b"@r%07d\n%s\n+\n%s\n" % (i, s, b"5" * len(s)))
+        res = {"metric": "seconds from the FASTQ file to the finished chunk loop", "unit": "s", "n_reads": len(F), "n_bases": n_bases,
+               "file_bytes": os.path.getsize(path), "chunk_size": cs, "nsample": a.nsample, "setup_s": round(time.time() - t0, 1)}
+        del F, flat
+        sum(ch.n for ch, _, _ in chunkpass.FileChunks(path, chunk_size=cs))       # device start-up, the file in the page cache
+        if a.only != "gather":
+            news, olds, same = [], [], True
+            for _ in range(a.reps):                                 # alternated
+                r_new, o_new = new_loop(path, cs, a.nsample, d)
+                r_old, o_old = old_loop(path, cs, a.nsample, d)
+                news.append(r_new); olds.append(r_old)
+                same = same and o_new == o_old
+            res.update(run_file=summary(news), python_reader_and_add_chunk=summary(olds), same_results=same, reps=a.reps, chunks=o_new[2])
+            res["value"] = res["run_file"]["wall_s"]["median"]
+        if a.only != "loop":
+            res["gather"] = gather_only(path, cs, a.reps, n_bases)
+    print(json.dumps(res))
+    if os.environ.get("OUT"):
+        os.makedirs(os.environ["OUT"], exist_ok=True)
+        with open(os.path.join(os.environ["OUT"], "filechunks_time.json"), "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()
