@@ -410,6 +410,15 @@ int  lqreader_next(lqreader *r, lqchunk *c, uint32_t *n, uint64_t *n_seqs_cum, u
 int  lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens);
 void lqreader_close(lqreader *r);
 const char *lqreader_last_error(const lqreader *r);
+/* An unaligned BAM file (a BGZF file whose inflated bytes begin with "BAM\1"; lq_utils.parse_bam_chunk) is read through the same
+ * calls: lqreader_open recognises it, n_threads threads inflate its blocks, every record is a read whatever its flag, the name is
+ * read_name, the sequence the decoded nibbles ("=ACMGRSVTWYHKDBN"; is_upper changes nothing).  lqreader_format: 0 FASTA/FASTQ, 1 BAM.
+ * The qualities are '!' for every base, as open_seq_chunk's is_sequel=True gives them; lqreader_bam_qualities(r, 1) -- before the first
+ * lqreader_next, LQCOV_E_STATE afterwards -- makes them chr(q + 33) of the file's (a record without qualities, first byte 0xff: '!').
+ * On a FASTA/FASTQ reader the call changes nothing.  Errors: LQCOV_E_IO for a block cut short, a CRC32 or ISIZE mismatch, a record
+ * whose block_size is too small for its fields, a name without its NUL, a file that ends inside a record. */
+int  lqreader_format(const lqreader *r);
+int  lqreader_bam_qualities(lqreader *r, int from_file);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 #ifdef __cplusplus

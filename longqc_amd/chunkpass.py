@@ -1,7 +1,7 @@
 """One upload per chunk: the chunk loop of `longQC.py sampleqc` (longQC.py:299-360) and the coverage call (:438-445) on the same
 device bytes, over the lqchunk_* / lqstore_* calls of include/lqcov.h.
 
-FileChunks is the loop's source, lq_utils.open_seq_chunk for a plain or gzip FASTA/FASTQ file (lqreader_*): it yields
+FileChunks is the loop's source, lq_utils.open_seq_chunk for a plain or gzip FASTA/FASTQ file or an unaligned BAM (lqreader_*): it yields
 (chunk, n_seqs, n_bases) with `chunk` a ReadChunk that the library filled on the device straight from the file -- no read is a Python
 object, the bases are never on the host.  SampleQCPass.run_file(path) is the whole loop on such chunks.
 
@@ -45,6 +45,8 @@ def _lib(lib=None):
             "lqreader_names": (C.c_int, [H, P, P, P]),
             "lqreader_close": (None, [H]),
             "lqreader_last_error": (C.c_char_p, [H]),
+            "lqreader_format": (C.c_int, [H]),
+            "lqreader_bam_qualities": (C.c_int, [H, C.c_int]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -196,12 +198,17 @@ class FileChunks:
     and n_bases cumulative over the file, and after the last record one more chunk, empty if the last record ended a chunk.  The chunk
     is the same object every time and valid until the next iteration: its handle's buffers are used again.  Every iteration starts
     the file anew.  str_overhead: sys.getsizeof("") of the interpreter whose chunk borders are wanted (49 or 41, by the CPython
-    version; default: this interpreter's)."""
+    version; default: this interpreter's).
+    A BAM file (parse_bam_chunk: every record a read, the name read_name, the sequence the decoded nibbles) is recognised by its
+    first bytes; n_threads (default 16, at most 16) threads inflate its blocks.  is_sequel=True, what open_seq_chunk passes: every
+    quality string is '!' * len; False: chr(q + 33) of the file's qualities.  `format` (0 FASTA/FASTQ, 1 BAM) is set when iteration
+    starts."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
-                 lib=None, n_threads: int = 0):
+                 lib=None, n_threads: int = 0, is_sequel: bool = True):
         self.lib = _lib(lib)
         self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
+        self.is_sequel, self.format = is_sequel, None
         self.chunk_size = max(0, int(math.ceil(chunk_size)))        # size >= chunk_size for an integer size
         self.str_overhead = sys.getsizeof("") if str_overhead is None else int(str_overhead)
 
@@ -212,6 +219,11 @@ class FileChunks:
             raise api.LqcovError(-2, lib.lqreader_last_error(None).decode() or "lqreader_open failed")
         chunk = None
         try:
+            self.format = lib.lqreader_format(r)
+            if not self.is_sequel:
+                rc = lib.lqreader_bam_qualities(r, 1)
+                if rc != 0:
+                    raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
             chunk = ReadChunk(None, device=self.device, lib=lib)
             n, n_seqs, n_bases, last = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int()
             while not last.value:
@@ -312,11 +324,13 @@ class SampleQCPass:
         self.n_bases += int(chunk.lens.sum())
         return result
 
-    def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim: bool = False, is_upper: bool = True, str_overhead: Optional[int] = None):
-        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file: FileChunks + add_resident.  -> the per-chunk
+    def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim: bool = False, is_upper: bool = True, str_overhead: Optional[int] = None,
+                 is_sequel: bool = True):
+        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (no FASTQ is written first, as
+        longQC.py:302-303 does; is_sequel: FileChunks'): FileChunks + add_resident.  -> the per-chunk
         adapter results; with trim=True `trimmed_chunks` holds every chunk's trimmed records (longQC.py:330-338 writes them out)"""
         results, self.trimmed_chunks = [], []
-        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib):
+        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel):
             results.append(self.add_resident(chunk, trim=trim))
             if trim:
                 self.trimmed_chunks.append(self.trimmed)

@@ -8,6 +8,7 @@
 #include "chunk.hpp"
 #include "kernels_chunk.hpp"
 #include "kernels_gather.hpp"
+#include "kernels_bam.hpp"
 #include <algorithm>
 #include <memory>
 
@@ -45,7 +46,8 @@ void lq_chunk_ready(lqchunk &c)
 	c.resident = true;
 }
 
-static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &segs, u8 *dst, bool upper)
+// kind: 0 bytes (k_chunk_gather), 1 a BAM file's packed sequences (k_bam_gather), 2 its quality bytes (k_bam_qual)
+static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &segs, u8 *dst, bool upper, int kind)
 {
 	const u64 total = c.total;
 	if (!total) return;
@@ -65,12 +67,14 @@ static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &seg
 	LQ_HIP_CHECK(hipMemcpyAsync(c.gseg.p, segs.data(), (n_segs + 1) * sizeof(GatherSeg), hipMemcpyHostToDevice, c.stream));
 	LQ_HIP_CHECK(hipMemcpyAsync(c.gtile.p, tile_seg.data(), (n_tiles + 1) * 4, hipMemcpyHostToDevice, c.stream));
 	const u32 grid = (u32)std::min<u64>(n_tiles, LQ_GATHER_MAX_BLOCKS);
-	LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
+	if (kind == 1) LQ_LAUNCH(k_bam_gather, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst);
+	else if (kind == 2) LQ_LAUNCH(k_bam_qual, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst);
+	else LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
 	LQ_HIP_CHECK(hipGetLastError());
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (tile_seg dies here, and the two device lists serve the next launch)
 }
 
-void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper)
+void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper, int bam)
 {
 	lq_cabi::select_device(c.device);
 	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
@@ -83,8 +87,8 @@ void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std
 	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + 16); c.d_off.ensure(((size_t)n + 1) * 8);
 	LQ_HIP_CHECK(hipMemsetAsync(c.seq.as<u8>() + words, 0, (size_t)(alloc - words), c.stream));
 	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
-	gather_launch(c, raw, sseg, c.seq.as<u8>(), upper);
-	gather_launch(c, raw, qseg, c.qual.as<u8>(), false);
+	gather_launch(c, raw, sseg, c.seq.as<u8>(), upper, bam ? 1 : 0);
+	gather_launch(c, raw, qseg, c.qual.as<u8>(), false, bam == 2 ? 2 : 0);
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
 	c.resident = true;
 }

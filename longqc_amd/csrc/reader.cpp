@@ -10,8 +10,16 @@
 // so far and not at the end of the file, so it parses one record at a time and gives up (to be called again with more bytes) wherever
 // kseq would have read on.  The chunk rule is parse_fastx_chunk's: size += getsizeof(name) + getsizeof(seq) + getsizeof(qual), a
 // chunk ends with the record that makes size >= chunk_size; for an ASCII str getsizeof is str_overhead + len.
+//
+// A BAM file (file_code 0 of open_seq_chunk, parse_bam_chunk, lq_utils.py:238-261) goes through the same calls.  Its BGZF blocks are
+// inflated into the piece by a pool of threads (bgzf.hpp); the host walks the records there and reads of each one the 36 fixed bytes
+// and the name -- no base, no quality, no tag -- and hands k_bam_gather (kernels_bam.hpp) one descriptor per read for the packed
+// sequence.  Every record is a read, whatever its flag; the qualities are '!' (open_seq_chunk passes is_sequel=True), or with
+// lqreader_bam_qualities(r, 1) the file's, as chr(q + 33).  The chunk rule is the same sum.  The format is the SAM/BAM specification's
+// (4.1 BGZF, 4.2 the records); no file here was read or written by htslib.
 #include "chunk.hpp"
 #include "fastx_mem.hpp"
+#include "bgzf.hpp"
 #include <zlib.h>
 #include <cstdlib>
 #include <memory>
@@ -41,6 +49,11 @@ struct lqreader {
 	bool eof = false;                                         // nothing more to read
 	bool over = false;                                        // no more records: the end of the file, or a truncated quality string (kseq: -2)
 	bool done = false;                                        // the last chunk has been handed out
+	// BAM
+	int format = 0;                                           // 0 FASTA/FASTQ, 1 BAM
+	bool bam_qual = false, started = false;                   // the qualities come from the file; lqreader_next has been called
+	BgzfInflater bgzf;
+	int hdr_state = 0; u64 hdr_skip = 0; u32 hdr_refs = 0;    // the BAM header: 0 magic and l_text, 1 the text, 2 n_ref, 3 l_name, 4 name and l_ref, 5 records
 	// the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet
 	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
 	int last_char = 0;                                        // kseq's: the header character at pos - 1 has been consumed
@@ -64,6 +77,11 @@ struct lqreader {
 		if (fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
 		u8 magic[2] = {0, 0};
 		const bool is_gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+		if (is_gz && is_bam()) {
+			format = 1;
+			bgzf = BgzfInflater(); bgzf.fd = fd; bgzf.n_threads = n_threads;
+			return;
+		}
 		if (is_gz) {
 			gz = gzdopen(fd, "r");
 			if (!gz) throw std::runtime_error("failed to open file '" + path + "'");
@@ -71,6 +89,24 @@ struct lqreader {
 			gzbuffer(gz, 1 << 20);
 		}
 	}
+
+	// a BGZF file whose first four inflated bytes are "BAM\1"
+	bool is_bam()
+	{
+		try {
+			BgzfInflater probe; probe.fd = fd;
+			std::vector<u8> head(BgzfInflater::MAX_BLOCK + 4);
+			u64 have = 0, need = 0;
+			while (have < 4) {
+				const u64 got = probe.fill(head.data() + have, BgzfInflater::MAX_BLOCK + 4 - have, &need, 1);
+				if (!got) return false;
+				have += got;
+			}
+			return memcmp(head.data(), "BAM\1", 4) == 0;
+		} catch (const std::exception &) { return false; }          // (not BGZF, or broken: gzread's to read or to refuse)
+	}
+
+	[[noreturn]] void bam_fail(const std::string &what) { throw std::runtime_error("failed to open file '" + path + "': " + what); }
 
 	void set_piece(u64 bytes)
 	{
@@ -84,6 +120,17 @@ struct lqreader {
 	// more bytes behind buf[fill); false: the file has ended
 	bool read_more()
 	{
+		if (format == 1) {
+			while (!eof) {
+				u64 need = 0, got = 0;
+				try { got = bgzf.fill(buf + fill, cap - fill, &need); }
+				catch (const std::runtime_error &e) { bam_fail(e.what()); }
+				if (got) { fill += got; return true; }
+				if (bgzf.ended) { eof = true; break; }
+				set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
+			}
+			return false;
+		}
 		while (!eof && fill < cap) {
 			const u64 want = std::min<u64>(cap - fill, 1u << 30);
 			i64 got;
@@ -171,6 +218,73 @@ struct lqreader {
 		return REC;
 	}
 
+	static u32 le32(const u8 *p) { return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
+
+	// the BAM header (magic, l_text, text, n_ref, per reference l_name, name, l_ref) is skipped as it comes: it may be longer than
+	// the piece.  true: the records begin at pos
+	bool bam_header()
+	{
+		for (;;) {
+			const u64 have = fill - pos;
+			switch (hdr_state) {
+			case 0: if (have < 8) return false; hdr_skip = le32(buf + pos + 4); pos += 8; hdr_state = 1; break;
+			case 1: case 4: {
+				const u64 m = std::min(have, hdr_skip);
+				pos += m; hdr_skip -= m;
+				if (hdr_skip) return false;
+				if (hdr_state == 4) --hdr_refs;
+				hdr_state = hdr_state == 1 ? 2 : hdr_refs ? 3 : 5;
+				break;
+			}
+			case 2: if (have < 4) return false; hdr_refs = le32(buf + pos); pos += 4; hdr_state = hdr_refs ? 3 : 5; break;
+			case 3: if (have < 4) return false; hdr_skip = (u64)le32(buf + pos) + 4; pos += 4; hdr_state = 4; break;
+			default: return true;
+			}
+		}
+	}
+
+	// one BAM record at buf[pos ..) into the chunk's descriptors.  NEED_MORE: the record is not whole in the piece yet
+	int parse_bam_one()
+	{
+		if (hdr_state != 5) {
+			const bool in = bam_header();
+			up_from = pos;                                        // (no descriptor points into the header: it is not uploaded)
+			if (!in) { if (eof) bam_fail("the file ends inside the BAM header"); return NEED_MORE; }
+		}
+		const u64 have = fill - pos;
+		const std::string where = "BAM record " + std::to_string(n_seqs + 1) + ": ";
+		if (have == 0 && eof) return END;
+		if (have < 36) { if (eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
+		const u8 *p = buf + pos;
+		const u64 block_size = le32(p), l_name = p[12], n_cigar = (u64)p[16] | (u64)p[17] << 8, l_seq = le32(p + 20);
+		if (l_seq > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases (bseq.c:80)");
+		const u64 fields = 32 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+		if (block_size > 0x7fffffffULL || block_size < fields)
+			bam_fail(where + "block_size " + std::to_string((i32)block_size) + " is too small for its fields (" + std::to_string(fields) + " bytes)");
+		if (l_name == 0) bam_fail(where + "l_read_name is 0");
+		if (have < 4 + block_size) { if (eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
+		if (p[36 + l_name - 1] != 0) bam_fail(where + "the read name has no NUL at its end");
+		if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
+		const u8 *nm = p + 36;
+		const u64 name_len = strlen((const char*)nm);
+		for (u64 i = 0; i < name_len; ++i) if (nm[i] >= 0x80)
+			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
+		names.insert(names.end(), nm, nm + name_len + 1);
+		name_off.push_back(names.size());
+		// (where a byte of the piece lies in the chunk's raw bytes: add_record)
+		const u64 seq_at = raw_used + (pos + 36 + l_name + 4 * n_cigar - up_from), d = off.back();
+		if (l_seq) {
+			sseg.push_back({seq_at, d});
+			qseg.push_back({bam_qual ? seq_at + (l_seq + 1) / 2 : LQ_GATHER_FILL, d});
+		}
+		off.push_back(d + l_seq);
+		lens.push_back((u32)l_seq);
+		++n_seqs; n_bases += l_seq;
+		rec.name_len = name_len; rec.seq_len = l_seq;
+		pos += 4 + block_size;
+		return REC;
+	}
+
 	// device room for `more` raw bytes behind raw_used, what is there kept
 	void raw_reserve(hipStream_t stream, u64 more)
 	{
@@ -232,6 +346,7 @@ struct lqreader {
 	void next(lqchunk &c, u32 *n_out, u64 *n_seqs_cum, u64 *n_bases_cum, int *last)
 	{
 		if (done) throw std::logic_error("the reader has handed out its last chunk");
+		started = true;
 		if (c.device != device) throw std::invalid_argument("the chunk lives on another device than the reader");
 		lq_cabi::select_device(device);
 		if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
@@ -240,17 +355,19 @@ struct lqreader {
 		if (!buf) { set_piece(piece_bytes()); read_more(); }
 		u64 size = 0; bool ended = false;
 		while (!over) {
-			const int st = parse_one();
+			const int st = format == 1 ? parse_bam_one() : parse_one();
 			if (st == NEED_MORE) { refill(c.stream); continue; }
 			if (st == END) { over = true; break; }
-			if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
-			add_record();
+			if (format == 0) {
+				if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
+				add_record();
+			}
 			size += 3 * overhead + rec.name_len + 2 * rec.seq_len;
 			if (size >= chunk_size) { ended = true; break; }
 		}
 		upload(c.stream);
 		done = !ended;
-		lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper);
+		lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
 		const u32 n = c.n;
 		*n_out = n; *n_seqs_cum = n_seqs; *n_bases_cum = n_bases; *last = done ? 1 : 0;
 	}
@@ -298,6 +415,16 @@ int lqreader_next(lqreader *r, lqchunk *c, uint32_t *n, uint64_t *n_seqs_cum, ui
 	});
 	if (rc) { r->err = buf; r->done = true; }                 // (a reader that failed hands out nothing more)
 	return rc;
+}
+
+int lqreader_format(const lqreader *r) { return r ? r->format : LQCOV_E_ARG; }
+
+int lqreader_bam_qualities(lqreader *r, int from_file)
+{
+	if (!r) return LQCOV_E_ARG;
+	if (r->started) { r->err = "lqreader_bam_qualities after the first lqreader_next"; return LQCOV_E_STATE; }
+	r->bam_qual = from_file != 0;
+	return 0;
 }
 
 int lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens)
