@@ -419,6 +419,29 @@ const char *lqreader_last_error(const lqreader *r);
  * whose block_size is too small for its fields, a name without its NUL, a file that ends inside a record. */
 int  lqreader_format(const lqreader *r);
 int  lqreader_bam_qualities(lqreader *r, int from_file);
+/* The second way to inflate BGZF blocks, opt-in: lqreader_inflate(r, LQREADER_INFLATE_DEVICE) -- before the first lqreader_next,
+ * LQCOV_E_STATE afterwards; the default is LQREADER_INFLATE_HOST, or what the environment variable LQREADER_INFLATE ("device") says
+ * when the reader is opened -- has k_bgzf_inflate inflate them on the device: the compressed bytes go up, the inflated bytes come back
+ * for the record walk and the CRC32 check (the pool's threads) and stay in the chunk's raw device buffer for the gather kernels, so
+ * the piece is not uploaded.  The chunks, the errors (LQCOV_E_IO: "corrupt deflate stream", "ISIZE does not match the inflated
+ * bytes", "CRC32 mismatch", the lowest failing file offset) are those of the host mode.  In device mode a BGZF file that is not BAM
+ * (bgzip FASTA/FASTQ) is inflated the same way instead of by gzread; a file that is not BGZF ignores the mode.
+ * lqinflate_blocks is the array-level call (tests; callers that hold BGZF blocks of their own): block i is the raw deflate stream
+ * comp[in_off[i] .. + in_len[i]) (in_len < 2^24) and inflates to out_host[out_off[i] .. + isize[i]), isize[i] <= 65536.  out_host[0 ..
+ * max(out_off + isize)) goes to the device before the launch and comes back after it: bytes outside the blocks' ranges return as they
+ * were given.  status[i]: 0 the stream ended after exactly isize bytes; LQINFLATE_INVALID not a deflate stream; LQINFLATE_INPUT the input
+ * ended inside the stream; LQINFLATE_LONG / LQINFLATE_SHORT a valid stream of more / fewer bytes (what a failing block leaves in its
+ * range is unspecified, nothing outside it is written).  A bad block is not an error of the call.  LQCOV_E_ARG: null buffers, a range
+ * outside comp, isize above 65536 (the message: lqreader_last_error(NULL)). */
+#define LQREADER_INFLATE_HOST   0
+#define LQREADER_INFLATE_DEVICE 1
+#define LQINFLATE_INVALID 1
+#define LQINFLATE_INPUT   2
+#define LQINFLATE_LONG    3
+#define LQINFLATE_SHORT   4
+int  lqreader_inflate(lqreader *r, int mode);
+int  lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_t n, const uint64_t *in_off, const uint32_t *in_len,
+                      const uint64_t *out_off, const uint32_t *isize, uint8_t *out_host, uint32_t *status);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 #ifdef __cplusplus

@@ -12,6 +12,7 @@ subsample, GC fractions, then the chunk is 2-bit packed on the device and kept t
 against the kept chunks without touching the input again.  No CPU fallback: without liblqcov.so or a HIP device the calls raise."""
 import ctypes as C
 import math
+import os
 import sys
 from typing import Optional
 
@@ -47,6 +48,8 @@ def _lib(lib=None):
             "lqreader_last_error": (C.c_char_p, [H]),
             "lqreader_format": (C.c_int, [H]),
             "lqreader_bam_qualities": (C.c_int, [H, C.c_int]),
+            "lqreader_inflate": (C.c_int, [H, C.c_int]),
+            "lqinflate_blocks": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P, P, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -62,6 +65,43 @@ def _join(items, n):
     if len(flat) != int(lens.sum()):
         raise ValueError("reads must be all str or all bytes")
     return flat, lens
+
+
+INFLATE_MODES = {"host": 0, "device": 1}
+INFLATE_OK, INFLATE_INVALID, INFLATE_INPUT, INFLATE_LONG, INFLATE_SHORT = range(5)      # lqinflate_blocks' status words
+
+
+def inflate_mode(inflate):
+    """"host" | "device" | None (the environment variable LQREADER_INFLATE, "host" without it) -> the mode's name"""
+    mode = os.environ.get("LQREADER_INFLATE", "host") if inflate is None else inflate
+    if mode not in INFLATE_MODES:
+        raise ValueError("inflate must be 'host' or 'device', not %r" % (mode,))
+    return mode
+
+
+def inflate_blocks(comp, in_off, in_len, out_off, isize, out=None, device: int = 0, lib=None):
+    """k_bgzf_inflate over arrays (lqinflate_blocks): block i is the raw deflate stream comp[in_off[i] : in_off[i] + in_len[i]] and
+    inflates to out[out_off[i] : out_off[i] + isize[i]] (isize <= 65536).  out: a uint8 array to write into (what lies outside the
+    blocks' ranges stays), default zeros up to the last range's end.  -> (out, status uint32[n]: INFLATE_OK, INFLATE_INVALID and
+    INFLATE_INPUT (not a whole deflate stream), INFLATE_LONG and INFLATE_SHORT (a stream of more / fewer bytes than isize))"""
+    lib = _lib(lib)
+    comp = np.frombuffer(bytes(comp), dtype=np.uint8) if not isinstance(comp, np.ndarray) else np.ascontiguousarray(comp, dtype=np.uint8)
+    in_off, out_off = np.ascontiguousarray(in_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+    in_len, isize = np.ascontiguousarray(in_len, dtype=np.uint32), np.ascontiguousarray(isize, dtype=np.uint32)
+    n = in_off.shape[0]
+    if not (in_len.shape[0] == out_off.shape[0] == isize.shape[0] == n):
+        raise ValueError("in_off, in_len, out_off and isize differ in length")
+    end = int((out_off + isize.astype(np.uint64)).max()) if n else 0
+    if out is None:
+        out = np.zeros(end, np.uint8)
+    if out.dtype != np.uint8 or not out.flags["C_CONTIGUOUS"] or out.shape[0] < end:
+        raise ValueError("out must be a contiguous uint8 array that holds every block's range")
+    status = np.zeros(max(n, 1), np.uint32)
+    rc = lib.lqinflate_blocks(device, comp.ctypes.data if comp.shape[0] else None, comp.shape[0], n, in_off.ctypes.data, in_len.ctypes.data,
+                              out_off.ctypes.data, isize.ctypes.data, out.ctypes.data if out.shape[0] else None, status.ctypes.data)
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return out, status[:n]
 
 
 class ReadChunk:
@@ -202,11 +242,15 @@ class FileChunks:
     A BAM file (parse_bam_chunk: every record a read, the name read_name, the sequence the decoded nibbles) is recognised by its
     first bytes; n_threads (default 16, at most 16) threads inflate its blocks.  is_sequel=True, what open_seq_chunk passes: every
     quality string is '!' * len; False: chr(q + 33) of the file's qualities.  `format` (0 FASTA/FASTQ, 1 BAM) is set when iteration
-    starts."""
+    starts.
+    inflate="device": the BGZF blocks of a BAM file -- and of a bgzip FASTA/FASTQ, which otherwise is gzread's -- are inflated on the
+    device (k_bgzf_inflate); "host": the thread pool and gzread; None: what the environment variable LQREADER_INFLATE says, "host"
+    without it.  The chunks are the same."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
-                 lib=None, n_threads: int = 0, is_sequel: bool = True):
+                 lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None):
         self.lib = _lib(lib)
+        self.inflate = inflate_mode(inflate)
         self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
         self.is_sequel, self.format = is_sequel, None
         self.chunk_size = max(0, int(math.ceil(chunk_size)))        # size >= chunk_size for an integer size
@@ -220,8 +264,7 @@ class FileChunks:
         chunk = None
         try:
             self.format = lib.lqreader_format(r)
-            if not self.is_sequel:
-                rc = lib.lqreader_bam_qualities(r, 1)
+            for rc in (lib.lqreader_bam_qualities(r, 1) if not self.is_sequel else 0, lib.lqreader_inflate(r, INFLATE_MODES[self.inflate])):
                 if rc != 0:
                     raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
             chunk = ReadChunk(None, device=self.device, lib=lib)
@@ -325,12 +368,13 @@ class SampleQCPass:
         return result
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim: bool = False, is_upper: bool = True, str_overhead: Optional[int] = None,
-                 is_sequel: bool = True):
+                 is_sequel: bool = True, inflate: Optional[str] = None):
         """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (no FASTQ is written first, as
-        longQC.py:302-303 does; is_sequel: FileChunks'): FileChunks + add_resident.  -> the per-chunk
+        longQC.py:302-303 does; is_sequel, inflate: FileChunks'): FileChunks + add_resident.  -> the per-chunk
         adapter results; with trim=True `trimmed_chunks` holds every chunk's trimmed records (longQC.py:330-338 writes them out)"""
         results, self.trimmed_chunks = [], []
-        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel):
+        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
+                                                    inflate=inflate):
             results.append(self.add_resident(chunk, trim=trim))
             if trim:
                 self.trimmed_chunks.append(self.trimmed)

@@ -2,13 +2,18 @@
 // with an extra subfield 'B','C' that holds the member's size minus one (BSIZE) and, as every gzip member, the CRC32 and the size of
 // its inflated bytes (ISIZE) in its last eight bytes.  The members are independent deflate streams, so the sizes alone say where
 // each one's bytes land and a pool of threads inflates them side by side, straight into the caller's buffer.  A unit of its own: it
-// knows nothing of what the bytes are (today reader.cpp's BAM branch; a bgzip-compressed FASTA/FASTQ still goes through gzread).
+// knows nothing of what the bytes are (reader.cpp's BAM branch; a bgzip-compressed FASTA/FASTQ goes through gzread unless the reader
+// is in device mode).  The second way, opt-in: `device` set, the listed blocks are inflated by k_bgzf_inflate (kernels_inflate.hpp) --
+// the owner's hook uploads the compressed bytes, launches and brings the inflated bytes back to dst and one status per block -- and
+// the pool only checks the CRC32 of what came back, which vouches for the kernel and for the copy alike.  The errors are the same
+// three, for the same blocks.
 #pragma once
 #include "lq_common.hpp"
 #include <zlib.h>
 #include <fcntl.h>
 #include <unistd.h>
 #include <atomic>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -23,6 +28,9 @@ struct BgzfInflater {
 	std::vector<u8> win; u64 win_at = 0, win_len = 0; bool win_eof = false;      // compressed bytes win_at .. win_at + win_len of the file
 
 	struct Block { u64 at, in, in_len, isize, out; u32 crc; };        // at: file offset; in: deflate bytes in win; out: offset in the caller's buffer
+	// device mode: inflate `blocks` (their bytes: win) into dst[0 .. out_bytes) -> status[i]: 0 fine, 1 not a deflate stream, other: the
+	// stream does not give isize bytes (LQ_INF_* of kernels_inflate.hpp)
+	std::function<void(const std::vector<Block> &blocks, const u8 *win, u8 *dst, u64 out_bytes, std::vector<u32> &status)> device;
 
 	[[noreturn]] static void fail(u64 at, const char *what)
 	{
@@ -101,17 +109,29 @@ struct BgzfInflater {
 				out += isize; next += size;
 			}
 			if (blocks.empty()) break;
-			inflate_all(blocks, dst);
+			inflate_all(blocks, dst, out);
 		}
 		return out;
 	}
 
-	void inflate_all(const std::vector<Block> &blocks, u8 *dst)
+	void inflate_all(const std::vector<Block> &blocks, u8 *dst, u64 out_bytes)
 	{
+		std::vector<u32> status;
+		if (device) device(blocks, win.data(), dst, out_bytes, status);
 		const u32 nt = (u32)std::min<u64>((u64)std::max(n_threads, 1), blocks.size());
 		std::atomic<u64> turn{0};
 		std::vector<u64> bad_at(nt, LQ_U64MAX); std::vector<const char*> bad(nt, nullptr);
 		auto work = [&](u32 w) {
+			if (device) {                                             // the bytes are there: what the kernel said of them, then the CRC32
+				for (u64 i; (i = turn.fetch_add(1)) < blocks.size();) {
+					const Block &b = blocks[i];
+					const char *what = nullptr;
+					if (status[i]) what = status[i] == 1 ? "corrupt deflate stream" : "ISIZE does not match the inflated bytes";
+					else if ((u32)crc32(crc32(0L, Z_NULL, 0), dst + b.out, (uInt)b.isize) != b.crc) what = "CRC32 mismatch";
+					if (what && b.at < bad_at[w]) { bad_at[w] = b.at; bad[w] = what; }
+				}
+				return;
+			}
 			z_stream z; memset(&z, 0, sizeof(z));
 			if (inflateInit2(&z, -15) != Z_OK) { bad_at[w] = 0; bad[w] = "no memory for zlib"; return; }
 			for (u64 i; (i = turn.fetch_add(1)) < blocks.size();) {

@@ -17,9 +17,17 @@
 // sequence.  Every record is a read, whatever its flag; the qualities are '!' (open_seq_chunk passes is_sequel=True), or with
 // lqreader_bam_qualities(r, 1) the file's, as chr(q + 33).  The chunk rule is the same sum.  The format is the SAM/BAM specification's
 // (4.1 BGZF, 4.2 the records); no file here was read or written by htslib.
+//
+// lqreader_inflate(r, LQREADER_INFLATE_DEVICE): the BGZF blocks are inflated by k_bgzf_inflate (kernels_inflate.hpp) instead.  Only the
+// compressed bytes go up; the kernel writes the inflated bytes into the chunk's raw device buffer where the piece's upload would have
+// put them, and they come back into the piece for the host to parse and to check their CRC32 -- the parsers and the gather kernels
+// are the same, the upload of the piece falls away.  The raw buffer then mirrors the piece from its first byte that is not part of
+// the chunk yet (up_from) to its last (fill), not only what has been parsed.  In that mode a BGZF file that is not BAM (bgzip
+// FASTA/FASTQ) is inflated the same way and parsed by the kseq grammar; gzread is not used for it.
 #include "chunk.hpp"
 #include "fastx_mem.hpp"
 #include "bgzf.hpp"
+#include "kernels_inflate.hpp"
 #include <zlib.h>
 #include <cstdlib>
 #include <memory>
@@ -36,6 +44,24 @@ struct Record {
 };
 
 enum { REC = 0, NEED_MORE = 1, END = 2 };
+
+// k_bgzf_inflate over host arrays: the compressed bytes go up, the kernel writes into d_out (16-byte aligned), the statuses come back
+struct InflateDev {
+	DBuf comp, jobs, status;
+	void run(hipStream_t stream, const u8 *comp_host, u64 comp_len, const std::vector<InflateJob> &j, u8 *d_out, u32 *status_host)
+	{
+		const u32 n = (u32)j.size();
+		if (!n) return;
+		comp.ensure((size_t)(comp_len + 3) / 4 * 4 + LQ_INFLATE_PAD); jobs.ensure((size_t)n * sizeof(InflateJob)); status.ensure((size_t)n * 4);
+		if (comp_len) LQ_HIP_CHECK(hipMemcpyAsync(comp.p, comp_host, (size_t)comp_len, hipMemcpyHostToDevice, stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(jobs.p, j.data(), (size_t)n * sizeof(InflateJob), hipMemcpyHostToDevice, stream));
+		const u32 grid = std::min<u32>(n, LQ_INFLATE_MAX_BLOCKS);
+		LQ_LAUNCH(k_bgzf_inflate, grid, LQ_INFLATE_THREADS, stream, comp.as<u8>(), jobs.as<InflateJob>(), n, d_out, status.as<u32>());
+		LQ_HIP_CHECK(hipGetLastError());
+		LQ_HIP_CHECK(hipMemcpyAsync(status_host, status.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+	}
+};
 } // namespace
 
 struct lqreader {
@@ -53,6 +79,9 @@ struct lqreader {
 	int format = 0;                                           // 0 FASTA/FASTQ, 1 BAM
 	bool bam_qual = false, started = false;                   // the qualities come from the file; lqreader_next has been called
 	BgzfInflater bgzf;
+	int inflate_mode = LQREADER_INFLATE_HOST; bool bgzf_text = false;     // lqreader_inflate's; a BGZF file that is not BAM
+	int bgzf_fd = -1;                                         // device mode on such a file: the descriptor the blocks are read from
+	InflateDev inf; hipStream_t inf_stream = nullptr;
 	int hdr_state = 0; u64 hdr_skip = 0; u32 hdr_refs = 0;    // the BAM header: 0 magic and l_text, 1 the text, 2 n_ref, 3 l_name, 4 name and l_ref, 5 records
 	// the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet
 	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
@@ -68,6 +97,7 @@ struct lqreader {
 	{
 		if (gz) gzclose(gz);
 		if (fd >= 0) ::close(fd);
+		if (bgzf_fd >= 0) ::close(bgzf_fd);
 		if (buf) lqcov_host_free(buf);
 	}
 
@@ -77,7 +107,9 @@ struct lqreader {
 		if (fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
 		u8 magic[2] = {0, 0};
 		const bool is_gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-		if (is_gz && is_bam()) {
+		const int kind = is_gz ? bgzf_kind() : 0;
+		bgzf_text = kind == 1;
+		if (kind == 2) {
 			format = 1;
 			bgzf = BgzfInflater(); bgzf.fd = fd; bgzf.n_threads = n_threads;
 			return;
@@ -90,8 +122,8 @@ struct lqreader {
 		}
 	}
 
-	// a BGZF file whose first four inflated bytes are "BAM\1"
-	bool is_bam()
+	// 2: a BGZF file whose first four inflated bytes are "BAM\1"; 1: another BGZF file (its first blocks inflate); 0: neither
+	int bgzf_kind()
 	{
 		try {
 			BgzfInflater probe; probe.fd = fd;
@@ -99,11 +131,38 @@ struct lqreader {
 			u64 have = 0, need = 0;
 			while (have < 4) {
 				const u64 got = probe.fill(head.data() + have, BgzfInflater::MAX_BLOCK + 4 - have, &need, 1);
-				if (!got) return false;
+				if (!got) return 1;
 				have += got;
 			}
-			return memcmp(head.data(), "BAM\1", 4) == 0;
-		} catch (const std::exception &) { return false; }          // (not BGZF, or broken: gzread's to read or to refuse)
+			return memcmp(head.data(), "BAM\1", 4) == 0 ? 2 : 1;
+		} catch (const std::exception &) { return 0; }              // (not BGZF, or broken: gzread's to read or to refuse)
+	}
+
+	bool use_bgzf() const { return format == 1 || (bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE); }
+	bool on_device() const { return inflate_mode == LQREADER_INFLATE_DEVICE && use_bgzf(); }
+
+	// the first lqreader_next: the mode is final
+	void start()
+	{
+		started = true;
+		if (!on_device()) return;
+		if (format == 0) {                                        // (gz keeps its descriptor; nothing has been read through it)
+			bgzf_fd = ::open(path.c_str(), O_RDONLY);
+			if (bgzf_fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
+			bgzf = BgzfInflater(); bgzf.fd = bgzf_fd; bgzf.n_threads = n_threads;
+		}
+		bgzf.device = [this](const std::vector<BgzfInflater::Block> &blocks, const u8 *win, u8 *dst, u64 out_bytes, std::vector<u32> &status) {
+			// dst is buf + fill: its place in the raw bytes is where upload() would put it
+			const u64 ahead = (u64)(dst - buf) - up_from, lo = blocks.front().in & ~(u64)15, hi = blocks.back().in + blocks.back().in_len;
+			raw_reserve(inf_stream, ahead + out_bytes, ahead);
+			std::vector<InflateJob> jobs(blocks.size());
+			for (size_t i = 0; i < blocks.size(); ++i)
+				jobs[i] = {blocks[i].in - lo, raw_used + ahead + blocks[i].out, (u32)blocks[i].in_len, (u32)blocks[i].isize};
+			status.assign(blocks.size(), 0);
+			inf.run(inf_stream, win + lo, hi - lo, jobs, raw.as<u8>(), status.data());
+			if (out_bytes) LQ_HIP_CHECK(hipMemcpyAsync(dst, raw.as<u8>() + raw_used + ahead, (size_t)out_bytes, hipMemcpyDeviceToHost, inf_stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(inf_stream));
+		};
 	}
 
 	[[noreturn]] void bam_fail(const std::string &what) { throw std::runtime_error("failed to open file '" + path + "': " + what); }
@@ -120,11 +179,14 @@ struct lqreader {
 	// more bytes behind buf[fill); false: the file has ended
 	bool read_more()
 	{
-		if (format == 1) {
+		if (use_bgzf()) {
 			while (!eof) {
 				u64 need = 0, got = 0;
 				try { got = bgzf.fill(buf + fill, cap - fill, &need); }
-				catch (const std::runtime_error &e) { bam_fail(e.what()); }
+				catch (const std::runtime_error &e) {
+					if (strncmp(e.what(), "BGZF block", 10) && strcmp(e.what(), "read error")) throw;      // (the device's, not the file's)
+					bam_fail(e.what());
+				}
 				if (got) { fill += got; return true; }
 				if (bgzf.ended) { eof = true; break; }
 				set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
@@ -248,6 +310,7 @@ struct lqreader {
 	{
 		if (hdr_state != 5) {
 			const bool in = bam_header();
+			if (on_device()) raw_used += pos - up_from;           // (the header is in the raw bytes already)
 			up_from = pos;                                        // (no descriptor points into the header: it is not uploaded)
 			if (!in) { if (eof) bam_fail("the file ends inside the BAM header"); return NEED_MORE; }
 		}
@@ -285,15 +348,15 @@ struct lqreader {
 		return REC;
 	}
 
-	// device room for `more` raw bytes behind raw_used, what is there kept
-	void raw_reserve(hipStream_t stream, u64 more)
+	// device room for `more` raw bytes behind raw_used, what is there -- and `keep` bytes behind raw_used -- kept
+	void raw_reserve(hipStream_t stream, u64 more, u64 keep = 0)
 	{
 		const u64 need = raw_used + more + LQ_GATHER_SRC_PAD;
 		if (need <= raw.cap) return;
 		DBuf nb;
 		nb.ensure((size_t)std::max<u64>(need, 2 * raw_used + LQ_GATHER_SRC_PAD));
-		if (raw_used) {
-			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, raw.p, (size_t)raw_used, hipMemcpyDeviceToDevice, stream));
+		if (raw_used + keep) {
+			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, raw.p, (size_t)(raw_used + keep), hipMemcpyDeviceToDevice, stream));
 			LQ_HIP_CHECK(hipStreamSynchronize(stream));
 		}
 		raw.swap(nb);
@@ -304,7 +367,8 @@ struct lqreader {
 	void upload(hipStream_t stream)
 	{
 		const u64 len = pos - up_from;
-		if (len) {
+		if (on_device()) raw_used += len;                         // (the kernel has put them there)
+		else if (len) {
 			raw_reserve(stream, len);
 			LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used, buf + up_from, (size_t)len, hipMemcpyHostToDevice, stream));
 			LQ_HIP_CHECK(hipStreamSynchronize(stream));           // the piece is free again
@@ -346,13 +410,19 @@ struct lqreader {
 	void next(lqchunk &c, u32 *n_out, u64 *n_seqs_cum, u64 *n_bases_cum, int *last)
 	{
 		if (done) throw std::logic_error("the reader has handed out its last chunk");
-		started = true;
 		if (c.device != device) throw std::invalid_argument("the chunk lives on another device than the reader");
 		lq_cabi::select_device(device);
 		if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
+		inf_stream = c.stream;
+		if (!started) start();
 		c.resident = false; c.packed = false; c.n_chunks = 0;
 		raw_used = 0; sseg.clear(); qseg.clear(); names.clear(); name_off.assign(1, 0); off.assign(1, 0); lens.clear();
 		if (!buf) { set_piece(piece_bytes()); read_more(); }
+		else if (on_device() && fill > up_from) {                 // what the piece still holds belongs to this chunk: the mirror starts anew
+			raw_reserve(c.stream, fill - up_from);
+			LQ_HIP_CHECK(hipMemcpyAsync(raw.p, buf + up_from, (size_t)(fill - up_from), hipMemcpyHostToDevice, c.stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+		}
 		u64 size = 0; bool ended = false;
 		while (!over) {
 			const int st = format == 1 ? parse_bam_one() : parse_one();
@@ -391,6 +461,8 @@ lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int i
 		std::unique_ptr<lqreader> r(new lqreader());
 		r->path = path; r->device = device; r->chunk_size = chunk_size; r->upper = is_upper != 0; r->overhead = str_overhead;
 		r->n_threads = n_threads <= 0 ? 16 : std::min(n_threads, 16);
+		const char *mode = getenv("LQREADER_INFLATE");
+		if (mode && !strcmp(mode, "device")) r->inflate_mode = LQREADER_INFLATE_DEVICE;
 		r->open_file();
 		return r.release();
 	} catch (const std::exception &e) { g_reader_open_error = e.what(); return nullptr; }
@@ -425,6 +497,46 @@ int lqreader_bam_qualities(lqreader *r, int from_file)
 	if (r->started) { r->err = "lqreader_bam_qualities after the first lqreader_next"; return LQCOV_E_STATE; }
 	r->bam_qual = from_file != 0;
 	return 0;
+}
+
+int lqreader_inflate(lqreader *r, int mode)
+{
+	if (!r || (mode != LQREADER_INFLATE_HOST && mode != LQREADER_INFLATE_DEVICE)) return LQCOV_E_ARG;
+	if (r->started) { r->err = "lqreader_inflate after the first lqreader_next"; return LQCOV_E_STATE; }
+	r->inflate_mode = mode;
+	return 0;
+}
+
+int lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_t n, const uint64_t *in_off, const uint32_t *in_len,
+                     const uint64_t *out_off, const uint32_t *isize, uint8_t *out_host, uint32_t *status)
+{
+	char msg[512] = {0};
+	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+		if (!n) return;
+		if (!in_off || !in_len || !out_off || !isize || !status || (comp_len && !comp)) throw std::invalid_argument("null buffers");
+		std::vector<InflateJob> jobs(n);
+		u64 out_len = 0;
+		for (u32 i = 0; i < n; ++i) {
+			if (isize[i] > 65536) throw std::invalid_argument("ISIZE above 65536");
+			if (in_len[i] >= 1u << 24 || in_off[i] > comp_len || in_len[i] > comp_len - in_off[i]) throw std::invalid_argument("a block's bytes lie outside the compressed buffer");
+			if (out_off[i] > ((u64)1 << 40)) throw std::invalid_argument("an output offset above 2^40");
+			jobs[i] = {in_off[i], out_off[i], in_len[i], isize[i]};
+			out_len = std::max(out_len, out_off[i] + isize[i]);
+		}
+		if (out_len && !out_host) throw std::invalid_argument("null buffers");
+		lq_cabi::select_device(device);
+		hipStream_t stream = nullptr;
+		LQ_HIP_CHECK(hipStreamCreate(&stream));
+		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		InflateDev inf; DBuf out;
+		out.ensure((size_t)out_len + 16);
+		if (out_len) LQ_HIP_CHECK(hipMemcpyAsync(out.p, out_host, (size_t)out_len, hipMemcpyHostToDevice, stream));
+		inf.run(stream, comp, comp_len, jobs, out.as<u8>(), status);
+		if (out_len) LQ_HIP_CHECK(hipMemcpyAsync(out_host, out.p, (size_t)out_len, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+	});
+	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
+	return rc;
 }
 
 int lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens)

@@ -1,0 +1,214 @@
+"""The reader in device mode (lqreader_inflate, FileChunks(inflate="device"), SampleQCPass.run_file(inflate="device"): bgzf.hpp,
+reader.cpp, k_bgzf_inflate), under the wave emulator and on the GPU.  What a mode may change is where the blocks are inflated;
+everything a caller sees must be the host mode's:
+  1. BAM: the cases of test_bamchunks.check_records and check_qualities (block payloads 37, 4096 and 65280, levels 0 and 6, empty
+     blocks, no EOF marker, LQREADER_PIECE_BYTES=4096, a header longer than a piece) run with LQREADER_INFLATE=device against the list
+     the test wrote; then host and device mode side by side: records, names, lens, n_seqs, n_bases and flat bytes, both quality modes;
+  2. a bgzip multi-line FASTQ and a bgzip FASTA give the chunks and borders of the gzread path at two chunk sizes;
+  3. run_file(bam, inflate="device") leaves the sdust table, the subsample and the adapter rows of the host mode;
+  4. a flipped CRC byte, a flipped deflate byte and a file cut inside a block give LQCOV_E_IO with the host mode's message and offset;
+  5. lqreader_inflate after the first lqreader_next is LQCOV_E_STATE; a plain .gz FASTQ in device mode reads as before."""
+import ctypes as C
+import gzip
+import struct
+
+import numpy as np
+import pytest
+
+from longqc_amd import api, chunkpass, sampleqc, synth
+from tests import bam_writer as BW
+from tests import test_bamchunks as TB
+from tests import test_filechunks as TF
+
+
+# ---- 1. BAM ----
+def check_bam(lib, tmp_path, monkeypatch):
+    L = chunkpass._lib(lib)
+    monkeypatch.setenv("LQREADER_INFLATE", "device")
+    assert chunkpass.FileChunks("x", lib=lib).inflate == "device"
+    TB.check_records(lib, tmp_path, monkeypatch)
+    TB.check_qualities(lib, tmp_path)
+    monkeypatch.delenv("LQREADER_INFLATE")
+    assert chunkpass.FileChunks("x", lib=lib).inflate == "host"
+    # side by side, with qualities in the file
+    reads, cigars, tags, flags = TB.seeded_reads(6)
+    rng = np.random.default_rng(3)
+    quals = [bytes(rng.integers(0, 94, len(r[1])).astype(np.uint8)) for r in reads]
+    size = sum(3 * 49 + len(r[0]) + 2 * len(r[1]) for r in reads)
+    for bp, lv, piece in ((37, 6, None), (4096, 0, "4096"), (65280, 6, None)):
+        path = str(tmp_path / ("s_%d_%d.bam" % (bp, lv)))
+        BW.write_bam(path, reads, quals, bp, lv, TB.HEADER_TEXT, (), cigars, tags, flags, True, 3 if bp == 4096 else 0)
+        if piece:
+            monkeypatch.setenv("LQREADER_PIECE_BYTES", piece)
+        for sequel in (True, False):
+            for cs in (1 << 40, size // 3 + 1):
+                got = {}
+                for mode in ("host", "device"):
+                    fc = chunkpass.FileChunks(path, chunk_size=cs, lib=lib, is_sequel=sequel, inflate=mode, str_overhead=49)
+                    got[mode] = [(ch.records(), ns, nb, ch.names, ch.lens.tolist(), TB.flat(L, ch)) for ch, ns, nb in fc]
+                    assert fc.format == 1
+                assert got["host"] == got["device"] and len(got["host"]) == (1 if cs == 1 << 40 else 3), (bp, lv, piece, sequel, cs)
+        monkeypatch.delenv("LQREADER_PIECE_BYTES", raising=False)
+
+
+# ---- 2. bgzip FASTA/FASTQ ----
+def check_bgzip_text(lib, tmp_path, monkeypatch):
+    recs = TF.rand_records(31)
+    for name, data, bp in (("ml.fq.gz", TF.fastq_bytes(recs, 60), 1000), ("w.fa.gz", TF.fasta_bytes(recs, 60), 65280), ("crlf.fq.gz", TF.fastq_bytes(recs, 0, b"\r\n"), 37)):
+        path = str(tmp_path / name)
+        open(path, "wb").write(BW.bgzf(data, bp, 6, eof=name != "w.fa.gz"))
+        want = TF.as_reads(TF.kseq_records(data)[0])
+        size = sum(3 * 49 + len(r[0]) + 2 * len(r[1]) for r in want)
+        for piece in (None, "4096"):
+            if piece:
+                monkeypatch.setenv("LQREADER_PIECE_BYTES", piece)
+            for cs in (size // 5 + 1, 3000):
+                host = TF.all_chunks(lib, path, chunk_size=cs, str_overhead=49, inflate="host")
+                fc = chunkpass.FileChunks(path, chunk_size=cs, str_overhead=49, lib=lib, inflate="device")
+                dev = [(ch.records(), ns, nb) for ch, ns, nb in fc]
+                assert fc.format == 0 and dev == host and len(host) >= 4, (name, piece, cs)
+                assert [r for c, _, _ in dev for r in c] == want, (name, piece, cs)
+            monkeypatch.delenv("LQREADER_PIECE_BYTES", raising=False)
+
+
+# ---- 3. run_file ----
+def check_run_file(lib, tmp_path):
+    cfg = synth.SynthConfig("bam", n_reads=120, mean_len=2000, depth=6.0, seed=7111, nsample=30)
+    T, _ = synth.make_dataset(cfg)
+    bam = str(tmp_path / "w.bam")
+    BW.write_bam(bam, [(nm.encode(), s.tobytes()) for nm, s in zip(T.names, T.seqs)], None, 65280, 6)
+    adp5, adp3 = sampleqc.PRESET_ADAPTERS["pb-sequel"]
+    cs = sum(3 * 49 + len(nm) + 2 * s.shape[0] for nm, s in zip(T.names, T.seqs)) // 3 + 1
+    out = []
+    for mode in ("host", "device"):
+        p = chunkpass.SampleQCPass(str(tmp_path / mode), "pb-sequel", adp5=adp5, adp3=adp3, nsample=30, inds=200000, gc_draw="device", gc_seed=3,
+                                   suffix="x", lib=lib)
+        np.random.seed(11)
+        res = p.run_file(bam, chunk_size=cs, str_overhead=49, inflate=mode)
+        p.mask.close_pool()
+        out.append((p, res))
+    (a, ra), (b, rb) = out
+    assert len(ra) >= 3 and ra == rb
+    table = open(a.mask.get_outfile_path(), "rb").read()
+    assert table == open(b.mask.get_outfile_path(), "rb").read() and table.count(b"\n") == 120
+    assert a.s_reads == b.s_reads and len(a.s_reads) == 30 and all(a.s_reads)
+    assert a.adapters.json_block() == b.adapters.json_block() and a.gc.json_block() == b.gc.json_block()
+    assert (a.cum_n_seq, a.chunk_n, a.n_bases) == (b.cum_n_seq, b.chunk_n, b.n_bases) == (120, len(ra), T.n_bases)
+    a.close(); b.close()
+
+
+# ---- 4. errors ----
+def check_errors(lib, tmp_path):
+    L = chunkpass._lib(lib)
+    reads = [[b"r%d" % i, b"ACGTNACGTN" * (3 + i)] for i in range(40)]
+    whole = BW.bgzf(BW.bam_stream(reads), 300)
+    blocks, at = [], 0
+    while at < len(whole):
+        blocks.append(at)
+        at += struct.unpack_from("<H", whole, at + 16)[0] + 1
+    crc, deflate, deflate2 = bytearray(whole), bytearray(whole), bytearray(whole)
+    crc[blocks[4] - 8] ^= 0x01                                     # the fourth block's CRC32
+    deflate[blocks[3] + 18 + 5] ^= 0x40
+    deflate2[blocks[6] + 18 + 1] ^= 0xff; deflate2[blocks[2] + 18 + 30] ^= 0x04      # two bad blocks: the lower offset is reported
+    btype, isize = bytearray(whole), bytearray(whole)
+    btype[blocks[3] + 18] |= 0x06                                   # block type 3
+    isize[blocks[3] - 4] += 1                                       # the third block's ISIZE
+    cases = [("crc", bytes(crc)), ("deflate", bytes(deflate)), ("deflate2", bytes(deflate2)), ("cut", whole[:blocks[5] + 40]),
+             ("btype", bytes(btype)), ("isize", bytes(isize))]
+    ch = chunkpass.ReadChunk(None, lib=lib)
+    n, a, b, last = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int()
+    seen = set()
+    for name, data in cases:
+        path = str(tmp_path / (name + ".bam"))
+        open(path, "wb").write(data)
+        msg = {}
+        for mode in ("host", "device"):
+            with pytest.raises(api.LqcovError) as e:
+                list(chunkpass.FileChunks(path, lib=lib, inflate=mode))
+            assert e.value.code == -2, (name, mode, str(e.value))
+            msg[mode] = str(e.value)
+        print(name, msg["device"])
+        assert msg["host"] == msg["device"] and "BGZF block at file offset" in msg["host"], name
+        seen.add(msg["host"].split(": ")[-1])
+        r = L.lqreader_open(path.encode(), 0, 1 << 30, 1, 49, 0)    # the reader then refuses next
+        assert r and L.lqreader_inflate(r, 1) == 0
+        args = (r, ch.h, C.byref(n), C.byref(a), C.byref(b), C.byref(last))
+        assert L.lqreader_next(*args) == -2 and L.lqreader_last_error(r).decode() in msg["host"]
+        assert L.lqreader_next(*args) == -4
+        L.lqreader_close(r)
+    assert "CRC32 mismatch" in seen and "cut short by the end of the file" in seen and "corrupt deflate stream" in seen and "ISIZE does not match the inflated bytes" in seen
+    ch.close()
+
+
+# ---- 5. state, files that are not BGZF ----
+def check_state_and_plain_gzip(lib, tmp_path):
+    L = chunkpass._lib(lib)
+    bam = str(tmp_path / "d.bam")
+    BW.write_bam(bam, [(b"a", b"ACGT"), (b"b", b"TTGCA")])
+    r = L.lqreader_open(bam.encode(), 0, 1, 1, 49, 0)
+    assert r and L.lqreader_inflate(r, 1) == 0 and L.lqreader_inflate(r, 0) == 0 and L.lqreader_inflate(r, 1) == 0 and L.lqreader_inflate(r, 2) == -1
+    ch = chunkpass.ReadChunk(None, lib=lib)
+    n, a, b, last = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int()
+    assert L.lqreader_next(r, ch.h, C.byref(n), C.byref(a), C.byref(b), C.byref(last)) == 0 and n.value == 1 and not last.value
+    assert L.lqreader_inflate(r, 0) == -4 and b"lqreader_inflate" in L.lqreader_last_error(r)
+    assert L.lqreader_next(r, ch.h, C.byref(n), C.byref(a), C.byref(b), C.byref(last)) == 0 and n.value == 1 and b.value == 9
+    L.lqreader_close(r)
+    ch.close()
+    recs = TF.rand_records(17)
+    data = TF.fastq_bytes(recs, 60)
+    path = str(tmp_path / "plain.fq.gz")
+    with gzip.open(path, "wb") as f:
+        f.write(data)
+    want = TF.as_reads(TF.kseq_records(data)[0])
+    for mode in ("host", "device"):
+        assert [r for c, _, _ in TF.all_chunks(lib, path, chunk_size=5000, inflate=mode) for r in c] == want
+    plain = str(tmp_path / "plain.fq")
+    open(plain, "wb").write(data)
+    assert [r for c, _, _ in TF.all_chunks(lib, plain, inflate="device") for r in c] == want
+    with pytest.raises(ValueError):
+        chunkpass.FileChunks(plain, lib=lib, inflate="gpu")
+
+
+def test_emulated_device_inflate_bam(emu_lib, tmp_path, monkeypatch):
+    check_bam(emu_lib, tmp_path, monkeypatch)
+
+
+def test_emulated_device_inflate_bgzip_text(emu_lib, tmp_path, monkeypatch):
+    check_bgzip_text(emu_lib, tmp_path, monkeypatch)
+
+
+def test_emulated_device_inflate_run_file(emu_lib, tmp_path):
+    check_run_file(emu_lib, tmp_path)
+
+
+def test_emulated_device_inflate_errors(emu_lib, tmp_path):
+    check_errors(emu_lib, tmp_path)
+
+
+def test_emulated_device_inflate_state_and_plain_gzip(emu_lib, tmp_path):
+    check_state_and_plain_gzip(emu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_gpu_device_inflate_bam(gpu_lib, tmp_path, monkeypatch):
+    check_bam(gpu_lib, tmp_path, monkeypatch)
+
+
+@pytest.mark.gpu
+def test_gpu_device_inflate_bgzip_text(gpu_lib, tmp_path, monkeypatch):
+    check_bgzip_text(gpu_lib, tmp_path, monkeypatch)
+
+
+@pytest.mark.gpu
+def test_gpu_device_inflate_run_file(gpu_lib, tmp_path):
+    check_run_file(gpu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_gpu_device_inflate_errors(gpu_lib, tmp_path):
+    check_errors(gpu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_gpu_device_inflate_state_and_plain_gzip(gpu_lib, tmp_path):
+    check_state_and_plain_gzip(gpu_lib, tmp_path)

@@ -9,7 +9,11 @@ the bare chunkpass.FileChunks loop (chunk_size 0.5 GiB) over
 must be faster per base than the reference point outside the spread (max < min): exit code 1 otherwise.
 --only bam: the BAM loop alone, for a `rocprofv3 --kernel-trace --stats` run around this script (k_bam_gather's time comes from its
 statistics; it moves 1.5 B per base).  One JSON line (also written to $OUT/bam_time.json when OUT is set).
-Usage: python tools/bam_time.py [--reads 500000] [--chunk-mb 512] [--reps 3] [--workers 16] [--only bam]"""
+--inflate host,device (or one of them): the inflate modes of FileChunks side by side instead -- the BAM at 16 threads and the same
+reads as a bgzip FASTQ (BGZF blocks of 65 280 bytes; "host" is gzread's one thread for it), the modes alternated within every
+repetition, the median and the spread per mode; $OUT/bam_time_inflate.json.  Around a `rocprofv3 --kernel-trace --stats` run with
+--inflate device, k_bgzf_inflate's time per launch comes from the statistics.
+Usage: python tools/bam_time.py [--reads 500000] [--chunk-mb 512] [--reps 3] [--workers 16] [--only bam] [--inflate host,device]"""
 import argparse
 import dataclasses
 import json
@@ -74,15 +78,49 @@ def write_fastq_gz(path, F, pool):
     return len(text)
 
 
+def one_pass(path, cs, threads, inflate=None):
+    t = time.perf_counter()
+    n, nb = 0, 0
+    for ch, _n_seqs, nb in chunkpass.FileChunks(path, chunk_size=cs, n_threads=threads, inflate=inflate):
+        n += ch.n
+    return n, nb, time.perf_counter() - t
+
+
 def loop(path, cs, threads, reps):
     ts, n, nb = [], 0, 0
     for _ in range(reps + 1):
-        t = time.perf_counter()
-        n = 0
-        for ch, _n_seqs, nb in chunkpass.FileChunks(path, chunk_size=cs, n_threads=threads):
-            n += ch.n
-        ts.append(time.perf_counter() - t)
+        n, nb, t = one_pass(path, cs, threads)
+        ts.append(t)
     return n, nb, ts[1:]
+
+
+def inflate_modes(a, F, cs, res, d, pool):
+    """--inflate: the modes alternated on the BAM and on the bgzip FASTQ of the same reads"""
+    modes = a.inflate.split(",")
+    n_reads, n_bases = len(F), int(F.n_bases)
+    bam, fq = os.path.join(d, "all.bam"), os.path.join(d, "all.fastq.gz")
+    stream = bam_stream(F, False)
+    write_bgzf(bam, stream, pool)
+    res["bam_bytes"], res["bam_inflated_bytes"] = os.path.getsize(bam), len(stream)
+    flat, off = F.flat.tobytes(), F.off
+    stream = b"".join(b"@r%07d\n%s\n+\n%s\n" % (i, flat[int(off[i]):int(off[i + 1])], b"!" * int(off[i + 1] - off[i])) for i in range(n_reads))
+    write_bgzf(fq, stream, pool)
+    res["fastq_bgzf_bytes"], res["fastq_bytes"] = os.path.getsize(fq), len(stream)
+    del stream, flat
+    for key, path in (("bam_16_threads", bam), ("fastq_bgzf", fq)):
+        ts = {m: [] for m in modes}
+        for rep in range(a.reps + 1):                               # (the first pass of every mode is the warm-up)
+            for m in modes:
+                n, nb, t = one_pass(path, cs, 16, m)
+                assert (n, nb) == (n_reads, n_bases), (key, m, n, nb)
+                if rep:
+                    ts[m].append(t)
+        for m in modes:
+            res["%s_%s" % (key, m)] = dict(summary(ts[m], n_bases), runs_s=[round(t, 4) for t in ts[m]])
+    if len(modes) == 2:
+        for key in ("bam_16_threads", "fastq_bgzf"):
+            res["%s_%s_over_%s" % (key, modes[0], modes[1])] = round(res["%s_%s" % (key, modes[0])]["median_s"] / res["%s_%s" % (key, modes[1])]["median_s"], 2)
+    res["value"] = res["bam_16_threads_%s" % modes[-1]]["median_s"]
 
 
 def summary(ts, n_bases):
@@ -97,7 +135,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--only", choices=("bam",), default=None)
+    ap.add_argument("--inflate", default=None, help="host, device or host,device: compare FileChunks' inflate modes instead")
     a = ap.parse_args()
+    if a.inflate and not set(a.inflate.split(",")) <= {"host", "device"}:
+        ap.error("--inflate takes host, device or host,device")
     cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
     cs = int(a.chunk_mb * 1024 ** 2)
     t0 = time.time()
@@ -106,6 +147,16 @@ def main():
     res = {"metric": "seconds from the file to resident chunks (bare FileChunks loop)", "unit": "s", "n_reads": n_reads, "n_bases": n_bases,
            "chunk_size": cs, "reps": a.reps}
     ok = True
+    if a.inflate:
+        with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(a.workers) as pool:
+            inflate_modes(a, F, cs, res, d, pool)
+        res["setup_and_run_s"] = round(time.time() - t0, 1)
+        print(json.dumps(res))
+        if os.environ.get("OUT"):
+            os.makedirs(os.environ["OUT"], exist_ok=True)
+            with open(os.path.join(os.environ["OUT"], "bam_time_inflate.json"), "w") as f:
+                f.write(json.dumps(res) + "\n")
+        return 0
     with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(a.workers) as pool:
         bam = os.path.join(d, "all.bam")
         stream = bam_stream(F, False)

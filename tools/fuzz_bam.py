@@ -3,12 +3,16 @@
 16 codes, names, cigars, tag blobs, flags, qualities (some records without), header texts and references, block sizes, stored and
 deflated blocks, empty blocks, files without the EOF marker, piece sizes, thread counts, chunk sizes and both quality modes.  Every
 chunk's records must be the written list cut by lq_utils.parse_bam_chunk's rule.
-    python tools/fuzz_bam.py [--n 300] [--seed 1]        (the emulator build: no GPU needed)"""
+--inflate device: the blocks are inflated by k_bgzf_inflate (FileChunks(inflate="device")); the files then also take level 9 and the
+strategies Z_FIXED, Z_RLE and Z_HUFFMAN_ONLY, and every case is read in host mode as well: the two modes must give the same chunks.
+    python tools/fuzz_bam.py [--n 300] [--seed 1] [--inflate device]        (the emulator build: no GPU needed)"""
 import argparse
 import os
 import random
 import sys
+import struct
 import tempfile
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,6 +23,7 @@ def main():
     ap.add_argument("--n", type=int, default=300)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
+    ap.add_argument("--inflate", choices=("host", "device"), default="host")
     args = ap.parse_args()
     from longqc_amd import api, chunkpass
     from tests import bam_writer as BW
@@ -43,7 +48,21 @@ def main():
                       header_text=bytes(rng.choices(b"@HDSQ\tVN:1.5\n", k=rng.choice((0, 10, 5000)))),
                       refs=[(b"c%d" % i, i) for i in range(rng.choice((0, 0, 1, 200)))], eof=rng.random() < 0.7,
                       empty_block_every=rng.choice((0, 0, 1, 5)))
-            BW.write_bam(path, reads, quals, cigars=cigars, tags=tags, flags=flags, **kw)
+            if args.inflate == "device":                            # bam_writer's blocks with a strategy of zlib's
+                kw["level"], kw["strategy"] = rng.choice((0, 1, 6, 9)), rng.choice((zlib.Z_DEFAULT_STRATEGY, zlib.Z_FIXED, zlib.Z_RLE, zlib.Z_HUFFMAN_ONLY))
+                stream = BW.bam_stream(reads, quals, kw["header_text"], kw["refs"], cigars, tags, flags)
+                with open(path, "wb") as f:
+                    for k, i in enumerate(range(0, len(stream), kw["block_payload"])):
+                        data = [b""] * (kw["empty_block_every"] and k % kw["empty_block_every"] == kw["empty_block_every"] - 1) + [stream[i:i + kw["block_payload"]]]
+                        for part in data:
+                            c = zlib.compressobj(kw["level"], zlib.DEFLATED, -15, 9, kw["strategy"])
+                            body = c.compress(part) + c.flush()
+                            f.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", 18 + len(body) + 8 - 1) + body
+                                    + struct.pack("<II", zlib.crc32(part) & 0xffffffff, len(part)))
+                    if kw["eof"]:
+                        f.write(BW.EOF_BLOCK)
+            else:
+                BW.write_bam(path, reads, quals, cigars=cigars, tags=tags, flags=flags, **kw)
             piece, threads, ov, sequel = rng.choice((None, 16, 100, 4096)), rng.choice((0, 1, 2, 3, 16)), rng.choice((49, 41)), rng.random() < 0.5
             size = sum(3 * ov + len(r[0]) + 2 * len(r[1]) for r in reads)
             cs = rng.choice((1 << 40, 1, size // 3 + 1, max(size, 1)))
@@ -60,9 +79,12 @@ def main():
                     want.append((cur, ns, nb)); cur, acc = [], 0
             want.append((cur, ns, nb))
             try:
-                fc = chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads, is_sequel=sequel)
+                fc = chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads, is_sequel=sequel, inflate=args.inflate)
                 got = [(ch.records(), a, b) for ch, a, b in fc]
                 ok = got == want and fc.format == 1
+                if ok and args.inflate == "device":
+                    ok = got == [(ch.records(), a, b) for ch, a, b in chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads,
+                                                                                         is_sequel=sequel, inflate="host")]
             except api.LqcovError as e:
                 got, ok = repr(e), False
             if not ok:
