@@ -425,7 +425,7 @@ int  lqreader_bam_qualities(lqreader *r, int from_file);
  * for the record walk and the CRC32 check (the pool's threads) and stay in the chunk's raw device buffer for the gather kernels, so
  * the piece is not uploaded.  The chunks, the errors (LQCOV_E_IO: "corrupt deflate stream", "ISIZE does not match the inflated
  * bytes", "CRC32 mismatch", the lowest failing file offset) are those of the host mode.  In device mode a BGZF file that is not BAM
- * (bgzip FASTA/FASTQ) is inflated the same way instead of by gzread; a file that is not BGZF ignores the mode.
+ * (bgzip FASTA/FASTQ) is inflated the same way instead of by gzread; a gzip file that is not BGZF: below; any other file ignores the mode.
  * lqinflate_blocks is the array-level call (tests; callers that hold BGZF blocks of their own): block i is the raw deflate stream
  * comp[in_off[i] .. + in_len[i]) (in_len < 2^24) and inflates to out_host[out_off[i] .. + isize[i]), isize[i] <= 65536.  out_host[0 ..
  * max(out_off + isize)) goes to the device before the launch and comes back after it: bytes outside the blocks' ranges return as they
@@ -442,6 +442,30 @@ int  lqreader_bam_qualities(lqreader *r, int from_file);
 int  lqreader_inflate(lqreader *r, int mode);
 int  lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_t n, const uint64_t *in_off, const uint32_t *in_len,
                       const uint64_t *out_off, const uint32_t *isize, uint8_t *out_host, uint32_t *status);
+/* A gzip file that is not BGZF (what gzip, pigz and most sequencers' pipelines write) carries no block sizes; in device mode it is
+ * inflated by speculative spans: the compressed bytes are cut into spans of LQREADER_GZ_SPAN_BYTES (environment,
+ * read when the reader starts; default 16384, at least 1024, at most 131072, a multiple of 16), k_gz_find looks in each for a
+ * dynamic block's header, k_gz_inflate_spec decodes every span without its history, and a span counts only if it starts at the bit
+ * where the span before it ended (the chain).  What the device cannot vouch for -- an error, a block that fits no span's region -- zlib
+ * redoes on the host from the last accepted block boundary, and zlib's verdict is the call's.  Chunks, borders, counts and names are
+ * the host mode's, and so is the one error: LQCOV_E_IO, "failed to open file '...': not a complete gzip stream" (a bad header, a
+ * corrupt block, a wrong CRC32 or ISIZE; as with gzread, a file that merely ends early ends the reads, and bytes behind the last
+ * member that are not a gzip header are ignored).  How many chunks come out before that error is not part of the contract.
+ * lqreader_inflate_stats: what the reader's gzip stream has done so far (zeros for any other file or mode).
+ * lqinflate_gzip is the array-level call: comp[0 .. comp_len) is a whole gzip file, its bytes go to out[0 .. *out_len), *out_len <=
+ * out_cap (LQCOV_E_ARG if the stream is longer); span_bytes: 0 the default, else as LQREADER_GZ_SPAN_BYTES; stats may be NULL. */
+typedef struct lqinflate_stats {
+	uint64_t launches;           /* windows of compressed bytes uploaded and decoded */
+	uint64_t spans_found;        /* spans in which the search found a block header (a launch's first span is given, not found) */
+	uint64_t spans_accepted;     /* of those: accepted by the chain */
+	uint64_t spans_rejected;     /* of those: not accepted -- the span at which the chain broke and every span behind it in that launch */
+	uint64_t markers_resolved;   /* symbols that stood for a byte in front of their span */
+	uint64_t bytes_device;       /* inflated bytes the device made */
+	uint64_t bytes_zlib;         /* inflated bytes zlib made on the host instead */
+} lqinflate_stats;
+int  lqreader_inflate_stats(const lqreader *r, lqinflate_stats *stats);
+int  lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t span_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                    lqinflate_stats *stats);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 #ifdef __cplusplus

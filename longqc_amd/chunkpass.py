@@ -50,6 +50,8 @@ def _lib(lib=None):
             "lqreader_bam_qualities": (C.c_int, [H, C.c_int]),
             "lqreader_inflate": (C.c_int, [H, C.c_int]),
             "lqinflate_blocks": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P, P, P]),
+            "lqinflate_gzip": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, C.c_uint64, P, P]),
+            "lqreader_inflate_stats": (C.c_int, [H, P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -102,6 +104,44 @@ def inflate_blocks(comp, in_off, in_len, out_off, isize, out=None, device: int =
     if rc != 0:
         raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
     return out, status[:n]
+
+
+INFLATE_STATS = ("launches", "spans_found", "spans_accepted", "spans_rejected", "markers_resolved", "bytes_device", "bytes_zlib")
+
+
+def _stats_dict(words):
+    return dict(zip(INFLATE_STATS, (int(w) for w in words)))
+
+
+def inflate_gzip(data, span_bytes: Optional[int] = None, device: int = 0, lib=None, out_cap: Optional[int] = None):
+    """A whole gzip file in memory, inflated on the device by speculative spans (lqinflate_gzip: k_gz_find, k_gz_inflate_spec,
+    k_gz_window, k_gz_resolve; zlib on the host for what the device cannot vouch for).  span_bytes: compressed bytes per span, a
+    multiple of 16 from 1024 to 131072, None: LQREADER_GZ_SPAN_BYTES or the default.  out_cap: room for the bytes, default what the
+    members' ISIZE fields and the deflate bound allow.  -> (bytes, stats: a dict of INFLATE_STATS).  A stream that gzread would
+    refuse raises LqcovError (-2)."""
+    lib = _lib(lib)
+    comp = np.frombuffer(bytes(data), dtype=np.uint8)
+    if out_cap is None:
+        out_cap = 1032 * comp.shape[0] + 64                        # (deflate gives at most 1032 bytes per byte)
+        if comp.shape[0] >= 18 and comp.shape[0] < (1 << 32):
+            import zlib
+            try:                                                    # (a well-formed file says how long it is)
+                d, n, rest = zlib.decompressobj(31), 0, bytes(data)
+                while rest[:2] == b"\x1f\x8b":
+                    n += len(d.decompress(rest)); rest = d.unused_data
+                    if not d.eof:
+                        break
+                    d = zlib.decompressobj(31)
+                out_cap = n + 64
+            except zlib.error:
+                out_cap = min(out_cap, 1 << 28)
+    out = np.empty(max(int(out_cap), 1), np.uint8)
+    n, st = C.c_uint64(), (C.c_uint64 * len(INFLATE_STATS))()
+    rc = lib.lqinflate_gzip(device, comp.ctypes.data if comp.shape[0] else None, comp.shape[0], int(span_bytes or 0), out.ctypes.data, int(out_cap),
+                            C.byref(n), st)
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return out[:n.value].tobytes(), _stats_dict(st)
 
 
 class ReadChunk:
@@ -245,14 +285,15 @@ class FileChunks:
     starts.
     inflate="device": the BGZF blocks of a BAM file -- and of a bgzip FASTA/FASTQ, which otherwise is gzread's -- are inflated on the
     device (k_bgzf_inflate); "host": the thread pool and gzread; None: what the environment variable LQREADER_INFLATE says, "host"
-    without it.  The chunks are the same."""
+    without it.  The chunks are the same.  A gzip file that is not BGZF is inflated in device mode by speculative spans (k_gz_*; the span
+    length: LQREADER_GZ_SPAN_BYTES); inflate_stats (a dict of INFLATE_STATS) says after iteration what that took."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
                  lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None):
         self.lib = _lib(lib)
         self.inflate = inflate_mode(inflate)
         self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
-        self.is_sequel, self.format = is_sequel, None
+        self.is_sequel, self.format, self.inflate_stats = is_sequel, None, _stats_dict([0] * len(INFLATE_STATS))
         self.chunk_size = max(0, int(math.ceil(chunk_size)))        # size >= chunk_size for an integer size
         self.str_overhead = sys.getsizeof("") if str_overhead is None else int(str_overhead)
 
@@ -276,6 +317,9 @@ class FileChunks:
                 chunk._from_reader(r, n.value)
                 yield chunk, n_seqs.value, n_bases.value
         finally:
+            st = (C.c_uint64 * len(INFLATE_STATS))()
+            if lib.lqreader_inflate_stats(r, st) == 0:
+                self.inflate_stats = _stats_dict(st)
             lib.lqreader_close(r)
             if chunk is not None:
                 chunk.close()

@@ -23,11 +23,14 @@
 // put them, and they come back into the piece for the host to parse and to check their CRC32 -- the parsers and the gather kernels
 // are the same, the upload of the piece falls away.  The raw buffer then mirrors the piece from its first byte that is not part of
 // the chunk yet (up_from) to its last (fill), not only what has been parsed.  In that mode a BGZF file that is not BAM (bgzip
-// FASTA/FASTQ) is inflated the same way and parsed by the kseq grammar; gzread is not used for it.
+// FASTA/FASTQ) is inflated the same way and parsed by the kseq grammar; gzread is not used for it.  A gzip file that is not BGZF
+// is inflated by speculative spans (gzip.hpp, kernels_gzip.hpp) under the same rules: the bytes land in the raw buffer, come back
+// into the piece, and what the file is or is not is what gzread says of it.
 #include "chunk.hpp"
 #include "fastx_mem.hpp"
 #include "bgzf.hpp"
 #include "kernels_inflate.hpp"
+#include "gzip.hpp"
 #include <zlib.h>
 #include <cstdlib>
 #include <memory>
@@ -82,6 +85,7 @@ struct lqreader {
 	int inflate_mode = LQREADER_INFLATE_HOST; bool bgzf_text = false;     // lqreader_inflate's; a BGZF file that is not BAM
 	int bgzf_fd = -1;                                         // device mode on such a file: the descriptor the blocks are read from
 	InflateDev inf; hipStream_t inf_stream = nullptr;
+	GzipInflater gzdev; int gzdev_fd = -1;                    // device mode on a gzip file that is not BGZF
 	int hdr_state = 0; u64 hdr_skip = 0; u32 hdr_refs = 0;    // the BAM header: 0 magic and l_text, 1 the text, 2 n_ref, 3 l_name, 4 name and l_ref, 5 records
 	// the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet
 	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
@@ -98,6 +102,7 @@ struct lqreader {
 		if (gz) gzclose(gz);
 		if (fd >= 0) ::close(fd);
 		if (bgzf_fd >= 0) ::close(bgzf_fd);
+		if (gzdev_fd >= 0) ::close(gzdev_fd);
 		if (buf) lqcov_host_free(buf);
 	}
 
@@ -139,13 +144,25 @@ struct lqreader {
 	}
 
 	bool use_bgzf() const { return format == 1 || (bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE); }
-	bool on_device() const { return inflate_mode == LQREADER_INFLATE_DEVICE && use_bgzf(); }
+	bool use_gzdev() const { return format == 0 && gz && !bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE; }
+	bool on_device() const { return inflate_mode == LQREADER_INFLATE_DEVICE && (use_bgzf() || use_gzdev()); }
 
 	// the first lqreader_next: the mode is final
 	void start()
 	{
 		started = true;
 		if (!on_device()) return;
+		if (use_gzdev()) {                                        // (gz keeps its descriptor; nothing has been read through it)
+			gzdev_fd = ::open(path.c_str(), O_RDONLY);
+			if (gzdev_fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
+			gzdev.fd = gzdev_fd; gzdev.span_bytes = GzipInflater::span_bytes_env();
+			gzdev.dev_room = [this](u8 *dst, u64 n) {             // as below: dst is a place of the piece
+				const u64 ahead = (u64)(dst - buf) - up_from;
+				raw_reserve(inf_stream, ahead + n, ahead);
+				return raw.as<u8>() + raw_used + ahead;
+			};
+			return;
+		}
 		if (format == 0) {                                        // (gz keeps its descriptor; nothing has been read through it)
 			bgzf_fd = ::open(path.c_str(), O_RDONLY);
 			if (bgzf_fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
@@ -192,6 +209,24 @@ struct lqreader {
 				set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
 			}
 			return false;
+		}
+		if (use_gzdev()) {                                        // as gzread: until the piece is full, the stream over, or broken
+			bool any = false;
+			while (!eof) {
+				u64 need = 0, got = 0;
+				gzdev.stream = inf_stream;
+				try { got = gzdev.fill(buf + fill, cap - fill, &need); }
+				catch (const GzipError &e) { bam_fail(e.what()); }
+				catch (const std::runtime_error &e) { if (strcmp(e.what(), "read error")) throw; bam_fail(e.what()); }
+				fill += got; any = any || got;
+				if (gzdev.done) { eof = true; break; }
+				if (fill == cap) break;
+				if (!got) {
+					if (any) break;                                       // (the next call makes room)
+					set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
+				}
+			}
+			return any;
 		}
 		while (!eof && fill < cap) {
 			const u64 want = std::min<u64>(cap - fill, 1u << 30);
@@ -505,6 +540,48 @@ int lqreader_inflate(lqreader *r, int mode)
 	if (r->started) { r->err = "lqreader_inflate after the first lqreader_next"; return LQCOV_E_STATE; }
 	r->inflate_mode = mode;
 	return 0;
+}
+
+int lqreader_inflate_stats(const lqreader *r, lqinflate_stats *stats)
+{
+	if (!r || !stats) return LQCOV_E_ARG;
+	*stats = r->gzdev.stats;
+	return 0;
+}
+
+int lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t span_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                   lqinflate_stats *stats)
+{
+	char msg[512] = {0};
+	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+		if (!out_len || (comp_len && !comp) || (out_cap && !out)) throw std::invalid_argument("null buffers");
+		if (span_bytes && (span_bytes < 1024 || span_bytes > (1u << 17) || (span_bytes & 15))) throw std::invalid_argument("span_bytes must be a multiple of 16 from 1024 to 131072");
+		*out_len = 0;
+		lq_cabi::select_device(device);
+		hipStream_t stream = nullptr;
+		LQ_HIP_CHECK(hipStreamCreate(&stream));
+		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		DBuf d_out;
+		d_out.ensure((size_t)out_cap + 16);
+		GzipInflater g;
+		u8 none[1];
+		g.mem = comp_len ? comp : none; g.mem_len = comp_len; g.stream = stream;
+		g.span_bytes = span_bytes ? span_bytes : GzipInflater::span_bytes_env();
+		g.dev_room = [&](u8 *dst, u64) { return d_out.as<u8>() + (dst - out); };
+		u64 n = 0;
+		try {
+			while (!g.done) {
+				u64 need = 0;
+				const u64 got = g.fill(out + n, out_cap - n, &need);
+				n += got;
+				if (!got && !g.done) throw std::invalid_argument("out_cap is smaller than the inflated stream");
+			}
+		} catch (const GzipError &e) { throw std::runtime_error(std::string("failed to open file '(memory)': ") + e.what()); }
+		*out_len = n;
+		if (stats) *stats = g.stats;
+	});
+	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
+	return rc;
 }
 
 int lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_t n, const uint64_t *in_off, const uint32_t *in_len,

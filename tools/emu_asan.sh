@@ -11,4 +11,4 @@ SRCS="engine.cpp api.cpp dust.cpp adapt.cpp gc.cpp chunk.cpp reader.cpp"      # 
 # what the environment preloads already stays, behind the sanitizer)
 LQCOV_EMU_LIB="$OUT" LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libstdc++.so)${LD_PRELOAD:+ $LD_PRELOAD}" ASAN_OPTIONS=detect_leaks=0 \
   python -m pytest tests/test_emu_pipeline.py tests/test_mmi.py tests/test_sdust.py tests/test_adapter.py tests/test_gcfrac.py tests/test_chunkpass.py \
-    tests/test_launch_caps.py tests/test_filechunks.py tests/test_inflate.py tests/test_inflate_caps.py -m "not gpu" -x -q "${@:--n 6}"
+    tests/test_launch_caps.py tests/test_filechunks.py tests/test_inflate.py tests/test_inflate_caps.py tests/test_gzip_inflate.py tests/test_gzip_reader.py tests/test_gzip_caps.py -m "not gpu" -x -q "${@:--n 6}"

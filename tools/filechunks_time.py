@@ -7,7 +7,11 @@ exists in Python for a one-line FASTQ), the reader's time reported apart; --reps
 (b) --only gather: FileChunks alone, --reps times over the file, for a `rocprofv3 --kernel-trace --stats` run around this script
 (k_chunk_gather's time comes from its statistics), and a device-to-device copy of the bytes the two launches move (torch, same
 process, wall time of copy + synchronize; under rocprofv3 its kernel is in the same statistics).  One JSON line (also written to $OUT/filechunks_time.json when OUT is set).
-Usage: python tools/filechunks_time.py [--reads 500000] [--chunk-mb 512] [--nsample 5000] [--reps 3] [--workers 16] [--only loop|gather]"""
+(c) --inflate host,device: the same FASTQ as a plain .gz (zlib level 6, one member), FileChunks alone in each mode named -- gzread
+on one thread against the speculative spans of csrc/gzip.hpp -- alternated, one warm-up pass and --reps timed ones per mode, medians
+and the spread, the device mode's inflate_stats; the modes must count the same reads and bases.
+Usage: python tools/filechunks_time.py [--reads 500000] [--chunk-mb 512] [--nsample 5000] [--reps 3] [--workers 16] [--only loop|gather]
+       python tools/filechunks_time.py --reads 50000 --inflate host,device [--reps 3]"""
 import argparse
 import dataclasses
 import json
@@ -95,6 +99,31 @@ def gather_only(path, cs, reps, n_bases):
             "copy_ms_median": round(med, 3), "copy_ms_min": round(min(ms), 3), "copy_gb_per_s": round(4 * n_bases / med / 1e6, 1)}
 
 
+def inflate_modes(path, cs, reps, modes):
+    import zlib
+    gz = path + ".gz"
+    t0 = time.time()
+    c = zlib.compressobj(6, zlib.DEFLATED, 31)
+    with open(path, "rb") as f, open(gz, "wb") as g:
+        for block in iter(lambda: f.read(1 << 24), b""):
+            g.write(c.compress(block))
+        g.write(c.flush())
+    out = {"gz_bytes": os.path.getsize(gz), "compress_s": round(time.time() - t0, 1), "modes": {}}
+    runs, counts, stats = {m: [] for m in modes}, {}, {}
+    for it in range(reps + 1):                                  # alternated; the first pass of every mode is the warm-up
+        for m in modes:
+            fc = chunkpass.FileChunks(gz, chunk_size=cs, inflate=m)
+            t = time.perf_counter()
+            tot = [(ns, nb) for _, ns, nb in fc][-1]
+            if it:
+                runs[m].append({"wall_s": time.perf_counter() - t})
+            counts[m], stats[m] = tot, fc.inflate_stats
+    for m in modes:
+        out["modes"][m] = dict(summary(runs[m]), reads_bases=counts[m], inflate_stats=stats[m])
+    out["same_counts"] = len(set(counts.values())) == 1
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=500000)
@@ -103,6 +132,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--only", choices=("loop", "gather"), default=None)
+    ap.add_argument("--inflate", default=None, help="host,device: time FileChunks on the file as a plain .gz in these modes, and nothing else")
     a = ap.parse_args()
     cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
     cs = int(a.chunk_mb * 1024 ** 2)
@@ -119,7 +149,10 @@ def main():
                "file_bytes": os.path.getsize(path), "chunk_size": cs, "nsample": a.nsample, "setup_s": round(time.time() - t0, 1)}
         del F, flat
         sum(ch.n for ch, _, _ in chunkpass.FileChunks(path, chunk_size=cs))       # device start-up, the file in the page cache
-        if a.only != "gather":
+        if a.inflate:
+            res["metric"] = "seconds from the gzip FASTQ file to its chunks on the device"
+            res["inflate"] = inflate_modes(path, cs, a.reps, a.inflate.split(","))
+        elif a.only != "gather":
             news, olds, same = [], [], True
             for _ in range(a.reps):                                 # alternated
                 r_new, o_new = new_loop(path, cs, a.nsample, d)
@@ -128,7 +161,7 @@ def main():
                 same = same and o_new == o_old
             res.update(run_file=summary(news), python_reader_and_add_chunk=summary(olds), same_results=same, reps=a.reps, chunks=o_new[2])
             res["value"] = res["run_file"]["wall_s"]["median"]
-        if a.only != "loop":
+        if a.only != "loop" and not a.inflate:
             res["gather"] = gather_only(path, cs, a.reps, n_bases)
     print(json.dumps(res))
     if os.environ.get("OUT"):

@@ -2,7 +2,12 @@
 """The two FASTA/FASTQ readers on random text: the streaming reader (csrc/fastx.hpp, kseq's grammar, kseq.h:179-224) and the
 mapped-file reader (csrc/fastx_mem.hpp: pieces parsed by several threads from guessed record starts) must report the same
 records -- count, bases, and the two digests of names+sequences and of qualities -- on every input, however malformed.
-    python tools/fuzz_reader.py [--n 20000] [--seed 1]        (host code only: any build of the library will do)"""
+    python tools/fuzz_reader.py [--n 20000] [--seed 1]        (host code only: any build of the library will do)
+--inflate device: gzip cases instead, as tools/fuzz_bam.py has them for BGZF -- record texts compressed by zlib at random level, memLevel,
+strategy and flush points, as one or several members, some with a damaged byte, a cut end or bytes behind the last member; each is
+read by FileChunks in host mode (gzread) and in device mode (speculative spans, csrc/gzip.hpp) at a random span length, and the
+records, the counts and the error must be the same.
+    python tools/fuzz_reader.py --inflate device [--n 300] [--seed 1]        (the emulator build, or the GPU's with --lib)"""
 import argparse
 import ctypes as C
 import os
@@ -15,14 +20,79 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def gzip_cases(lib, n, seed):
+    import random
+    import zlib
+    from longqc_amd import api, chunkpass
+    rng = random.Random(seed)
+
+    def text():
+        recs = []
+        for r in range(rng.randrange(1, 400)):
+            L = rng.randrange(0, 3000) if rng.random() < 0.2 else rng.randrange(0, 200)
+            s = bytes(rng.choices(b"ACGTN", k=L))
+            if rng.random() < 0.3:
+                recs.append(b">r%d c\n" % r + s + b"\n")
+            else:
+                recs.append(b"@r%d\n" % r + s + b"\n+\n" + bytes(rng.choices(b"#$%&'()*+,-./0123456789:;<=>?@ABCDEFGHI", k=L)) + b"\n")
+        return b"".join(recs)
+
+    def member(data):
+        c = zlib.compressobj(rng.choice((0, 1, 1, 6, 6, 6, 9)), zlib.DEFLATED, 31, rng.randrange(1, 10),
+                             rng.choice((zlib.Z_DEFAULT_STRATEGY,) * 4 + (zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE, zlib.Z_FILTERED)))
+        if rng.random() < 0.7:
+            return c.compress(data) + c.flush()
+        step, out = rng.randrange(500, 20000), []
+        for i in range(0, len(data), step):
+            out.append(c.compress(data[i:i + step]) + c.flush(rng.choice((zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH))))
+        return b"".join(out) + c.flush()
+
+    def read(path, mode):
+        try:
+            fc = chunkpass.FileChunks(path, chunk_size=rng_cs, lib=lib, str_overhead=49, inflate=mode)
+            return [(ch.records(), ns, nb) for ch, ns, nb in fc], None
+        except api.LqcovError as e:
+            return None, (e.code, str(e))
+
+    bad = 0
+    with tempfile.TemporaryDirectory() as d:
+        fn = os.path.join(d, "f.fq.gz")
+        for it in range(n):
+            data = bytearray(b"".join(member(text()) for _ in range(rng.choice((1, 1, 1, 2, 3)))))
+            kind = rng.randrange(6)
+            if kind == 1:
+                data[rng.randrange(len(data))] ^= 1 << rng.randrange(8)
+            elif kind == 2:
+                del data[rng.randrange(len(data)):]
+            elif kind == 3:
+                data += rng.choice((bytes(rng.randrange(1, 200)), b"@x\nACGT\n+\nIIII\n", b"\x1f", b"\x1f\x8b", b"\x1f\x8b\x08\x00"))
+            open(fn, "wb").write(bytes(data))
+            os.environ["LQREADER_GZ_SPAN_BYTES"] = str(rng.choice((1024, 2048, 4096, 16384)))
+            rng_cs = rng.choice((1 << 40, 20000, 100000))
+            host, dev = read(fn, "host"), read(fn, "device")
+            # (an error: the code and the message; how many chunks came before it is not compared)
+            if host != dev:
+                bad += 1
+                print("case %d (kind %d, %d bytes, span %s) differs: host %s, device %s" % (it, kind, len(data), os.environ["LQREADER_GZ_SPAN_BYTES"],
+                      host[1] or len(host[0]), dev[1] or len(dev[0])))
+                open("fuzz_reader_case_%d.gz" % it, "wb").write(bytes(data))
+                if bad >= 5:
+                    break
+    print("%d gzip inputs, %d on which host and device mode disagree" % (it + 1, bad))
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=20000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
+    ap.add_argument("--inflate", choices=("host", "device"), default="host")
     args = ap.parse_args()
     from longqc_amd import api
     lib = api.load_library(args.lib)
+    if args.inflate == "device":
+        sys.exit(gzip_cases(lib, args.n if args.n != 20000 else 300, args.seed))
     rng = np.random.default_rng(args.seed)
     toks = [b">", b"@", b"+", b"\n", b"\n", b"\n", b"\r\n", b"\r", b" ", b"\t", b"ACGT", b"acgtnN", b"U", b"!!!!", b"IIII", b"@@", b">>", b"+\n", b"name", b"x y", b""]
     bad = 0
