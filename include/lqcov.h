@@ -468,6 +468,33 @@ int  lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t
                     lqinflate_stats *stats);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
+/* ---- the chunk loop's files: trimmed reads (longQC.py:345-346) and the FASTQ a BAM file is converted to (:302-303) ------------------ */
+/* The reads of a resident chunk as FASTQ text, made on the device (k_fastq_format): record i is '@' name '\n' seq[begin[i]:end[i]]
+ * '\n' '+' '\n' qual[begin[i]:end[i]] '\n' -- what lq_utils.write_fastq writes for the record cut that way.  names / name_off: as
+ * lqstore_append takes them (NUL-terminated, n offsets; names == NULL: empty names); begin == end == NULL: whole reads.
+ * lqchunk_fastq makes the whole text in out[0 .. *out_len) (*out_len is set to the text's length also when out_cap is too small).
+ * lqfastq_* streams it into a file: lqfastq_write makes the text in pieces of piece_bytes (a multiple of 4096, 0: the default of 16
+ * MiB; byte ranges of the text, not records), each copied into one of two page-locked buffers on the chunk's stream and appended to
+ * the file by the writer's thread while the next piece is made; it returns when the last piece is in its buffer -- the chunk handle is
+ * free for the next chunk -- with *bytes_written the text's length (bytes_written may be NULL).  The file is opened for appending
+ * (created if missing) when the first byte comes; a chunk without reads writes nothing and creates nothing.  lqfastq_close waits for
+ * the thread, closes the file, frees the writer and returns its first error; the file is complete when it returns 0.
+ * Errors: LQCOV_E_ARG -- begin[i] > end[i], end[i] > the read's length, a chunk loaded without qualities, a chunk of another device,
+ * out_cap too small (nothing was written, the writer stays usable); LQCOV_E_STATE -- no chunk loaded; LQCOV_E_IO -- the file cannot
+ * be opened or written (from the lqfastq_write that meets it, a later one, or lqfastq_close); LQCOV_E_DEVICE.  After an I/O or device
+ * error every later lqfastq_write returns that error at once.  The message: lqchunk_last_error (lqchunk_fastq), lqfastq_last_error(w),
+ * and lqfastq_last_error(NULL) for a failed lqfastq_open and for what lqfastq_close reported (per thread).  lqfastq_kernel_ms:
+ * k_fastq_format's time on the device over all writes so far (HIP events), for measurements. */
+typedef struct lqfastq lqfastq;
+int  lqchunk_fastq(lqchunk *c, const char *names, const uint64_t *name_off, const uint32_t *begin, const uint32_t *end,
+                   uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+lqfastq *lqfastq_open(const char *path, int device, uint64_t piece_bytes);
+int  lqfastq_write(lqfastq *w, lqchunk *c, const char *names, const uint64_t *name_off, const uint32_t *begin, const uint32_t *end,
+                   uint64_t *bytes_written);
+int  lqfastq_close(lqfastq *w);
+const char *lqfastq_last_error(const lqfastq *w);
+double lqfastq_kernel_ms(const lqfastq *w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,11 +107,28 @@ def _cut(reads, rows, th, r, three, len_list, lens):
     return (iden_max, len(cut_pos), cut_pos)
 
 
-def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=150, device=0, lib=None, chunk=None):
+def trim_bounds(o5, o3, lens, th=0.75, length=150):
+    """What _cut leaves of every read, in the untrimmed read's coordinates: (begin, end) as uint32 arrays, read i keeps
+    seq[begin[i]:end[i]].  o5 / o3: the rows of the 5' / 3' search (n x 4 of d, s, e, L; None: that adapter is not cut), lens: the
+    reads' lengths.  begin = e5 + 1 where the read is long enough (>= 2 * length) and the 5' identity exceeds th, else 0; end =
+    L - length + s3 where the identity exceeds th and the 5'-trimmed read is long enough (L - begin >= 2 * length), else L."""
+    lens = np.asarray(lens, dtype=np.int64)
+    begin, end = np.zeros(lens.shape[0], dtype=np.int64), lens.copy()
+    if o5 is not None:
+        hit = (lens >= 2 * length) & (_identity(o5) > th)
+        begin[hit] = o5[hit, 2].astype(np.int64) + 1
+    if o3 is not None:
+        hit = (lens - begin >= 2 * length) & (_identity(o3) > th)
+        end[hit] = lens[hit] - length + o3[hit, 1].astype(np.int64)
+    return begin.astype(np.uint32), end.astype(np.uint32)
+
+
+def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=150, device=0, lib=None, chunk=None, bounds_out=None):
     """== lq_adapt.cut_adapter (lq_adapt.py:80-101): reads are LongQC's mutable [name, seq, qual, ...] records, trimmed in
     place; returns (iden_max, match_num, cut_pos) for one adapter, ((...5'), (...3')) for two, None (logged) for none.
     chunk: a chunkpass.ReadChunk made of these (untrimmed) reads: the search runs on its device copy, which stays as it is;
-    nothing is gathered or uploaded.  With a chunk, reads may be None: the tuples alone, no record is trimmed."""
+    nothing is gathered or uploaded.  With a chunk, reads may be None: the tuples alone, no record is trimmed.
+    bounds_out: a list that is given [begin, end], trim_bounds of the rows this call searched (what a FastqWriter takes)."""
     if not adp_t and not adp_b:
         logger.error("No adapter sequence is given.")
         return None
@@ -126,6 +143,8 @@ def cut_adapter(reads, len_list=None, adp_t=None, adp_b=None, th=0.75, length=15
         seqs = [rd[1] for rd in reads]
         o5, o3 = _hits(seqs, adp_t, adp_b, length, device, lib)
         lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
+    if bounds_out is not None:
+        bounds_out[:] = trim_bounds(o5, o3, lens, th, length)
     t5 = t3 = None
     if adp_t:
         t5 = _cut(reads, o5, th, length, False, len_list, lens)

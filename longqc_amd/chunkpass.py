@@ -52,6 +52,12 @@ def _lib(lib=None):
             "lqinflate_blocks": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P, P, P]),
             "lqinflate_gzip": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, C.c_uint64, P, P]),
             "lqreader_inflate_stats": (C.c_int, [H, P]),
+            "lqchunk_fastq": (C.c_int, [H, C.c_char_p, P, P, P, P, C.c_uint64, P]),
+            "lqfastq_open": (H, [C.c_char_p, C.c_int, C.c_uint64]),
+            "lqfastq_write": (C.c_int, [H, H, C.c_char_p, P, P, P, P]),
+            "lqfastq_close": (C.c_int, [H]),
+            "lqfastq_last_error": (C.c_char_p, [H]),
+            "lqfastq_kernel_ms": (C.c_double, [H]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -236,6 +242,35 @@ class ReadChunk:
             a += l
         return out
 
+    def names_c(self):
+        """the names as the C ABI takes them (NUL-terminated blob, uint64 offsets), encoded once per chunk"""
+        if self._name_blob is None:
+            self._name_blob = api.encode_names(self.names)
+        return self._name_blob
+
+    def bounds_c(self, begin, end):
+        """begin / end of fastq_bytes and FastqWriter.write as contiguous uint32 arrays of n entries, (None, None) for whole reads"""
+        if (begin is None) != (end is None):
+            raise ValueError("begin and end come together")
+        if begin is None:
+            return None, None
+        begin, end = np.ascontiguousarray(begin, dtype=np.uint32), np.ascontiguousarray(end, dtype=np.uint32)
+        if begin.shape != (self.n,) or end.shape != (self.n,):
+            raise ValueError("begin and end must have one entry per read")
+        return begin, end
+
+    def fastq_bytes(self, begin=None, end=None) -> bytes:
+        """the chunk's reads, read i cut to [begin[i], end[i]) (None: whole reads), as FASTQ text -- what sampleqc.write_fastq writes for
+        records() trimmed that way -- made on the device (k_fastq_format): lqchunk_fastq"""
+        begin, end = self.bounds_c(begin, end)
+        nb, noff = self.names_c()
+        kept = self.lens if begin is None else end.astype(np.int64) - begin.astype(np.int64)
+        cap = int((np.diff(noff).astype(np.int64) - 1).sum() + 2 * kept.sum() + 6 * self.n) if self.n else 0
+        out, n = np.empty(max(cap, 1), np.uint8), C.c_uint64()
+        self._ck(self.lib.lqchunk_fastq(self.h, nb, noff.ctypes.data, begin.ctypes.data if begin is not None else None,
+                                        end.ctypes.data if end is not None else None, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].tobytes()
+
     # -- the steps, as arrays --
     def sdust(self, w: int = 64, t: int = 20):
         """-> (masked bases, sums of 10^(-q/10), qualities above Q7) per read: lqchunk_sdust"""
@@ -325,6 +360,74 @@ class FileChunks:
                 chunk.close()
 
 
+class FastqWriter:
+    """Appends resident chunks to a FASTQ file as sampleqc.write_fastq(path, records, is_chunk=True) does (lqfastq_*): write(chunk,
+    begin, end) makes the text of the chunk's reads, read i cut to [begin[i], end[i]) (None: whole reads), on the device piece by
+    piece (piece_bytes, a multiple of 4096; None: the library's default) and hands the pieces to a thread that appends them to the
+    file -- it returns the bytes of text, possibly before the last of them is in the file.  The file is opened (for appending) when
+    the first byte comes: a writer that saw only empty chunks leaves no file.  close() waits for the thread and raises what it or
+    the file reported; after an I/O or device error every later write raises it again.  A context manager."""
+
+    def __init__(self, path, device: int = 0, piece_bytes: Optional[int] = None, lib=None):
+        self.lib = _lib(lib)
+        self.path, self.device, self.kernel_ms = os.fspath(path), device, 0.0
+        self.h = self.lib.lqfastq_open(os.fsencode(self.path), device, int(piece_bytes or 0))
+        if not self.h:
+            raise api.LqcovError(-1, self.lib.lqfastq_last_error(None).decode() or "lqfastq_open failed")
+
+    def write(self, chunk: ReadChunk, begin=None, end=None) -> int:
+        if not self.h:
+            raise ValueError("the writer is closed")
+        begin, end = chunk.bounds_c(begin, end)
+        nb, noff = chunk.names_c()
+        n = C.c_uint64()
+        rc = self.lib.lqfastq_write(self.h, chunk.h, nb, noff.ctypes.data, begin.ctypes.data if begin is not None else None,
+                                    end.ctypes.data if end is not None else None, C.byref(n))
+        if rc != 0:
+            raise api.LqcovError(rc, self.lib.lqfastq_last_error(self.h).decode())
+        return n.value
+
+    def close(self):
+        """the file is complete when this returns; raises the error of a piece written since the last write()"""
+        if getattr(self, "h", None):
+            h, self.h = self.h, None
+            self.kernel_ms = float(self.lib.lqfastq_kernel_ms(h))   # k_fastq_format's time on the device, all writes (HIP events)
+            rc = self.lib.lqfastq_close(h)
+            if rc != 0:
+                raise api.LqcovError(rc, self.lib.lqfastq_last_error(None).decode())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:                                                      # (the error on its way out is the one to report)
+            try:
+                self.close()
+            except api.LqcovError:
+                pass
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _close_writers(writers, quiet: bool = False):
+    """close every FastqWriter; the first error is raised when all are closed (quiet: dropped)"""
+    first = None
+    for w in writers:
+        try:
+            w.close()
+        except api.LqcovError as e:
+            first = first or e
+    if first is not None and not quiet:
+        raise first
+
+
 class PackedStore:
     """The packed chunks of the whole input in device memory (lqstore_*)."""
 
@@ -337,7 +440,7 @@ class PackedStore:
     def append(self, chunk: ReadChunk):
         if not chunk.packed:
             chunk.pack()
-        nb, noff = chunk._name_blob or api.encode_names(chunk.names)
+        nb, noff = chunk.names_c()
         chunk._ck(self.lib.lqstore_append(self.h, chunk.h, nb, noff.ctypes.data))
 
     @property
@@ -380,6 +483,7 @@ class SampleQCPass:
         self.store = PackedStore(device, lib)
         self.s_reads, self.cum_n_seq, self.chunk_n, self.n_bases = [], 0, 0, 0
         self.trimmed = None
+        self.trim_writer = self.fastx_writer = None                 # FastqWriters of run_file(trim=<path>, fastx_out=<path>)
 
     def add_chunk(self, reads):
         chunk = ReadChunk(reads, device=self.device, lib=self.lib)
@@ -388,18 +492,23 @@ class SampleQCPass:
         finally:
             chunk.close()
 
-    def add_resident(self, chunk: ReadChunk, trim: bool = False):
+    def add_resident(self, chunk: ReadChunk, trim=False):
         """add_chunk on a chunk that is on the device already (FileChunks'): nothing is gathered or uploaded, and of the reads only
-        the subsample's winners come to the host -- with trim=True (--trim) all of them, for `trimmed`"""
+        the subsample's winners come to the host -- with trim=True (--trim) all of them, for `trimmed`.  trim=<a FastqWriter>: the
+        trimmed reads go to it from the device (k_fastq_format), `trimmed` stays None and no further read comes to the host"""
         return self._add(chunk, None, trim)
 
     def _add(self, chunk, reads, trim):
         self.mask.submit_sdust(reads, self.chunk_n, chunk=chunk)                                        # longQC.py:307
         result = None
+        writer = trim if isinstance(trim, FastqWriter) else None
         if self.adp5 or self.adp3:                                                                      # :310-320, on a copy as the pool's pickling makes one
-            self.trimmed = ([list(r) for r in reads] if reads is not None else chunk.records()) if trim else None
-            result = adapter.cut_adapter(self.trimmed, adp_t=self.adp5, adp_b=self.adp3, chunk=chunk)
+            self.trimmed = ([list(r) for r in reads] if reads is not None else chunk.records()) if trim and not writer else None
+            bounds = [] if writer else None
+            result = adapter.cut_adapter(self.trimmed, adp_t=self.adp5, adp_b=self.adp3, chunk=chunk, bounds_out=bounds)
             self.adapters.add(result)                                                                   # :348-357
+            if writer:
+                writer.write(chunk, *bounds)                                                            # :345-346
         if reads is not None:
             self.s_reads = sampleqc.subsample_from_chunk(reads, self.cum_n_seq, self.s_reads, self.nsample)    # :323
         else:
@@ -411,17 +520,38 @@ class SampleQCPass:
         self.n_bases += int(chunk.lens.sum())
         return result
 
-    def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim: bool = False, is_upper: bool = True, str_overhead: Optional[int] = None,
-                 is_sequel: bool = True, inflate: Optional[str] = None):
-        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (no FASTQ is written first, as
-        longQC.py:302-303 does; is_sequel, inflate: FileChunks'): FileChunks + add_resident.  -> the per-chunk
-        adapter results; with trim=True `trimmed_chunks` holds every chunk's trimmed records (longQC.py:330-338 writes them out)"""
+    def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
+                 is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None):
+        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate:
+        FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
+        trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
+        appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
+        `trimmed` stays None and `trimmed_chunks` empty.  fastx_out=<path>: every chunk is appended to that file untrimmed -- the
+        FASTQ that longQC.py:302-303 converts a BAM file to, for any input.  Both files are complete, and their errors raised, when
+        the call returns."""
         results, self.trimmed_chunks = [], []
-        for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
-                                                    inflate=inflate):
-            results.append(self.add_resident(chunk, trim=trim))
-            if trim:
-                self.trimmed_chunks.append(self.trimmed)
+        to_file = isinstance(trim, (str, os.PathLike))
+        if to_file and not (self.adp5 or self.adp3):
+            raise ValueError("trim=<path> needs an adapter")
+        writers = []
+        try:
+            if to_file:
+                self.trim_writer = trim = FastqWriter(trim, device=self.device, lib=self.lib)
+                writers.append(trim)
+            if fastx_out is not None:
+                self.fastx_writer = FastqWriter(fastx_out, device=self.device, lib=self.lib)
+                writers.append(self.fastx_writer)
+            for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
+                                                        inflate=inflate):
+                if fastx_out is not None:
+                    self.fastx_writer.write(chunk)                                                      # longQC.py:302-303
+                results.append(self.add_resident(chunk, trim=trim))
+                if trim and not isinstance(trim, FastqWriter):
+                    self.trimmed_chunks.append(self.trimmed)
+        except BaseException:
+            _close_writers(writers, quiet=True)                    # (the loop's error is the one to report)
+            raise
+        _close_writers(writers)
         return results
 
     def coverage(self, s_reads=None, short_threshold: Optional[int] = None, out: Optional[str] = None, exclude_seqs=None, chunks=None):

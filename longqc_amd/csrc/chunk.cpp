@@ -38,7 +38,7 @@ void lq_chunk_ready(lqchunk &c)
 	c.d_off.ensure(((size_t)c.n + 1) * 8);
 	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)c.n + 1) * 8, hipMemcpyHostToDevice, c.stream));
 	if (c.has_qual) {
-		c.qual.ensure((size_t)c.total + 16);
+		c.qual.ensure((size_t)c.total + LQ_GATHER_SRC_PAD);       // (k_fastq_format's second load)
 		if (c.total) LQ_HIP_CHECK(hipMemcpyAsync(c.qual.p, c.h_qual, (size_t)c.total, hipMemcpyHostToDevice, c.stream));
 	}
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // the caller's buffers are free again
@@ -84,7 +84,7 @@ void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std
 	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
 	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
 	const u64 words = (total + 15) / 16 * 16;
-	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + 16); c.d_off.ensure(((size_t)n + 1) * 8);
+	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + LQ_GATHER_SRC_PAD); c.d_off.ensure(((size_t)n + 1) * 8);
 	LQ_HIP_CHECK(hipMemsetAsync(c.seq.as<u8>() + words, 0, (size_t)(alloc - words), c.stream));
 	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
 	gather_launch(c, raw, sseg, c.seq.as<u8>(), upper, bam ? 1 : 0);

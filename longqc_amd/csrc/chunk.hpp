@@ -1,6 +1,6 @@
 // longqc_amd/csrc/chunk.hpp -- a chunk of reads resident on the device (lqchunk of include/lqcov.h): the bases, the offsets and, if
-// given, the qualities go up once; the low-complexity scan (dust.cpp), the adapter search (adapt.cpp), the GC counts (gc.cpp) and
-// the packing for the coverage engine (chunk.cpp) run on those buffers.  The buffer-level entry points lqsdust_reads,
+// given, the qualities go up once; the low-complexity scan (dust.cpp), the adapter search (adapt.cpp), the GC counts (gc.cpp), the
+// packing for the coverage engine (chunk.cpp) and the FASTQ writer (writer.cpp) run on those buffers.  The buffer-level entry points lqsdust_reads,
 // lqadapt_reads and lqgc_reads are the same steps on a chunk that lives for one call.
 #pragma once
 #include "lq_cabi.hpp"
@@ -32,6 +32,7 @@ struct lqchunk {
 	DBuf draw_off, gc, pos, win, kept;                        // GC counts
 	DBuf coff, tile_read, codes, amb, flags;                  // packed form
 	DBuf gseg, gtile;                                         // k_chunk_gather's segments and work list
+	DBuf fq_names, fq_noff, fq_be, fq_rec, fq_tile, fq_text;  // k_fastq_format's names and tables (writer.cpp), lqchunk_fastq's text
 	std::vector<u64> h_coff;                                  // packed chunks before read i
 	u64 n_chunks = 0; bool packed = false;
 	~lqchunk() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }

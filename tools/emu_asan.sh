@@ -4,7 +4,7 @@
 #   bash tools/emu_asan.sh [pytest args, default: the whole emulator suite]
 cd "$(dirname "$0")/.."
 OUT=${TMPDIR:-/tmp}/liblqcov_emu_asan.so
-SRCS="engine.cpp api.cpp dust.cpp adapt.cpp gc.cpp chunk.cpp reader.cpp"      # (longqc_amd/csrc/Makefile's SRCS)
+SRCS="engine.cpp api.cpp dust.cpp adapt.cpp gc.cpp chunk.cpp reader.cpp writer.cpp"      # (longqc_amd/csrc/Makefile's SRCS)
 ( cd longqc_amd/csrc && g++ -DLQ_EMU -include ../../tests/emu/hipemu.hpp -DLQ_EXACT_ALLOC -O1 -g -fsanitize=address -fno-omit-frame-pointer -std=c++17 -fPIC \
     -Wno-unused-function -Wno-unknown-pragmas $SRCS -shared -o "$OUT" -lz ) || exit 1
 # (libstdc++ preloaded too: the sanitizer's __cxa_throw interceptor needs it at start-up, and the tests of refused inputs throw;
