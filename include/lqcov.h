@@ -466,6 +466,39 @@ typedef struct lqinflate_stats {
 int  lqreader_inflate_stats(const lqreader *r, lqinflate_stats *stats);
 int  lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t span_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                     lqinflate_stats *stats);
+/* The record scan on the device, opt-in: lqreader_parse(r, LQREADER_PARSE_DEVICE) -- before the first lqreader_next,
+ * LQCOV_E_STATE afterwards; the default is LQREADER_PARSE_HOST, or what the environment variable LQREADER_PARSE ("device") says when
+ * the reader is opened; a BAM reader accepts the mode and ignores it.  Every piece of the file is then uploaded as it is read (with
+ * lqreader_inflate's device mode it is there already), k_fx_* find the records of the piece there and write the segment lists that
+ * k_chunk_gather reads; the host gets 16 bytes per record (where the name is, its length, the sequence's length, whether there is a
+ * quality string), copies the names out of the piece and applies the chunk rule.  The device answers only for records it can vouch
+ * for: the header character is a line's first byte, no sequence or quality line is exactly "\r" and no empty line follows one that
+ * ends in "\r\r", the record is complete inside the piece whatever follows it (FASTQ: the quality string reaches the sequence's
+ * length exactly, at the end of a line that has its line break; FASTA: the next header's first byte is there), fewer than 2^31
+ * bases.  Every other record, and everything at the end of the file, is the host parser's as before; chunks, borders, counts,
+ * names and errors are the host mode's.  lqreader_parse_stats says what happened so far.
+ * lqfx_scan is the array-level call: bytes[0 .. n) on the host, a parser that stands at start_pos with kseq's last_char (0, '@' or
+ * '>': that header character is bytes[start_pos - 1]).  rows: 4 words per vouched record (name offset, name length, sequence
+ * length, flags: bit 0 a quality string), sseg / qseg: (src, dst) pairs as k_chunk_gather takes them, src an offset into bytes (or
+ * all ones: no quality string, '!'), dst the place in the concatenated sequences of the vouched records.  The vouched records are
+ * the first *n_rows records kseq reads from that state; (*resume_pos, *resume_last_char) is the state behind them.  A start that is
+ * not a line's first byte gives no rows.  LQCOV_E_ARG: null buffers, tables smaller than the result, a last_char that bytes does not
+ * hold (the message: lqreader_last_error(NULL)). */
+#define LQREADER_PARSE_HOST   0
+#define LQREADER_PARSE_DEVICE 1
+typedef struct lqparse_stats {
+	uint64_t pieces;             /* reads of the file that brought bytes */
+	uint64_t scans;              /* scans run on the device */
+	uint64_t records_device;     /* records the device vouched for */
+	uint64_t records_host;       /* records the host parser made */
+	uint64_t lines;              /* lines the scans saw */
+	uint64_t fallbacks;          /* scans that stopped in front of a complete record of their range */
+} lqparse_stats;
+int  lqreader_parse(lqreader *r, int mode);
+int  lqreader_parse_stats(const lqreader *r, lqparse_stats *stats);
+int  lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, int last_char, uint32_t *rows, uint64_t n_rows_cap,
+               uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg,
+               uint64_t *resume_pos, int *resume_last_char);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 /* ---- the chunk loop's files: trimmed reads (longQC.py:345-346) and the FASTQ a BAM file is converted to (:302-303) ------------------ */

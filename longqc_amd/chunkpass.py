@@ -52,6 +52,9 @@ def _lib(lib=None):
             "lqinflate_blocks": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P, P, P, P]),
             "lqinflate_gzip": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, C.c_uint64, P, P]),
             "lqreader_inflate_stats": (C.c_int, [H, P]),
+            "lqreader_parse": (C.c_int, [H, C.c_int]),
+            "lqreader_parse_stats": (C.c_int, [H, P]),
+            "lqfx_scan": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint64, C.c_int, P, C.c_uint64, P, P, C.c_uint64, P, P, P, P, P]),
             "lqchunk_fastq": (C.c_int, [H, C.c_char_p, P, P, P, P, C.c_uint64, P]),
             "lqfastq_open": (H, [C.c_char_p, C.c_int, C.c_uint64]),
             "lqfastq_write": (C.c_int, [H, H, C.c_char_p, P, P, P, P]),
@@ -148,6 +151,38 @@ def inflate_gzip(data, span_bytes: Optional[int] = None, device: int = 0, lib=No
     if rc != 0:
         raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
     return out[:n.value].tobytes(), _stats_dict(st)
+
+
+PARSE_MODES = {"host": 0, "device": 1}
+PARSE_STATS = ("pieces", "scans", "records_device", "records_host", "lines", "fallbacks")
+GATHER_FILL = 0xffffffffffffffff                                    # src of a quality segment without source bytes ('!')
+
+
+def parse_mode(parse):
+    """"host" | "device" | None (the environment variable LQREADER_PARSE, "host" without it) -> the mode's name"""
+    mode = os.environ.get("LQREADER_PARSE", "host") if parse is None else parse
+    if mode not in PARSE_MODES:
+        raise ValueError("parse must be 'host' or 'device', not %r" % (mode,))
+    return mode
+
+
+def scan_records(data, start_pos: int = 0, last_char: int = 0, device: int = 0, lib=None):
+    """The record scan of the reader's device mode over bytes in memory (lqfx_scan: k_fx_lines, k_fx_candidates, k_fx_jump, k_fx_emit).
+    A kseq parser stands at data[start_pos] with last_char (0, or ord("@") / ord(">"): the header character data[start_pos - 1] has
+    been consumed).  -> (rows uint32[n, 4]: name offset, name length, sequence length, flags (bit 0: a quality string) of every
+    record the device vouches for, in file order; sseg, qseg uint64[k, 2]: (src, dst) of every line of the sequences / quality
+    strings that gives bytes, src GATHER_FILL for a record without qualities; resume = (pos, last_char) behind the last row)"""
+    lib = _lib(lib)
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = buf.shape[0]
+    cap = n // 2 + 2
+    rows, sseg, qseg = np.zeros((cap, 4), np.uint32), np.zeros((cap, 2), np.uint64), np.zeros((cap, 2), np.uint64)
+    n_rows, n_s, n_q, r_pos, r_lc = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+    rc = lib.lqfx_scan(device, buf.ctypes.data if n else None, n, int(start_pos), int(last_char), rows.ctypes.data, cap, sseg.ctypes.data,
+                       qseg.ctypes.data, cap, C.byref(n_rows), C.byref(n_s), C.byref(n_q), C.byref(r_pos), C.byref(r_lc))
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return rows[:n_rows.value].copy(), sseg[:n_s.value].copy(), qseg[:n_q.value].copy(), (r_pos.value, r_lc.value)
 
 
 class ReadChunk:
@@ -321,12 +356,16 @@ class FileChunks:
     inflate="device": the BGZF blocks of a BAM file -- and of a bgzip FASTA/FASTQ, which otherwise is gzread's -- are inflated on the
     device (k_bgzf_inflate); "host": the thread pool and gzread; None: what the environment variable LQREADER_INFLATE says, "host"
     without it.  The chunks are the same.  A gzip file that is not BGZF is inflated in device mode by speculative spans (k_gz_*; the span
-    length: LQREADER_GZ_SPAN_BYTES); inflate_stats (a dict of INFLATE_STATS) says after iteration what that took."""
+    length: LQREADER_GZ_SPAN_BYTES); inflate_stats (a dict of INFLATE_STATS) says after iteration what that took.
+    parse="device": the records of a FASTA/FASTQ file are found on the device (k_fx_*, lqreader_parse) wherever it vouches for them,
+    by the host parser elsewhere; "host": by the host parser; None: the environment variable LQREADER_PARSE, "host" without it.  The
+    chunks are the same; parse_stats (a dict of PARSE_STATS) says after iteration who found what.  A BAM file ignores the mode."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
-                 lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None):
+                 lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None, parse: Optional[str] = None):
         self.lib = _lib(lib)
         self.inflate = inflate_mode(inflate)
+        self.parse, self.parse_stats = parse_mode(parse), dict.fromkeys(PARSE_STATS, 0)
         self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
         self.is_sequel, self.format, self.inflate_stats = is_sequel, None, _stats_dict([0] * len(INFLATE_STATS))
         self.chunk_size = max(0, int(math.ceil(chunk_size)))        # size >= chunk_size for an integer size
@@ -340,7 +379,8 @@ class FileChunks:
         chunk = None
         try:
             self.format = lib.lqreader_format(r)
-            for rc in (lib.lqreader_bam_qualities(r, 1) if not self.is_sequel else 0, lib.lqreader_inflate(r, INFLATE_MODES[self.inflate])):
+            for rc in (lib.lqreader_bam_qualities(r, 1) if not self.is_sequel else 0, lib.lqreader_inflate(r, INFLATE_MODES[self.inflate]),
+                       lib.lqreader_parse(r, PARSE_MODES[self.parse])):
                 if rc != 0:
                     raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
             chunk = ReadChunk(None, device=self.device, lib=lib)
@@ -355,6 +395,9 @@ class FileChunks:
             st = (C.c_uint64 * len(INFLATE_STATS))()
             if lib.lqreader_inflate_stats(r, st) == 0:
                 self.inflate_stats = _stats_dict(st)
+            ps = (C.c_uint64 * len(PARSE_STATS))()
+            if lib.lqreader_parse_stats(r, ps) == 0:
+                self.parse_stats = dict(zip(PARSE_STATS, (int(w) for w in ps)))
             lib.lqreader_close(r)
             if chunk is not None:
                 chunk.close()
@@ -521,8 +564,8 @@ class SampleQCPass:
         return result
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
-                 is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None):
-        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate:
+                 is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None):
+        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse:
         FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
         trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
         appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
@@ -542,7 +585,7 @@ class SampleQCPass:
                 self.fastx_writer = FastqWriter(fastx_out, device=self.device, lib=self.lib)
                 writers.append(self.fastx_writer)
             for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
-                                                        inflate=inflate):
+                                                        inflate=inflate, parse=parse):
                 if fastx_out is not None:
                     self.fastx_writer.write(chunk)                                                      # longQC.py:302-303
                 results.append(self.add_resident(chunk, trim=trim))

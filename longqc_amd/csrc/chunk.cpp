@@ -9,6 +9,7 @@
 #include "kernels_chunk.hpp"
 #include "kernels_gather.hpp"
 #include "kernels_bam.hpp"
+#include "kernels_fxscan.hpp"
 #include <algorithm>
 #include <memory>
 
@@ -72,6 +73,49 @@ static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &seg
 	else LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, c.gseg.as<GatherSeg>(), c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
 	LQ_HIP_CHECK(hipGetLastError());
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (tile_seg dies here, and the two device lists serve the next launch)
+}
+
+// the same launch from segments that lie on the device (segs: room for one more entry): the work list is made there too
+static void gather_launch_dev(lqchunk &c, const u8 *raw, GatherSeg *segs, u64 n_segs, u8 *dst, bool upper)
+{
+	const u64 total = c.total;
+	if (!total) return;
+	const u64 n_tiles = (total + LQ_GATHER_TILE - 1) / LQ_GATHER_TILE;
+	if (n_segs > 0xffffffffULL) throw std::domain_error("more than 2^32-1 lines in one chunk");
+	if (!n_segs) throw std::logic_error("bases without segments");
+	const GatherSeg end = {0, total};
+	LQ_HIP_CHECK(hipMemcpyAsync(segs + n_segs, &end, sizeof(end), hipMemcpyHostToDevice, c.stream));
+	c.gtile.ensure((n_tiles + 1) * 4);
+	const u32 tgrid = (u32)std::min<u64>((n_tiles + 1 + LQ_FXSCAN_THREADS - 1) / LQ_FXSCAN_THREADS, LQ_FXSCAN_TILESEG_MAX_BLOCKS);
+	LQ_LAUNCH(k_fx_tileseg, tgrid, LQ_FXSCAN_THREADS, c.stream, (const GatherSeg*)segs, (u32)n_segs, n_tiles, LQ_GATHER_TILE, c.gtile.as<u32>());
+	const u32 grid = (u32)std::min<u64>(n_tiles, LQ_GATHER_MAX_BLOCKS);
+	LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, (const GatherSeg*)segs, (const u32*)c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
+	LQ_HIP_CHECK(hipGetLastError());
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (`end` dies here)
+}
+
+static void gather_begin(lqchunk &c, const std::vector<u64> &off)
+{
+	lq_cabi::select_device(c.device);
+	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
+	const u32 n = (u32)(off.size() - 1);
+	c.resident = false; c.packed = false; c.n_chunks = 0;
+	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
+	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
+	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
+	const u64 words = (total + 15) / 16 * 16;
+	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + LQ_GATHER_SRC_PAD); c.d_off.ensure(((size_t)n + 1) * 8);
+	LQ_HIP_CHECK(hipMemsetAsync(c.seq.as<u8>() + words, 0, (size_t)(alloc - words), c.stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+}
+
+void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper)
+{
+	gather_begin(c, off);
+	gather_launch_dev(c, raw, sseg, n_sseg, c.seq.as<u8>(), upper);
+	gather_launch_dev(c, raw, qseg, n_qseg, c.qual.as<u8>(), false);
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+	c.resident = true;
 }
 
 void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper, int bam)

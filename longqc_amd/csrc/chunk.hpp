@@ -48,6 +48,9 @@ void lq_chunk_ready(lqchunk &c);
 // as lq_chunk_set + lq_chunk_ready leave one that has qualities.  bam: 0 the raw bytes are a FASTA/FASTQ file's; 1 a BAM file's, sseg
 // names every read's packed sequence (kernels_bam.hpp) and qseg is LQ_GATHER_FILL throughout; 2 qseg names the reads' quality bytes.
 void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper, int bam = 0);
+// the same from segment lists that lie on the device already (the reader's device parse, kernels_fxscan.hpp): n_sseg / n_qseg entries
+// in destination order, room for one more behind each; the per-tile work list is made on the device (k_fx_tileseg)
+void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper);
 void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
 void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
 void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,

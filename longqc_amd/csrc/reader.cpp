@@ -31,6 +31,7 @@
 #include "bgzf.hpp"
 #include "kernels_inflate.hpp"
 #include "gzip.hpp"
+#include "fxscan.hpp"
 #include <zlib.h>
 #include <cstdlib>
 #include <memory>
@@ -96,6 +97,14 @@ struct lqreader {
 	std::vector<GatherSeg> sseg, qseg;
 	std::vector<char> names; std::vector<u64> name_off, off; std::vector<u32> lens;
 	Record rec;
+	// lqreader_parse(r, LQREADER_PARSE_DEVICE): the records of a piece are found on the device (fxscan.hpp) wherever it vouches for them
+	int parse_mode = LQREADER_PARSE_HOST;
+	bool bol = true;                                          // the byte at pos -- with last_char, the header character in front of it -- is a line's first
+	FxScan fx; lqparse_stats pst = {0, 0, 0, 0, 0, 0};
+	DBuf d_sseg, d_qseg; u64 n_dss = 0, n_dqs = 0;            // the chunk's segments on the device; sseg / qseg hold the host-parsed run behind them
+	u64 fx_cur = 0, fx_org = 0, fx_s = 0, fx_q = 0, fx_d = 0; // the last scan's rows from fx_cur on wait for a chunk: the piece byte its positions count from, record fx_cur's first segments and base
+	bool fresh = true, scanned = false, fb_counted = false, fb_at_end = false;      // bytes have come since the last scan; this piece has been scanned; that scan counts as a fallback / would if more records followed
+	u64 host_recs = 0, skip = 0, backoff = 0;                 // records parse_one has made since the last scan; scans that found nothing wait for 1, 2, 4 .. of them
 
 	~lqreader()
 	{
@@ -146,6 +155,8 @@ struct lqreader {
 	bool use_bgzf() const { return format == 1 || (bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE); }
 	bool use_gzdev() const { return format == 0 && gz && !bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE; }
 	bool on_device() const { return inflate_mode == LQREADER_INFLATE_DEVICE && (use_bgzf() || use_gzdev()); }
+	bool parse_dev() const { return parse_mode == LQREADER_PARSE_DEVICE && format == 0; }
+	bool mirror() const { return on_device() || parse_dev(); }            // the raw buffer holds buf[up_from .. fill), not only what has been parsed
 
 	// the first lqreader_next: the mode is final
 	void start()
@@ -239,6 +250,12 @@ struct lqreader {
 				if (got < 0) throw std::runtime_error("failed to open file '" + path + "': read error");
 			}
 			if (got == 0) { eof = true; break; }
+			if (mirror()) {                                       // (device parse: the bytes go up as they come)
+				const u64 ahead = fill - up_from;
+				raw_reserve(inf_stream, ahead + (u64)got, ahead);
+				LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used + ahead, buf + fill, (size_t)got, hipMemcpyHostToDevice, inf_stream));
+				LQ_HIP_CHECK(hipStreamSynchronize(inf_stream));
+			}
 			fill += (u64)got; file_pos += (u64)got;
 			return true;
 		}
@@ -402,7 +419,7 @@ struct lqreader {
 	void upload(hipStream_t stream)
 	{
 		const u64 len = pos - up_from;
-		if (on_device()) raw_used += len;                         // (the kernel has put them there)
+		if (mirror()) raw_used += len;                            // (they are there already)
 		else if (len) {
 			raw_reserve(stream, len);
 			LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used, buf + up_from, (size_t)len, hipMemcpyHostToDevice, stream));
@@ -419,7 +436,98 @@ struct lqreader {
 		if (pos) memmove(buf, buf + pos, (size_t)(fill - pos));
 		fill -= pos; pos = 0; up_from = 0;
 		if (fill == cap) set_piece(cap * 2);                      // a record longer than the piece
-		read_more();
+		more();
+	}
+
+	void more() { if (read_more()) { ++pst.pieces; fresh = true; scanned = false; } }
+
+	// ---- the device parse ----
+	static void seg_room(hipStream_t stream, DBuf &b, u64 have, u64 more)
+	{
+		const size_t need = (size_t)(have + more + 1) * sizeof(GatherSeg);
+		if (need <= b.cap) return;
+		DBuf nb;
+		nb.ensure(std::max(need, 2 * (size_t)have * sizeof(GatherSeg)));
+		if (have) {
+			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, b.p, (size_t)have * sizeof(GatherSeg), hipMemcpyDeviceToDevice, stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		}
+		b.swap(nb);
+		nb.release();
+	}
+
+	// the segments parse_one's records have made go behind the chunk's device lists
+	void flush_host_segs(hipStream_t stream)
+	{
+		if (sseg.empty() && qseg.empty()) return;
+		seg_room(stream, d_sseg, n_dss, sseg.size()); seg_room(stream, d_qseg, n_dqs, qseg.size());
+		if (!sseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_sseg.as<GatherSeg>() + n_dss, sseg.data(), sseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
+		if (!qseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_qseg.as<GatherSeg>() + n_dqs, qseg.data(), qseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		n_dss += sseg.size(); n_dqs += qseg.size();
+		sseg.clear(); qseg.clear();
+	}
+
+	// the scan's records fx_cur .. e have joined the chunk, their first base at dst0: their segments move behind the chunk's, device to device
+	void take_run(hipStream_t stream, u64 e, u64 dst0)
+	{
+		flush_host_segs(stream);
+		u64 s1 = 0, q1 = 0;
+		fx.seg_start(stream, e, &s1, &q1);
+		const u64 ns = s1 - fx_s, nq = q1 - fx_q;
+		// a byte of the scan lies at fx_org + its position in the piece, and a byte of the piece at raw_used - up_from + its place in the raw bytes
+		const u64 src_add = raw_used + fx_org - up_from, dst_add = dst0 - fx_d;
+		seg_room(stream, d_sseg, n_dss, ns); seg_room(stream, d_qseg, n_dqs, nq);
+		const auto grid = [](u64 n) { return (u32)std::min<u64>((n + LQ_FXSCAN_THREADS - 1) / LQ_FXSCAN_THREADS, LQ_FXSCAN_MAX_BLOCKS); };
+		if (ns) LQ_LAUNCH(k_fx_rebase, grid(ns), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.sseg.as<GatherSeg>() + fx_s, ns, src_add, dst_add, d_sseg.as<GatherSeg>() + n_dss);
+		if (nq) LQ_LAUNCH(k_fx_rebase, grid(nq), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.qseg.as<GatherSeg>() + fx_q, nq, src_add, dst_add, d_qseg.as<GatherSeg>() + n_dqs);
+		LQ_HIP_CHECK(hipGetLastError());
+		n_dss += ns; n_dqs += nq; fx_s = s1; fx_q = q1;
+	}
+
+	// the scan over buf[pos .. fill) if the parser stands at a clean start and the range has not been scanned from here; true: there are rows
+	bool scan(hipStream_t stream)
+	{
+		if (!bol || pos >= fill) return false;
+		if (!fresh && !(host_recs && !skip)) return false;
+		fresh = false; host_recs = 0;
+		fx_org = up_from; fx_cur = 0; fx_s = fx_q = fx_d = 0;
+		fx.run(stream, raw.as<u8>() + raw_used, fill - up_from, pos - up_from, last_char);
+		if (!fx.n_lines) return false;
+		++pst.scans; pst.lines += fx.n_lines;
+		if (fx.n_rows && fb_at_end) ++pst.fallbacks;              // (the scan before stopped in front of these)
+		scanned = true; fb_counted = fb_at_end = false;
+		if (!fx.n_rows) { backoff = backoff ? std::min<u64>(backoff * 2, 1u << 20) : 1; skip = backoff; return false; }
+		backoff = skip = 0;
+		return true;
+	}
+
+	// the waiting rows join the chunk until the chunk rule ends it (true) or they are used up
+	bool take_rows(hipStream_t stream, u64 &size)
+	{
+		const u64 dst0 = off.back();
+		bool ended = false;
+		while (fx_cur < fx.n_rows && !ended) {
+			const FxRow &w = fx.h_rows[fx_cur];
+			if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
+			const u8 *nm = buf + fx_org + w.name_at;
+			for (u64 i = 0; i < w.name_len; ++i) if (nm[i] >= 0x80)
+				throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
+			names.insert(names.end(), nm, nm + w.name_len); names.push_back('\0');
+			name_off.push_back(names.size());
+			off.push_back(off.back() + w.seq_len);
+			lens.push_back(w.seq_len);
+			++n_seqs; n_bases += w.seq_len; ++pst.records_device;
+			++fx_cur;
+			size += 3 * overhead + w.name_len + 2 * (u64)w.seq_len;
+			ended = size >= chunk_size;
+		}
+		take_run(stream, fx_cur, dst0);
+		fx_d += off.back() - dst0;
+		if (fx_cur < fx.n_rows) { pos = fx_org + fx.h_rows[fx_cur].name_at - 1; last_char = 0; }
+		else { pos = fx_org + fx.resume_pos; last_char = fx.resume_last_char; }
+		bol = true;
+		return ended;
 	}
 
 	void add_record()
@@ -452,17 +560,32 @@ struct lqreader {
 		if (!started) start();
 		c.resident = false; c.packed = false; c.n_chunks = 0;
 		raw_used = 0; sseg.clear(); qseg.clear(); names.clear(); name_off.assign(1, 0); off.assign(1, 0); lens.clear();
-		if (!buf) { set_piece(piece_bytes()); read_more(); }
-		else if (on_device() && fill > up_from) {                 // what the piece still holds belongs to this chunk: the mirror starts anew
+		n_dss = n_dqs = 0;
+		if (!buf) { set_piece(piece_bytes()); more(); }
+		else if (mirror() && fill > up_from) {                 // what the piece still holds belongs to this chunk: the mirror starts anew
 			raw_reserve(c.stream, fill - up_from);
 			LQ_HIP_CHECK(hipMemcpyAsync(raw.p, buf + up_from, (size_t)(fill - up_from), hipMemcpyHostToDevice, c.stream));
 			LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
 		}
 		u64 size = 0; bool ended = false;
 		while (!over) {
+			if (parse_dev()) {
+				if (fx_cur < fx.n_rows || scan(c.stream)) {
+					if (take_rows(c.stream, size)) { ended = true; break; }
+					continue;
+				}
+			}
+			const u64 pos0 = pos;
 			const int st = format == 1 ? parse_bam_one() : parse_one();
+			if (st == REC) bol = true;
+			else if (pos != pos0) bol = buf[pos - 1] == '\n';
 			if (st == NEED_MORE) { refill(c.stream); continue; }
 			if (st == END) { over = true; break; }
+			if (parse_dev()) {
+				++pst.records_host; ++host_recs;
+				if (skip) --skip;
+				if (scanned && !fb_counted) { if (eof) fb_at_end = true; else { ++pst.fallbacks; fb_counted = true; } }
+			}
 			if (format == 0) {
 				if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
 				add_record();
@@ -470,9 +593,11 @@ struct lqreader {
 			size += 3 * overhead + rec.name_len + 2 * rec.seq_len;
 			if (size >= chunk_size) { ended = true; break; }
 		}
+		if (parse_dev()) flush_host_segs(c.stream);
 		upload(c.stream);
 		done = !ended;
-		lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
+		if (parse_dev()) lq_chunk_gather_dev(c, off, raw.as<u8>(), d_sseg.as<GatherSeg>(), n_dss, d_qseg.as<GatherSeg>(), n_dqs, upper);
+		else lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
 		const u32 n = c.n;
 		*n_out = n; *n_seqs_cum = n_seqs; *n_bases_cum = n_bases; *last = done ? 1 : 0;
 	}
@@ -498,6 +623,8 @@ lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int i
 		r->n_threads = n_threads <= 0 ? 16 : std::min(n_threads, 16);
 		const char *mode = getenv("LQREADER_INFLATE");
 		if (mode && !strcmp(mode, "device")) r->inflate_mode = LQREADER_INFLATE_DEVICE;
+		const char *pm = getenv("LQREADER_PARSE");
+		if (pm && !strcmp(pm, "device")) r->parse_mode = LQREADER_PARSE_DEVICE;
 		r->open_file();
 		return r.release();
 	} catch (const std::exception &e) { g_reader_open_error = e.what(); return nullptr; }
@@ -540,6 +667,55 @@ int lqreader_inflate(lqreader *r, int mode)
 	if (r->started) { r->err = "lqreader_inflate after the first lqreader_next"; return LQCOV_E_STATE; }
 	r->inflate_mode = mode;
 	return 0;
+}
+
+int lqreader_parse(lqreader *r, int mode)
+{
+	if (!r || (mode != LQREADER_PARSE_HOST && mode != LQREADER_PARSE_DEVICE)) return LQCOV_E_ARG;
+	if (r->started) { r->err = "lqreader_parse after the first lqreader_next"; return LQCOV_E_STATE; }
+	r->parse_mode = mode;
+	return 0;
+}
+
+int lqreader_parse_stats(const lqreader *r, lqparse_stats *stats)
+{
+	if (!r || !stats) return LQCOV_E_ARG;
+	*stats = r->pst;
+	return 0;
+}
+
+int lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, int last_char, uint32_t *rows, uint64_t n_rows_cap,
+              uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg,
+              uint64_t *resume_pos, int *resume_last_char)
+{
+	char msg[512] = {0};
+	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+		if (!n_rows || !n_sseg || !n_qseg || !resume_pos || !resume_last_char || (n && !bytes)) throw std::invalid_argument("null buffers");
+		if (start_pos > n || (last_char != 0 && last_char != '@' && last_char != '>')) throw std::invalid_argument("no parser state");
+		*n_rows = *n_sseg = *n_qseg = 0; *resume_pos = start_pos; *resume_last_char = last_char;
+		// a clean start: at the first byte of a line, or behind a header character that was one (anything else is the host parser's)
+		const uint64_t at = start_pos - (last_char ? 1 : 0);
+		if (last_char && (start_pos == 0 || bytes[start_pos - 1] != last_char)) throw std::invalid_argument("no parser state");
+		if ((at && bytes[at - 1] != '\n') || start_pos >= n) return;
+		lq_cabi::select_device(device);
+		hipStream_t stream = nullptr;
+		LQ_HIP_CHECK(hipStreamCreate(&stream));
+		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		DBuf d;
+		d.ensure((size_t)n + LQ_GATHER_SRC_PAD);
+		LQ_HIP_CHECK(hipMemcpyAsync(d.p, bytes, (size_t)n, hipMemcpyHostToDevice, stream));
+		FxScan fx;
+		fx.run(stream, d.as<u8>(), n, start_pos, last_char);
+		if (fx.n_rows > n_rows_cap || fx.n_sseg > seg_cap || fx.n_qseg > seg_cap) throw std::invalid_argument("the tables are smaller than the scan's result");
+		if (fx.n_rows && (!rows || (fx.n_sseg && !sseg) || (fx.n_qseg && !qseg))) throw std::invalid_argument("null buffers");
+		if (fx.n_rows) memcpy(rows, fx.h_rows.data(), (size_t)fx.n_rows * sizeof(FxRow));
+		if (fx.n_sseg) LQ_HIP_CHECK(hipMemcpyAsync(sseg, fx.sseg.p, (size_t)fx.n_sseg * sizeof(GatherSeg), hipMemcpyDeviceToHost, stream));
+		if (fx.n_qseg) LQ_HIP_CHECK(hipMemcpyAsync(qseg, fx.qseg.p, (size_t)fx.n_qseg * sizeof(GatherSeg), hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		*n_rows = fx.n_rows; *n_sseg = fx.n_sseg; *n_qseg = fx.n_qseg; *resume_pos = fx.resume_pos; *resume_last_char = fx.resume_last_char;
+	});
+	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
+	return rc;
 }
 
 int lqreader_inflate_stats(const lqreader *r, lqinflate_stats *stats)

@@ -10,8 +10,12 @@ process, wall time of copy + synchronize; under rocprofv3 its kernel is in the s
 (c) --inflate host,device: the same FASTQ as a plain .gz (zlib level 6, one member), FileChunks alone in each mode named -- gzread
 on one thread against the speculative spans of csrc/gzip.hpp -- alternated, one warm-up pass and --reps timed ones per mode, medians
 and the spread, the device mode's inflate_stats; the modes must count the same reads and bases.
+(d) --parse host,device: the record scan on the device (lqreader_parse, k_fx_*) against the host parser, alternated, one warm-up pass
+and --reps timed ones per mode, medians and the spread: the bare FileChunks loop and run_file on the one-line FASTQ, the bare loop on
+the same reads as FASTA wrapped at 60 columns and on the FASTQ as level-6 gzip with inflate="device"; parse_stats of the device mode.
 Usage: python tools/filechunks_time.py [--reads 500000] [--chunk-mb 512] [--nsample 5000] [--reps 3] [--workers 16] [--only loop|gather]
-       python tools/filechunks_time.py --reads 50000 --inflate host,device [--reps 3]"""
+       python tools/filechunks_time.py --reads 50000 --inflate host,device [--reps 3]
+       python tools/filechunks_time.py --reads 50000 --parse host,device [--reps 3]"""
 import argparse
 import dataclasses
 import json
@@ -124,6 +128,49 @@ def inflate_modes(path, cs, reps, modes):
     return out
 
 
+def parse_modes(path, cs, reps, modes, nsample, wdir):
+    import zlib
+    fa, gz = path[:-3] + ".fa", path + ".gz"
+    with open(path, "rb") as f, open(fa, "wb") as g:               # the same reads as FASTA wrapped at 60 columns
+        lines = f.read().split(b"\n")
+        for i in range(0, len(lines) - 3, 4):
+            s = lines[i + 1]
+            g.write(b">" + lines[i][1:] + b"\n" + b"".join(s[k:k + 60] + b"\n" for k in range(0, len(s), 60)))
+        del lines
+    c = zlib.compressobj(6, zlib.DEFLATED, 31)
+    with open(path, "rb") as f, open(gz, "wb") as g:
+        for block in iter(lambda: f.read(1 << 24), b""):
+            g.write(c.compress(block))
+        g.write(c.flush())
+    out = {}
+    cases = (("fastq", path, {}), ("fasta_w60", fa, {}), ("fastq_gz_inflate_device", gz, {"inflate": "device"}))
+    for label, p, kw in cases:
+        runs, counts, stats = {m: [] for m in modes}, {}, {}
+        for it in range(reps + 1):                                  # alternated; the first pass of every mode is the warm-up
+            for m in modes:
+                fc = chunkpass.FileChunks(p, chunk_size=cs, parse=m, **kw)
+                t = time.perf_counter()
+                tot = [(ns, nb) for _, ns, nb in fc][-1]
+                if it:
+                    runs[m].append({"wall_s": time.perf_counter() - t})
+                counts[m], stats[m] = tot, fc.parse_stats
+        out[label] = {"file_bytes": os.path.getsize(p), "same_counts": len(set(counts.values())) == 1,
+                      "modes": {m: dict(summary(runs[m]), reads_bases=counts[m], parse_stats=stats[m]) for m in modes}}
+    runs, outs = {m: [] for m in modes}, {}
+    for it in range(reps + 1):
+        for m in modes:
+            t = time.perf_counter()
+            sp = chunkpass.SampleQCPass(wdir, PRESET, adp5=ADP5, adp3=ADP3, nsample=nsample, suffix=m)
+            sp.run_file(path, chunk_size=cs, parse=m)
+            sp.mask.close_pool()
+            if it:
+                runs[m].append({"wall_s": time.perf_counter() - t})
+            outs[m] = (open(sp.mask.get_outfile_path()).read(), sp.s_reads, sp.chunk_n)
+            sp.close()
+    out["run_file_fastq"] = {"same_results": len({repr(v) for v in outs.values()}) == 1, "modes": {m: summary(runs[m]) for m in modes}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=500000)
@@ -133,6 +180,7 @@ def main():
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--only", choices=("loop", "gather"), default=None)
     ap.add_argument("--inflate", default=None, help="host,device: time FileChunks on the file as a plain .gz in these modes, and nothing else")
+    ap.add_argument("--parse", default=None, help="host,device: time FileChunks and run_file with the record scan in these modes, and nothing else")
     a = ap.parse_args()
     cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
     cs = int(a.chunk_mb * 1024 ** 2)
@@ -152,6 +200,9 @@ def main():
         if a.inflate:
             res["metric"] = "seconds from the gzip FASTQ file to its chunks on the device"
             res["inflate"] = inflate_modes(path, cs, a.reps, a.inflate.split(","))
+        elif a.parse:
+            res["metric"] = "seconds from the file to its chunks on the device, by parse mode"
+            res["parse"] = parse_modes(path, cs, a.reps, a.parse.split(","), a.nsample, d)
         elif a.only != "gather":
             news, olds, same = [], [], True
             for _ in range(a.reps):                                 # alternated
@@ -161,7 +212,7 @@ def main():
                 same = same and o_new == o_old
             res.update(run_file=summary(news), python_reader_and_add_chunk=summary(olds), same_results=same, reps=a.reps, chunks=o_new[2])
             res["value"] = res["run_file"]["wall_s"]["median"]
-        if a.only != "loop" and not a.inflate:
+        if a.only != "loop" and not a.inflate and not a.parse:
             res["gather"] = gather_only(path, cs, a.reps, n_bases)
     print(json.dumps(res))
     if os.environ.get("OUT"):

@@ -7,7 +7,11 @@ records -- count, bases, and the two digests of names+sequences and of qualities
 strategy and flush points, as one or several members, some with a damaged byte, a cut end or bytes behind the last member; each is
 read by FileChunks in host mode (gzread) and in device mode (speculative spans, csrc/gzip.hpp) at a random span length, and the
 records, the counts and the error must be the same.
-    python tools/fuzz_reader.py --inflate device [--n 300] [--seed 1]        (the emulator build, or the GPU's with --lib)"""
+    python tools/fuzz_reader.py --inflate device [--n 300] [--seed 1]        (the emulator build, or the GPU's with --lib)
+--parse device: the token soup and the damaged records of the default mode, each read by FileChunks with parse="host" and with
+parse="device" (the record scan k_fx_*, csrc/kernels_fxscan.hpp) at a random piece length and chunk size: the chunks, names, records and
+the error must be the same; and chunkpass.scan_records' rows must be a prefix of the records the host parser reads.
+    python tools/fuzz_reader.py --parse device [--n 2000] [--seed 1]         (the emulator build, or the GPU's with --lib)"""
 import argparse
 import ctypes as C
 import os
@@ -82,15 +86,81 @@ def gzip_cases(lib, n, seed):
     return 1 if bad else 0
 
 
+def soup(rng, toks):
+    kind = rng.integers(0, 3)
+    if kind == 0:                           # token soup
+        return b"".join(toks[i] for i in rng.integers(0, len(toks), size=int(rng.integers(0, 60))))
+    recs = []                               # mostly well-formed records with a few damaged bytes
+    for r in range(int(rng.integers(1, 8))):
+        L = int(rng.integers(0, 40))
+        s = bytes(rng.choice(list(b"ACGTN"), size=L).astype(np.uint8)) if L else b""
+        eol = b"\r\n" if rng.random() < 0.2 else b"\n"
+        w = int(rng.integers(1, 30))
+        wrapped = rng.random() < 0.5 and L
+        if rng.random() < 0.5:
+            recs.append(b">r%d c" % r + eol + (eol.join(s[i:i + w] for i in range(0, len(s), w)) if wrapped else s) + eol)
+        else:
+            q = bytes(rng.integers(33, 74, size=L).astype(np.uint8)) if L else b""   # (qualities may hold '@', '>' and '+')
+            if wrapped:
+                s, q = eol.join(s[i:i + w] for i in range(0, L, w)), eol.join(q[i:i + w + 1] for i in range(0, L, w + 1))
+            recs.append(b"@r%d" % r + eol + s + eol + b"+" + eol + q + eol)
+    data = bytearray(b"".join(recs))
+    for _ in range(int(rng.integers(0, 3)) if kind == 2 else 0):
+        if data:
+            data[int(rng.integers(0, len(data)))] = int(rng.choice(list(b">@+\n\r A!")))
+    if rng.random() < 0.2 and data:
+        data = data[:int(rng.integers(0, len(data)))]      # truncated
+    return bytes(data)
+
+
+def parse_cases(lib, n, seed):
+    from longqc_amd import api, chunkpass
+    rng = np.random.default_rng(seed)
+    toks = [b">", b"@", b"+", b"\n", b"\n", b"\n", b"\r\n", b"\r", b"\r\r\n", b" ", b"\t", b"ACGT", b"acgtnN", b"U", b"!!!!", b"IIII", b"@@", b">>", b"+\n", b"name", b"x y", b""]
+
+    def read(path, mode, cs):
+        try:
+            fc = chunkpass.FileChunks(path, chunk_size=cs, lib=lib, str_overhead=49, parse=mode)
+            return [(ch.records(), list(ch.names), ns, nb) for ch, ns, nb in fc], None
+        except api.LqcovError as e:
+            return None, (e.code, str(e))
+
+    bad, vouched, total = 0, 0, 0
+    with tempfile.TemporaryDirectory() as d:
+        fn = os.path.join(d, "f.txt")
+        for it in range(n):
+            data = soup(rng, toks)
+            open(fn, "wb").write(data)
+            os.environ["LQREADER_PIECE_BYTES"] = str(rng.choice((16, 40, 100, 1 << 20)))
+            cs = int(rng.choice((1 << 40, 1, 300)))
+            host, dev = read(fn, "host", cs), read(fn, "device", cs)
+            ok = host == dev
+            if ok and host[0] is not None:
+                names = [x for c in host[0] for x in c[1]]
+                rows = chunkpass.scan_records(data, lib=lib)[0]
+                ok = [data[a:a + l].decode("ascii", "replace") for a, l, _, _ in rows.tolist()] == names[:rows.shape[0]]
+                vouched += rows.shape[0]; total += len(names)
+            if not ok:
+                bad += 1
+                print("case %d differs (piece %s, chunk size %d): %r\n  host %s\n  device %s" % (it, os.environ["LQREADER_PIECE_BYTES"], cs, data, host, dev))
+                if bad >= 5:
+                    break
+    print("%d inputs, %d on which the host and the device parse disagree; the device vouched for %d of %d records" % (it + 1, bad, vouched, total))
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=20000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
     ap.add_argument("--inflate", choices=("host", "device"), default="host")
+    ap.add_argument("--parse", choices=("host", "device"), default="host")
     args = ap.parse_args()
     from longqc_amd import api
     lib = api.load_library(args.lib)
+    if args.parse == "device":
+        sys.exit(parse_cases(lib, args.n if args.n != 20000 else 2000, args.seed))
     if args.inflate == "device":
         sys.exit(gzip_cases(lib, args.n if args.n != 20000 else 300, args.seed))
     rng = np.random.default_rng(args.seed)
