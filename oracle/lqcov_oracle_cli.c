@@ -7,7 +7,7 @@
  *   lqcov_oracle sketch [opts] <reads>
  *   lqcov_oracle index  [opts] <targets>
  *   lqcov_oracle chains [opts] <targets> <queries>
- *   opts: -k -w -H -I -g -n -m -p -q -s -a -l -c -r -Y -X -f  --stable-sort --grouped --ties-reversed --ties-hashed
+ *   opts: -k -w -H -I -g -n -m -p -q -s -a -l -c -r -Y -X -f  --stable-sort --grouped --ties-reversed --ties-hashed  --bw N
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -53,6 +53,10 @@ int main(int argc, char **argv)
 			else if (!strcmp(a, "--ties-reversed")) p.sort_mode = 2, p.chain_mode = 1;
 			else if (!strcmp(a, "--ties-hashed")) p.sort_mode = 3, p.chain_mode = 1;
 			else if (!strcmp(a, "--filter")) p.filter_flag = 1;
+			else if (!strcmp(a, "--bw")) {                      /* not an option of the reference (map.c:20 fixes it at 500): the engine's ABI exposes it */
+				if (i + 1 >= argc) { fprintf(stderr, "option --bw needs a value\n"); return 2; }
+				p.bw = atoi(argv[++i]);
+			}
 			else { fprintf(stderr, "unknown option %s\n", a); return 2; }
 		} else if (a[0] == '-' && a[1]) {
 			int j;

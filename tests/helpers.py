@@ -86,3 +86,41 @@ def read_fastx(path):
         else:
             i += 1
     return names, seqs, (quals if all(q is not None for q in quals) else None)
+
+
+def limits_dataset(d, seed=0, glen=12000, n_targets=20, n_queries=5, err=0.02, n_noisy=3, n_indel=10):
+    """the seeded repeat-rich set of tests/test_chain_limits.py (its docstring has the recipe), written to d -> (targets path, queries path)"""
+    from longqc_amd import synth
+    rng = np.random.default_rng(4100 + seed)
+    A, COMP = synth._ACGT, synth._COMP
+    g = A[rng.integers(0, 4, size=glen, dtype=np.uint8)]
+    for at in range(500, glen - 3000, 2000):                    # tandem repeats
+        u = int(rng.integers(40, 300)); c = min(int(rng.integers(4, 10)), 1800 // u)
+        unit = g[at:at + u].copy()
+        for i in range(c):
+            g[at + i * u:at + (i + 1) * u] = synth._mutate(unit, rng, 0.01, (1, 0, 0))[:u]
+    seg = g[1200:1700].copy()                                   # three dispersed copies of one segment
+    g[5100:5600] = seg
+    g[glen - 1500:glen - 1000] = COMP[seg[::-1]]
+
+    def cut(st, L, e=err, flip=None):
+        s = g[st:st + L]
+        if flip if flip is not None else rng.random() < 0.5:
+            s = COMP[s[::-1]]
+        return synth._mutate(s, rng, e, (3, 3, 4))
+
+    tseqs = [cut(int(rng.integers(0, glen - 4000)), int(rng.integers(1000, 4000))) for _ in range(n_targets - 1)]
+    tseqs.append(cut(3000, 6500, 0.005, False))                 # the long pair
+    qseqs = [cut(int(rng.integers(0, glen - 4000)), int(rng.integers(1500, 4000))) for _ in range(n_queries - 1)]
+    qseqs.append(cut(2800, 6800, 0.005, False))
+    for _ in range(n_noisy):                                    # sparse anchors: a predecessor exactly max_gap away can be the best one
+        qseqs.append(cut(int(rng.integers(0, glen - 4000)), int(rng.integers(2000, 3000)), 0.13))
+    for i in range(n_indel):                                    # exact copies of 400 bases with 20-24 more beyond a deletion of 70-97: two or three anchors 70-97 diagonals away
+        a, dele, tail = 3300 + 550 * i, 70 + 3 * i, 20 + i % 5
+        tseqs.append(np.concatenate([g[a:a + 400], g[a + 400 + dele:a + 400 + dele + tail]] if i % 2 == 0 else [g[a - dele - tail:a - dele], g[a:a + 400]]))
+
+    def readset(prefix, seqs):
+        return synth.ReadSet(["%s%03d" % (prefix, i) for i in range(len(seqs))], seqs, [(33 + rng.integers(3, 30, size=x.shape[0])).astype(np.uint8) for x in seqs])
+    tf, qf = os.path.join(str(d), "lim_all.fq"), os.path.join(str(d), "lim_sub.fq")
+    synth.write_fastq(tf, readset("t", tseqs)); synth.write_fastq(qf, readset("q", qseqs))
+    return tf, qf

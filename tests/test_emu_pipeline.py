@@ -102,9 +102,24 @@ def test_emulated_state_machine_only_adversarial(emu_lib, monkeypatch):
     test_emulated_sketch_halo_adversarial(emu_lib)
 
 
+def _oracle_sketch_equals(names, seqs, k, w, xy, off, what):
+    """the oracle's `sketch` dump of these reads (written as FASTA) against an engine's list; as in the fixture test the oracle
+    sketches read i with rid = i, the engine's queries all have rid 0"""
+    import tempfile
+    from longqc_amd import synth
+    with tempfile.TemporaryDirectory() as d:
+        fn = os.path.join(d, "x.fa")
+        synth.write_fastq(fn, synth.ReadSet(names, seqs, [None] * len(seqs)), fasta=True)
+        want = parse_sketch_dump(oracle_bind.dump("sketch", ["-k", str(k), "-w", str(w)], [fn]))
+    assert [nm for nm, _, _ in want] == list(names)
+    for i, (nm, ln, mm) in enumerate(want):
+        got = [(int(x), int(y)) for x, y in xy[int(off[i]):int(off[i + 1])]]
+        assert got == [(x, y & 0xffffffff) for x, y in mm], (what, nm)
+
+
 def test_emulated_data_parallel_sketch_fuzz(emu_lib, monkeypatch):
     """random reads with sparse Ns, AT stretches (palindromic k-mers), short-period repeats and tandem copies (ties), a
-    two-letter alphabet; random (k, w): the data-parallel kernel and the state machine give the same list"""
+    two-letter alphabet; random (k, w): the data-parallel kernel and the state machine give the same list, the oracle's"""
     A = np.frombuffer(b"ACGT", dtype=np.uint8)
     fixed = [(12, 5), (12, 10), (19, 5), (19, 10)]       # the windows k_sketch_dp_mask knows at compile time, 32- and 64-bit hashes
     for it in range(10 + len(fixed)):
@@ -137,6 +152,7 @@ def test_emulated_data_parallel_sketch_fuzz(emu_lib, monkeypatch):
             xy, off = eng.query_minimizers()
             res.append((np.array(xy).copy(), np.array(off).copy()))
             eng.close()
+        _oracle_sketch_equals(names, seqs, k, w, res[0][0], res[0][1], (it, k, w))   # (a rule all three kernels misread alike would pass the comparison below)
         for other in res[1:]:
             assert np.array_equal(res[0][0], other[0]) and np.array_equal(res[0][1], other[1]), (it, k, w)
 
@@ -145,7 +161,7 @@ def test_emulated_constant_k_sketch_fuzz(emu_lib, monkeypatch):
     """k_sketch_dp_fast (-k 12 with -w 5 / 10: k and w as constants, straight-line steps for threads without palindromes and ties,
     the literal rules for the others) against the state machine and against the general kernel (LQCOV_SKETCH_FAST=0): reads of
     several tiles with tandem repeats of short periods (tied minima inside a window), two- and three-letter alphabets, AT and
-    GC stretches (palindromes), Ns, reads that end inside and right after a tile"""
+    GC stretches (palindromes), Ns, reads that end inside and right after a tile; the first of the three against the oracle too"""
     A = np.frombuffer(b"ACGT", dtype=np.uint8)
     for it in range(12):
         rng = np.random.default_rng(700 + it)
@@ -181,6 +197,7 @@ def test_emulated_constant_k_sketch_fuzz(emu_lib, monkeypatch):
             xy, off = eng.query_minimizers()
             res.append((np.array(xy).copy(), np.array(off).copy()))
             eng.close()
+        _oracle_sketch_equals(names, seqs, 12, w, res[0][0], res[0][1], (it, w))
         for other in res[1:]:
             assert np.array_equal(res[0][0], other[0]) and np.array_equal(res[0][1], other[1]), (it, w)
 

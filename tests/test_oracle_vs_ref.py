@@ -8,7 +8,7 @@ import os
 import pytest
 
 from tests import oracle_bind
-from tests.helpers import GOLDEN, ONT
+from tests.helpers import GOLDEN, ONT, limits_dataset
 
 VARIANTS = {
     "ont": ONT,
@@ -47,6 +47,15 @@ def test_chains_intervals_counters(datasets):
     want = oracle_bind.ref_dump(["chains", "12", "5", "0", "4G", "40", "160", "160", tf, qf])
     got = oracle_bind.dump("chains", ["-k", "12", "-w", "5", "-m", "40", "-p", "160", "-q", "160", "-l", "0"], [tf, qf])
     assert got == want
+
+
+@pytest.mark.parametrize("name,flags", [("adv", ["-g", "300"]), ("adv", ["-s", "0"]), ("rr", ["-g", "300"]), ("rr", ["-s", "1"])], ids=lambda v: v if isinstance(v, str) else "".join(v))
+def test_table_identical_to_reference_at_gap_and_skip_limits(tmp_path, name, flags):
+    """-g / -s away from their defaults, on the two inputs of tests/test_chain_limits.py where they bite (its argv lines)"""
+    files = [os.path.join(GOLDEN, "adv_all.fa.gz"), os.path.join(GOLDEN, "adv_sub.fq.gz")] if name == "adv" else list(limits_dataset(tmp_path))
+    ref = oracle_bind.ref_table(ONT + flags + files)
+    assert oracle_bind.table(ONT + flags + files) == ref
+    assert oracle_bind.ref_table(ONT + files) != ref
 
 
 def test_klib_order_matters_stable_sort_is_not_exact(tmp_path):
