@@ -28,10 +28,8 @@ template <class F> static int guard(lqcov_handle *h, F &&f)
 	catch (const std::domain_error &e) { set_err(h, e.what()); return LQCOV_E_DOMAIN; }
 	catch (const std::logic_error &e) { set_err(h, e.what()); return LQCOV_E_STATE; }
 	catch (const std::ios_base::failure &e) { set_err(h, e.what()); return LQCOV_E_IO; }
-	catch (const std::runtime_error &e) {
-		set_err(h, e.what());
-		return strstr(e.what(), "failed to open") ? LQCOV_E_IO : LQCOV_E_DEVICE;
-	}
+	catch (const lq_io_error &e) { set_err(h, e.what()); return LQCOV_E_IO; }
+	catch (const std::runtime_error &e) { set_err(h, e.what()); return LQCOV_E_DEVICE; }
 	catch (const std::exception &e) { set_err(h, e.what()); return LQCOV_E_DEVICE; }
 }
 
@@ -434,7 +432,7 @@ int lqcov_write_table(lqcov_handle *h, const char *out_path)
 {
 	return guard(h, [&] {
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
-		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
+		if (!o) throw lq_open_error(out_path);
 		try { h->write_table(o); } catch (...) { if (out_path) fclose(o); throw; }
 		if (out_path) fclose(o); else fflush(o);
 	});
@@ -444,7 +442,7 @@ int lqcov_write_table_set(lqcov_handle *h, uint32_t set, const char *out_path)
 {
 	return guard(h, [&] {
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
-		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
+		if (!o) throw lq_open_error(out_path);
 		try { h->write_table_set(set, o); } catch (...) { if (out_path) fclose(o); throw; }
 		if (out_path) fclose(o); else fflush(o);
 	});
@@ -747,7 +745,7 @@ int lqcov_run_files_ex(lqcov_handle *h, const char *target_path, const char *que
 		if (!target_path) throw std::invalid_argument("no target");
 		if (!query_path && !dump_path) throw std::invalid_argument("neither a query file nor an index dump was asked for");
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
-		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
+		if (!o) throw lq_open_error(out_path);
 		FILE *e = err_path ? fopen(err_path, "a") : stderr;
 		try { h->run_files(target_path, query_path, o, e, dump_path); }
 		catch (...) { if (out_path) fclose(o); if (err_path && e) fclose(e); throw; }
@@ -784,7 +782,7 @@ int lqcov_run_files_sets(lqcov_handle *h, const char *target_path, uint32_t n_se
 			qs.paths.push_back(query_paths[s]); qs.med.push_back(med[s]); qs.good.push_back(good[s]);
 		}
 		FILE *e = err_path ? fopen(err_path, "a") : stderr;
-		if (!e) throw std::runtime_error(std::string("failed to open file '") + err_path + "'");
+		if (!e) throw lq_open_error(err_path);
 		struct Closer { std::vector<FILE *> fs; FILE *e; bool own_e; ~Closer() { for (FILE *f : fs) if (f) fclose(f); if (own_e && e) fclose(e); } } cl{{}, e, err_path != nullptr};
 		echo_params(e, h->P, target_path, query_paths[0]);
 		for (uint32_t s = 0; s < n_sets; ++s)
@@ -792,7 +790,7 @@ int lqcov_run_files_sets(lqcov_handle *h, const char *target_path, uint32_t n_se
 		fflush(e);
 		for (uint32_t s = 0; s < n_sets; ++s) {
 			FILE *o = fopen(out_paths[s], "w");
-			if (!o) throw std::runtime_error(std::string("failed to open file '") + out_paths[s] + "'");
+			if (!o) throw lq_open_error(out_paths[s]);
 			cl.fs.push_back(o); qs.outs.push_back(o);
 		}
 		h->run_files(target_path, nullptr, nullptr, e, nullptr, &qs);
@@ -803,7 +801,7 @@ int lqcov_part_dump(lqcov_handle *h, int part, const char *path, int append)
 {
 	return guard(h, [&] {
 		FILE *fp = fopen(path, append ? "ab" : "wb");
-		if (!fp) throw std::runtime_error(std::string("failed to open file '") + path + "'");
+		if (!fp) throw lq_open_error(path);
 		try { h->dump_part(h->part(part), fp); } catch (...) { fclose(fp); throw; }
 		fclose(fp);
 	});
@@ -815,7 +813,7 @@ int lqcov_part_load(lqcov_handle *h, const char *path, uint64_t *offset)
 	int rc = guard(h, [&] {
 		if (!offset) throw std::invalid_argument("null offset");
 		FILE *fp = fopen(path, "rb");
-		if (!fp) throw std::runtime_error(std::string("failed to open file '") + path + "'");
+		if (!fp) throw lq_open_error(path);
 		try {
 			if (fseeko(fp, (off_t)*offset, SEEK_SET) != 0) throw std::runtime_error("seek failed");
 			h->parts.emplace_back(new Part());

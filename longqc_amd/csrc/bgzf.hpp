@@ -8,7 +8,7 @@
 // the pool only checks the CRC32 of what came back, which vouches for the kernel and for the copy alike.  The errors are the same
 // three, for the same blocks.
 #pragma once
-#include "lq_common.hpp"
+#include "lq_cabi.hpp"
 #include <zlib.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -34,7 +34,7 @@ struct BgzfInflater {
 
 	[[noreturn]] static void fail(u64 at, const char *what)
 	{
-		throw std::runtime_error("BGZF block at file offset " + std::to_string(at) + ": " + what);
+		throw lq_file_error("BGZF block at file offset " + std::to_string(at) + ": " + what);
 	}
 
 	static u32 le32(const u8 *p) { return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
@@ -71,7 +71,7 @@ struct BgzfInflater {
 		win_at = next; win_len = keep; win_eof = false;
 		while (win_len < WINDOW) {
 			const ssize_t got = ::pread(fd, win.data() + win_len, (size_t)(WINDOW - win_len), (off_t)(win_at + win_len));
-			if (got < 0) throw std::runtime_error("read error");
+			if (got < 0) throw lq_file_error("read error");
 			if (got == 0) { win_eof = true; break; }
 			win_len += (u64)got;
 		}

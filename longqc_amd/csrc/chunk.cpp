@@ -120,17 +120,7 @@ void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw,
 
 void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper, int bam)
 {
-	lq_cabi::select_device(c.device);
-	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
-	const u32 n = (u32)(off.size() - 1);
-	c.resident = false; c.packed = false; c.n_chunks = 0;
-	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
-	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
-	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
-	const u64 words = (total + 15) / 16 * 16;
-	c.seq.ensure((size_t)alloc); c.qual.ensure((size_t)total + LQ_GATHER_SRC_PAD); c.d_off.ensure(((size_t)n + 1) * 8);
-	LQ_HIP_CHECK(hipMemsetAsync(c.seq.as<u8>() + words, 0, (size_t)(alloc - words), c.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+	gather_begin(c, off);
 	gather_launch(c, raw, sseg, c.seq.as<u8>(), upper, bam ? 1 : 0);
 	gather_launch(c, raw, qseg, c.qual.as<u8>(), false, bam == 2 ? 2 : 0);
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));

@@ -83,11 +83,11 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 	char err[512] = {0};
 	int rc = guarded(err, sizeof(err), [&] {
 		FILE *t = fopen(in, "rb");
-		if (!t) throw std::runtime_error(std::string("failed to open file '") + in + "'");
+		if (!t) throw lq_open_error(in);
 		fclose(t);
 		select_device(device);
 		FILE *o = out_path ? fopen(out_path, "w") : stdout;
-		if (!o) throw std::runtime_error(std::string("failed to open file '") + out_path + "'");
+		if (!o) throw lq_open_error(out_path);
 		struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); else if (f) fflush(f); } } oc{o, out_path != nullptr};
 		lqchunk D;                                              // one chunk object for every mini-batch: its buffers grow and stay
 		D.device = device;

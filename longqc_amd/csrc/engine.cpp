@@ -221,16 +221,10 @@ Part &lqcov_handle::part(int id)
 }
 
 // ---- read sets ------------------------------------------------------------------------------
+// a read set's or a lane's growing list: half as much again and 4096 bytes past what is needed now, from one plain hipMalloc
 static void grow_keep(DBuf &b, size_t old_bytes, size_t new_bytes, hipStream_t s)
 {
-	if (new_bytes <= b.cap) return;
-	void *np = nullptr;
-	size_t want = new_bytes + new_bytes / 2 + 4096;
-	LQ_HIP_CHECK(hipMalloc(&np, want));
-	if (old_bytes) LQ_HIP_CHECK(hipMemcpyAsync(np, b.p, old_bytes, hipMemcpyDeviceToDevice, s));
-	LQ_HIP_CHECK(hipStreamSynchronize(s));
-	if (b.p) { void *old = b.p; b.p = nullptr; DBuf tmp; tmp.p = old; tmp.cap = 1; tmp.pool_stream = b.pool_stream; }   // (freed the way it was allocated)
-	b.p = np; b.cap = want; b.pool_stream = nullptr;
+	b.grow(new_bytes, new_bytes + new_bytes / 2 + 4096, old_bytes, s, true);
 }
 
 // upload n reads (ASCII) and append them, 2-bit packed, to the set   (index.c:240-288 step 0)
@@ -2448,7 +2442,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 	i32 ik = 0, iw = 0, ihpc = 0;
 	{
 		FILE *t = fopen(target, "rb");
-		if (!t) throw std::runtime_error(std::string("failed to open file '") + target + "'");
+		if (!t) throw lq_open_error(target);
 		char magic[4]; u32 hdr[5];
 		if (fread(magic, 1, 4, t) == 4 && memcmp(magic, LQ_MMI_MAGIC, 4) == 0) {       // mm_idx_is_idx (index.c:481-498)
 			is_idx = true;
@@ -2508,7 +2502,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 	}
 	struct QueriesJoin { std::future<void> &f; ~QueriesJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } queries_join{queries_loaded};   // (never leave the task behind when something else throws)
 	FILE *dump = nullptr;
-	if (dump_path) { dump = fopen(dump_path, "wb"); if (!dump) throw std::runtime_error(std::string("failed to open file '") + dump_path + "'"); }
+	if (dump_path) { dump = fopen(dump_path, "wb"); if (!dump) throw lq_open_error(dump_path); }
 	struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } dump_closer{dump};
 	int n_parts = 0;
 	if (is_idx) {
@@ -2517,7 +2511,7 @@ int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FI
 			adopt_index_params(ik, iw, ihpc);
 		}
 		FILE *fi = fopen(target, "rb");
-		if (!fi) throw std::runtime_error(std::string("failed to open file '") + target + "'");
+		if (!fi) throw lq_open_error(target);
 		Closer fi_closer{fi};
 		for (;;) {
 			parts.emplace_back(new Part());

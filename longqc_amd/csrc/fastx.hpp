@@ -7,6 +7,7 @@
 //   * a truncated quality string ends the stream.
 // Reads go into one flat ReadBatch (bases, offsets, names) -- the layout the C ABI takes.
 #pragma once
+#include "lq_cabi.hpp"
 #include <zlib.h>
 #include <string>
 #include <vector>
@@ -88,7 +89,7 @@ public:
 	explicit FastxReader(const std::string &path) : buf_(1 << 20)
 	{
 		fp_ = gzopen(path.c_str(), "r");
-		if (!fp_) throw std::runtime_error("failed to open file '" + path + "'");
+		if (!fp_) throw lq_open_error(path);
 		gzbuffer(fp_, 1 << 20);
 	}
 	~FastxReader() { if (fp_) gzclose(fp_); }

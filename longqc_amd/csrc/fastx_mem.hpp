@@ -16,7 +16,7 @@
 // mapping (sequences of one line are not copied); 2-bit packing into the engine's layout (lq_pack_host's) happens in
 // parallel, read by read, straight into the buffers that are uploaded.
 #pragma once
-#include "lq_common.hpp"
+#include "lq_cabi.hpp"
 #include <string>
 #include <vector>
 #include <thread>
@@ -64,7 +64,7 @@ public:
 	{
 		close();
 		fd_ = ::open(path.c_str(), O_RDONLY);
-		if (fd_ < 0) throw std::runtime_error("failed to open file '" + path + "'");
+		if (fd_ < 0) throw lq_open_error(path);
 		struct stat st;
 		if (fstat(fd_, &st) != 0 || !S_ISREG(st.st_mode)) { ::close(fd_); fd_ = -1; return false; }
 		n_ = (u64)st.st_size;

@@ -25,7 +25,7 @@
 #include <unistd.h>
 #include <functional>
 
-struct GzipError : std::runtime_error { GzipError() : std::runtime_error("not a complete gzip stream") {} };
+struct GzipError : lq_file_error { GzipError() : lq_file_error("not a complete gzip stream") {} };
 
 struct GzipInflater {
 	// the input: a descriptor (not owned) or bytes in memory
@@ -72,7 +72,7 @@ struct GzipInflater {
 		u64 have = 0;
 		while (have < n) {
 			const ssize_t got = ::pread(fd, dst + have, (size_t)(n - have), (off_t)(off + have));
-			if (got < 0) throw std::runtime_error("read error");
+			if (got < 0) throw lq_file_error("read error");
 			if (got == 0) break;
 			have += (u64)got;
 		}

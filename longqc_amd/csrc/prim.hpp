@@ -113,6 +113,20 @@ struct DBuf {
 		LQ_HIP_CHECK(e);
 		cap = want;
 	}
+	// room for `need` bytes with the first `keep` bytes kept: if there is less, a new block -- ensure(want)'s, or with `plain` one
+	// hipMalloc of exactly `want` bytes, tried once (the engine's lists: they outlive a lane's arena, and the seed filter catches the
+	// failure) -- the kept bytes copied device to device on `stream`, and the old block freed the way it was allocated.  How far past
+	// `need` to grow is the caller's rule
+	void grow(size_t need, size_t want, size_t keep, hipStream_t stream, bool plain = false)
+	{
+		if (need <= cap) return;
+		DBuf nb; void *np = nullptr;
+		if (plain) { LQ_HIP_CHECK(hipMalloc(&np, want)); nb.p = np; nb.cap = want; }
+		else nb.ensure(want);
+		if (keep) LQ_HIP_CHECK(hipMemcpyAsync(nb.p, p, keep, hipMemcpyDeviceToDevice, stream));
+		if (keep || plain) LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		swap(nb);                                                  // (nb's destructor frees the old block)
+	}
 	void release()
 	{
 		if (in_arena) { p = nullptr; cap = 0; in_arena = false; return; }

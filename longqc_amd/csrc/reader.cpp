@@ -19,13 +19,13 @@
 // (4.1 BGZF, 4.2 the records); no file here was read or written by htslib.
 //
 // lqreader_inflate(r, LQREADER_INFLATE_DEVICE): the BGZF blocks are inflated by k_bgzf_inflate (kernels_inflate.hpp) instead.  Only the
-// compressed bytes go up; the kernel writes the inflated bytes into the chunk's raw device buffer where the piece's upload would have
-// put them, and they come back into the piece for the host to parse and to check their CRC32 -- the parsers and the gather kernels
-// are the same, the upload of the piece falls away.  The raw buffer then mirrors the piece from its first byte that is not part of
-// the chunk yet (up_from) to its last (fill), not only what has been parsed.  In that mode a BGZF file that is not BAM (bgzip
-// FASTA/FASTQ) is inflated the same way and parsed by the kseq grammar; gzread is not used for it.  A gzip file that is not BGZF
-// is inflated by speculative spans (gzip.hpp, kernels_gzip.hpp) under the same rules: the bytes land in the raw buffer, come back
-// into the piece, and what the file is or is not is what gzread says of it.
+// compressed bytes go up; the kernel writes into the chunk's raw device buffer where the piece's upload would have put the bytes, and
+// they come back into the piece for the host to parse and to check their CRC32.  The raw buffer then mirrors the piece from up_from to
+// fill.  A bgzip FASTA/FASTQ is inflated the same way, any other gzip file by speculative spans (gzip.hpp, kernels_gzip.hpp).
+//
+// The parts: a Source (pread, gzread, BGZF blocks or gzip spans, chosen once) fills the Piece; parse_one, parse_bam_one (BamHeader) or
+// DeviceParse (fxscan.hpp) finds the records, and each joins the chunk through ChunkParts::append_read: names, offsets, counts, the
+// chunk rule.  What a Source finds wrong with its file is an lq_file_error; read_more gives it the path (LQCOV_E_IO by type).
 #include "chunk.hpp"
 #include "fastx_mem.hpp"
 #include "bgzf.hpp"
@@ -66,78 +66,282 @@ struct InflateDev {
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	}
 };
+
+// ---- where the bytes come from ----
+// fill: bytes into dst[0 .. room) -> how many.  0 with `ended`: the file is over; 0 without: the next bytes want *need bytes of room.  How
+// much of the room one call fills is the source's own matter.  A read that fails, or a file that is not what it says it is, is an
+// lq_file_error.
+struct Source {
+	int fd = -1;                                              // closed with the source (gzread's stream owns its own)
+	bool ended = false;
+	bool in_mirror = false;                                   // fill puts the bytes into the chunk's raw device buffer as well
+	hipStream_t stream = nullptr;                             // the stream of the chunk that is being made
+	const lqinflate_stats *stats = nullptr;
+	virtual u64 fill(u8 *dst, u64 room, u64 *need) = 0;
+	virtual ~Source() { if (fd >= 0) ::close(fd); }
+};
+
+struct PlainSource : Source {
+	u64 at = 0;
+	explicit PlainSource(int f) { fd = f; }
+	u64 fill(u8 *dst, u64 room, u64 *) override
+	{
+		const ssize_t got = ::pread(fd, dst, (size_t)std::min<u64>(room, 1u << 30), (off_t)at);
+		if (got < 0) throw lq_file_error("read error");
+		ended = got == 0; at += (u64)got;
+		return (u64)got;
+	}
+};
+
+struct GzreadSource : Source {
+	gzFile gz;
+	explicit GzreadSource(gzFile g) : gz(g) { gzbuffer(gz, 1 << 20); }
+	~GzreadSource() { gzclose(gz); }
+	u64 fill(u8 *dst, u64 room, u64 *) override
+	{
+		const int got = gzread(gz, dst, (unsigned)std::min<u64>(room, 1u << 30));
+		if (got < 0) throw lq_file_error("not a complete gzip stream");
+		ended = got == 0;
+		return (u64)got;
+	}
+};
+
+struct BgzfSource : Source {                                  // whole blocks; the call that finds the file over brings nothing
+	BgzfInflater z;
+	BgzfSource(int f, int n_threads) { fd = z.fd = f; z.n_threads = n_threads; }
+	u64 fill(u8 *dst, u64 room, u64 *need) override { const u64 got = z.fill(dst, room, need); ended = !got && z.ended; return got; }
+};
+
+struct SpanSource : Source {                                  // as gzread: until the room is full, the stream over, or broken
+	GzipInflater z;
+	explicit SpanSource(int f) { fd = z.fd = f; z.span_bytes = GzipInflater::span_bytes_env(); stats = &z.stats; in_mirror = true; }
+	u64 fill(u8 *dst, u64 room, u64 *need) override
+	{
+		u64 out = 0;
+		z.stream = stream;
+		while (!z.done && out < room) {
+			const u64 got = z.fill(dst + out, room - out, need);
+			if (!got && !z.done) break;                           // (no room: the next call's, or with nothing made the caller's to make)
+			out += got;
+		}
+		ended = z.done;
+		return out;
+	}
+};
+
+// ---- the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet ----
+struct Piece {
+	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
+	int last_char = 0;                                        // kseq's: the header character at pos - 1 has been consumed
+	bool eof = false;                                         // nothing more to read
+	~Piece() { if (buf) lqcov_host_free(buf); }
+	void resize(u64 bytes)
+	{
+		u8 *nb = (u8*)lqcov_host_alloc(bytes);
+		if (!nb) throw std::runtime_error("no page-locked memory for a piece of the file");
+		if (fill) memcpy(nb, buf, fill);
+		if (buf) lqcov_host_free(buf);
+		buf = nb; cap = bytes;
+	}
+};
+
+// ---- the chunk being made ----
+struct ChunkParts {
+	u64 chunk_size = 0, overhead = 49;                        // the chunk rule
+	u64 n_seqs = 0, n_bases = 0;                              // of the file so far
+	std::vector<char> names; std::vector<u64> name_off, off; std::vector<u32> lens;
+	std::vector<GatherSeg> sseg, qseg;                        // the host parsers' segments (device parse: the run behind the device lists)
+	DBuf raw; u64 raw_used = 0;
+	DBuf d_sseg, d_qseg; u64 n_dss = 0, n_dqs = 0;            // device parse: the chunk's segments on the device
+	u64 size = 0;
+
+	void reset()
+	{
+		names.clear(); name_off.assign(1, 0); off.assign(1, 0); lens.clear(); sseg.clear(); qseg.clear();
+		raw_used = n_dss = n_dqs = size = 0;
+	}
+
+	// one more read, whichever parser found it; true: the chunk rule ends the chunk with it
+	bool append_read(const u8 *name, u64 name_len, u64 seq_len)
+	{
+		if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
+		for (u64 i = 0; i < name_len; ++i) if (name[i] >= 0x80)
+			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
+		names.insert(names.end(), name, name + name_len); names.push_back('\0');
+		name_off.push_back(names.size());
+		off.push_back(off.back() + seq_len);
+		lens.push_back((u32)seq_len);
+		++n_seqs; n_bases += seq_len;
+		size += 3 * overhead + name_len + 2 * seq_len;
+		return size >= chunk_size;
+	}
+
+	// device room for `more` raw bytes behind raw_used, what is there -- and `keep` bytes behind raw_used -- kept
+	void raw_reserve(hipStream_t stream, u64 more, u64 keep = 0)
+	{
+		const u64 need = raw_used + more + LQ_GATHER_SRC_PAD;
+		raw.grow((size_t)need, (size_t)std::max<u64>(need, 2 * raw_used + LQ_GATHER_SRC_PAD), (size_t)(raw_used + keep), stream);
+	}
+
+	static void seg_room(hipStream_t stream, DBuf &b, u64 have, u64 more)
+	{
+		const size_t need = (size_t)(have + more + 1) * sizeof(GatherSeg), kept = (size_t)have * sizeof(GatherSeg);
+		b.grow(need, std::max(need, 2 * kept), kept, stream);
+	}
+
+	// the segments the host parser's records have made go behind the chunk's device lists
+	void flush_host_segs(hipStream_t stream)
+	{
+		if (sseg.empty() && qseg.empty()) return;
+		seg_room(stream, d_sseg, n_dss, sseg.size()); seg_room(stream, d_qseg, n_dqs, qseg.size());
+		if (!sseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_sseg.as<GatherSeg>() + n_dss, sseg.data(), sseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
+		if (!qseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_qseg.as<GatherSeg>() + n_dqs, qseg.data(), qseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		n_dss += sseg.size(); n_dqs += qseg.size();
+		sseg.clear(); qseg.clear();
+	}
+};
+
+// ---- the BAM header (magic, l_text, text, n_ref, per reference l_name, name, l_ref): skipped as it comes, it may be longer than the piece ----
+struct BamHeader {
+	int state = 0; u64 skip = 0; u32 refs = 0;                // 0 magic and l_text, 1 the text, 2 n_ref, 3 l_name, 4 name and l_ref, 5 records
+	static u32 le32(const u8 *p) { return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
+	// true: the records begin at pc.pos
+	bool advance(Piece &pc)
+	{
+		for (;;) {
+			const u64 have = pc.fill - pc.pos;
+			const u8 *p = pc.buf + pc.pos;
+			switch (state) {
+			case 0: if (have < 8) return false; skip = le32(p + 4); pc.pos += 8; state = 1; break;
+			case 1: case 4: {
+				const u64 m = std::min(have, skip);
+				pc.pos += m; skip -= m;
+				if (skip) return false;
+				if (state == 4) --refs;
+				state = state == 1 ? 2 : refs ? 3 : 5;
+				break;
+			}
+			case 2: if (have < 4) return false; refs = le32(p); pc.pos += 4; state = refs ? 3 : 5; break;
+			case 3: if (have < 4) return false; skip = (u64)le32(p) + 4; pc.pos += 4; state = 4; break;
+			default: return true;
+			}
+		}
+	}
+};
+
+// ---- lqreader_parse(r, LQREADER_PARSE_DEVICE): the records of a piece are found on the device (fxscan.hpp) wherever it vouches for them ----
+struct DeviceParse {
+	FxScan fx; lqparse_stats pst = {0, 0, 0, 0, 0, 0};
+	bool bol = true;                                          // the byte at pos -- with last_char, the header character in front of it -- is a line's first
+	u64 cur = 0, org = 0, seg_s = 0, seg_q = 0, base_d = 0;   // the last scan's rows from cur on wait for a chunk: the piece byte its positions count from, record cur's first segments and base
+	bool fresh = true, scanned = false, fb_counted = false, fb_at_end = false;      // bytes have come since the last scan; this piece has been scanned; that scan counts as a fallback / would if more records followed
+	u64 host_recs = 0, skip = 0, backoff = 0;                 // records the host parser has made since the last scan; scans that found nothing wait for 1, 2, 4 .. of them
+
+	bool rows_waiting() const { return cur < fx.n_rows; }
+	void on_bytes() { ++pst.pieces; fresh = true; scanned = false; }
+
+	// the host parser has made a record: the fallback and back-off accounts
+	void on_host_record(bool eof)
+	{
+		++pst.records_host; ++host_recs;
+		if (skip) --skip;
+		if (scanned && !fb_counted) { if (eof) fb_at_end = true; else { ++pst.fallbacks; fb_counted = true; } }
+	}
+
+	// the scan over buf[pos .. fill) if the parser stands at a clean start and the range has not been scanned from here; true: there are rows
+	bool scan(hipStream_t stream, const Piece &pc, const ChunkParts &ck)
+	{
+		if (!bol || pc.pos >= pc.fill) return false;
+		if (!fresh && !(host_recs && !skip)) return false;
+		fresh = false; host_recs = 0;
+		org = pc.up_from; cur = 0; seg_s = seg_q = base_d = 0;
+		fx.run(stream, ck.raw.as<u8>() + ck.raw_used, pc.fill - pc.up_from, pc.pos - pc.up_from, pc.last_char);
+		if (!fx.n_lines) return false;
+		++pst.scans; pst.lines += fx.n_lines;
+		if (fx.n_rows && fb_at_end) ++pst.fallbacks;              // (the scan before stopped in front of these)
+		scanned = true; fb_counted = fb_at_end = false;
+		if (!fx.n_rows) { backoff = backoff ? std::min<u64>(backoff * 2, 1u << 20) : 1; skip = backoff; return false; }
+		backoff = skip = 0;
+		return true;
+	}
+
+	// the waiting rows join the chunk until the chunk rule ends it (true) or they are used up; their segments move behind the chunk's,
+	// device to device
+	bool take_rows(hipStream_t stream, Piece &pc, ChunkParts &ck)
+	{
+		const u64 dst0 = ck.off.back();
+		bool ended = false;
+		while (cur < fx.n_rows && !ended) {
+			const FxRow &w = fx.h_rows[cur++];
+			ended = ck.append_read(pc.buf + org + w.name_at, w.name_len, w.seq_len);
+			++pst.records_device;
+		}
+		ck.flush_host_segs(stream);
+		u64 s1 = 0, q1 = 0;
+		fx.seg_start(stream, cur, &s1, &q1);
+		const u64 ns = s1 - seg_s, nq = q1 - seg_q;
+		// a byte of the scan lies at org + its position in the piece, and a byte of the piece at raw_used - up_from + its place in the raw bytes
+		const u64 src_add = ck.raw_used + org - pc.up_from, dst_add = dst0 - base_d;
+		ChunkParts::seg_room(stream, ck.d_sseg, ck.n_dss, ns); ChunkParts::seg_room(stream, ck.d_qseg, ck.n_dqs, nq);
+		const auto grid = [](u64 n) { return (u32)std::min<u64>((n + LQ_FXSCAN_THREADS - 1) / LQ_FXSCAN_THREADS, LQ_FXSCAN_MAX_BLOCKS); };
+		if (ns) LQ_LAUNCH(k_fx_rebase, grid(ns), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.sseg.as<GatherSeg>() + seg_s, ns, src_add, dst_add, ck.d_sseg.as<GatherSeg>() + ck.n_dss);
+		if (nq) LQ_LAUNCH(k_fx_rebase, grid(nq), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.qseg.as<GatherSeg>() + seg_q, nq, src_add, dst_add, ck.d_qseg.as<GatherSeg>() + ck.n_dqs);
+		LQ_HIP_CHECK(hipGetLastError());
+		ck.n_dss += ns; ck.n_dqs += nq; seg_s = s1; seg_q = q1;
+		base_d += ck.off.back() - dst0;
+		if (cur < fx.n_rows) { pc.pos = org + fx.h_rows[cur].name_at - 1; pc.last_char = 0; }
+		else { pc.pos = org + fx.resume_pos; pc.last_char = fx.resume_last_char; }
+		bol = true;
+		return ended;
+	}
+};
 } // namespace
 
 struct lqreader {
 	std::string path, err;
-	int device = 0;
-	u64 chunk_size = 0, overhead = 49;
+	int device = 0, n_threads = 1;
 	bool upper = true;
-	int n_threads = 1;
-	// the file
-	int fd = -1; gzFile gz = nullptr; u64 file_pos = 0;
-	bool eof = false;                                         // nothing more to read
+	int format = 0;                                           // 0 FASTA/FASTQ, 1 BAM
+	bool gzip = false, bgzf_text = false;                     // the file begins with gzip's magic; it is BGZF and not BAM
+	bool bam_qual = false;                                       // the qualities come from the file
+	int inflate_mode = LQREADER_INFLATE_HOST, parse_mode = LQREADER_PARSE_HOST;   // lqreader_inflate's, lqreader_parse's
+	bool started = false;                                     // lqreader_next has been called: the modes are final, and with them
+	bool dev_parse = false, mirror = false;                   // ... the device parse is on; the raw buffer holds buf[up_from .. fill)
 	bool over = false;                                        // no more records: the end of the file, or a truncated quality string (kseq: -2)
 	bool done = false;                                        // the last chunk has been handed out
-	// BAM
-	int format = 0;                                           // 0 FASTA/FASTQ, 1 BAM
-	bool bam_qual = false, started = false;                   // the qualities come from the file; lqreader_next has been called
-	BgzfInflater bgzf;
-	int inflate_mode = LQREADER_INFLATE_HOST; bool bgzf_text = false;     // lqreader_inflate's; a BGZF file that is not BAM
-	int bgzf_fd = -1;                                         // device mode on such a file: the descriptor the blocks are read from
-	InflateDev inf; hipStream_t inf_stream = nullptr;
-	GzipInflater gzdev; int gzdev_fd = -1;                    // device mode on a gzip file that is not BGZF
-	int hdr_state = 0; u64 hdr_skip = 0; u32 hdr_refs = 0;    // the BAM header: 0 magic and l_text, 1 the text, 2 n_ref, 3 l_name, 4 name and l_ref, 5 records
-	// the piece: buf[0 .. fill) read, [pos ..) not parsed yet, [up_from .. pos) parsed and not uploaded yet
-	u8 *buf = nullptr; u64 cap = 0, fill = 0, pos = 0, up_from = 0;
-	int last_char = 0;                                        // kseq's: the header character at pos - 1 has been consumed
-	u64 n_seqs = 0, n_bases = 0;
-	// the chunk being made
-	DBuf raw; u64 raw_used = 0;
-	std::vector<GatherSeg> sseg, qseg;
-	std::vector<char> names; std::vector<u64> name_off, off; std::vector<u32> lens;
-	Record rec;
-	// lqreader_parse(r, LQREADER_PARSE_DEVICE): the records of a piece are found on the device (fxscan.hpp) wherever it vouches for them
-	int parse_mode = LQREADER_PARSE_HOST;
-	bool bol = true;                                          // the byte at pos -- with last_char, the header character in front of it -- is a line's first
-	FxScan fx; lqparse_stats pst = {0, 0, 0, 0, 0, 0};
-	DBuf d_sseg, d_qseg; u64 n_dss = 0, n_dqs = 0;            // the chunk's segments on the device; sseg / qseg hold the host-parsed run behind them
-	u64 fx_cur = 0, fx_org = 0, fx_s = 0, fx_q = 0, fx_d = 0; // the last scan's rows from fx_cur on wait for a chunk: the piece byte its positions count from, record fx_cur's first segments and base
-	bool fresh = true, scanned = false, fb_counted = false, fb_at_end = false;      // bytes have come since the last scan; this piece has been scanned; that scan counts as a fallback / would if more records followed
-	u64 host_recs = 0, skip = 0, backoff = 0;                 // records parse_one has made since the last scan; scans that found nothing wait for 1, 2, 4 .. of them
+	std::unique_ptr<Source> src;
+	InflateDev inf;
+	Piece pc;
+	BamHeader hdr; Record rec; DeviceParse dp;                // the parsers' state
+	bool rec_ends = false;                                    // the record a host parser has just put into the chunk ends it
+	ChunkParts ck;
 
-	~lqreader()
+	int open_fd() const
 	{
-		if (gz) gzclose(gz);
-		if (fd >= 0) ::close(fd);
-		if (bgzf_fd >= 0) ::close(bgzf_fd);
-		if (gzdev_fd >= 0) ::close(gzdev_fd);
-		if (buf) lqcov_host_free(buf);
+		const int fd = ::open(path.c_str(), O_RDONLY);
+		if (fd < 0) throw lq_open_error(path);
+		return fd;
 	}
 
 	void open_file()
 	{
-		fd = ::open(path.c_str(), O_RDONLY);
-		if (fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
+		const int fd = open_fd();
 		u8 magic[2] = {0, 0};
-		const bool is_gz = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
-		const int kind = is_gz ? bgzf_kind() : 0;
+		gzip = ::pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+		const int kind = gzip ? bgzf_kind(fd) : 0;
 		bgzf_text = kind == 1;
-		if (kind == 2) {
-			format = 1;
-			bgzf = BgzfInflater(); bgzf.fd = fd; bgzf.n_threads = n_threads;
-			return;
+		if (kind == 2) { format = 1; src.reset(new BgzfSource(fd, n_threads)); }
+		else if (gzip) {
+			gzFile gz = gzdopen(fd, "r");                         // (the stream owns the descriptor now)
+			if (!gz) { ::close(fd); throw lq_open_error(path); }
+			src.reset(new GzreadSource(gz));
 		}
-		if (is_gz) {
-			gz = gzdopen(fd, "r");
-			if (!gz) throw std::runtime_error("failed to open file '" + path + "'");
-			fd = -1;                                              // (the stream owns it now)
-			gzbuffer(gz, 1 << 20);
-		}
+		else src.reset(new PlainSource(fd));
 	}
 
 	// 2: a BGZF file whose first four inflated bytes are "BAM\1"; 1: another BGZF file (its first blocks inflate); 0: neither
-	int bgzf_kind()
+	static int bgzf_kind(int fd)
 	{
 		try {
 			BgzfInflater probe; probe.fd = fd;
@@ -152,112 +356,66 @@ struct lqreader {
 		} catch (const std::exception &) { return 0; }              // (not BGZF, or broken: gzread's to read or to refuse)
 	}
 
-	bool use_bgzf() const { return format == 1 || (bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE); }
-	bool use_gzdev() const { return format == 0 && gz && !bgzf_text && inflate_mode == LQREADER_INFLATE_DEVICE; }
-	bool on_device() const { return inflate_mode == LQREADER_INFLATE_DEVICE && (use_bgzf() || use_gzdev()); }
-	bool parse_dev() const { return parse_mode == LQREADER_PARSE_DEVICE && format == 0; }
-	bool mirror() const { return on_device() || parse_dev(); }            // the raw buffer holds buf[up_from .. fill), not only what has been parsed
-
-	// the first lqreader_next: the mode is final
+	// the first lqreader_next: the modes are final, and the source is.  In device mode a BGZF file's blocks are inflated by the kernel and
+	// any other gzip file by spans, from a descriptor of their own (nothing has been read through gzread's)
 	void start()
 	{
 		started = true;
-		if (!on_device()) return;
-		if (use_gzdev()) {                                        // (gz keeps its descriptor; nothing has been read through it)
-			gzdev_fd = ::open(path.c_str(), O_RDONLY);
-			if (gzdev_fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
-			gzdev.fd = gzdev_fd; gzdev.span_bytes = GzipInflater::span_bytes_env();
-			gzdev.dev_room = [this](u8 *dst, u64 n) {             // as below: dst is a place of the piece
-				const u64 ahead = (u64)(dst - buf) - up_from;
-				raw_reserve(inf_stream, ahead + n, ahead);
-				return raw.as<u8>() + raw_used + ahead;
+		dev_parse = parse_mode == LQREADER_PARSE_DEVICE && format == 0;
+		if (inflate_mode == LQREADER_INFLATE_DEVICE && (format == 1 || bgzf_text)) {
+			if (format == 0) src.reset(new BgzfSource(open_fd(), n_threads));
+			BgzfSource &b = static_cast<BgzfSource&>(*src);          // (a BAM file's source is one since open_file)
+			b.in_mirror = true;
+			b.z.device = [this](const std::vector<BgzfInflater::Block> &blocks, const u8 *win, u8 *dst, u64 out_bytes, std::vector<u32> &status) {
+				const u8 *d_dst = mirror_at(dst, out_bytes);
+				const u64 at = (u64)(d_dst - ck.raw.as<u8>()), lo = blocks.front().in & ~(u64)15, hi = blocks.back().in + blocks.back().in_len;
+				std::vector<InflateJob> jobs(blocks.size());
+				for (size_t i = 0; i < blocks.size(); ++i)
+					jobs[i] = {blocks[i].in - lo, at + blocks[i].out, (u32)blocks[i].in_len, (u32)blocks[i].isize};
+				status.assign(blocks.size(), 0);
+				inf.run(src->stream, win + lo, hi - lo, jobs, ck.raw.as<u8>(), status.data());
+				if (out_bytes) LQ_HIP_CHECK(hipMemcpyAsync(dst, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, src->stream));
+				LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
 			};
-			return;
+		} else if (inflate_mode == LQREADER_INFLATE_DEVICE && gzip) {
+			SpanSource *s = new SpanSource(open_fd());
+			src.reset(s);
+			s->z.dev_room = [this](u8 *dst, u64 n) { return mirror_at(dst, n); };
 		}
-		if (format == 0) {                                        // (gz keeps its descriptor; nothing has been read through it)
-			bgzf_fd = ::open(path.c_str(), O_RDONLY);
-			if (bgzf_fd < 0) throw std::runtime_error("failed to open file '" + path + "'");
-			bgzf = BgzfInflater(); bgzf.fd = bgzf_fd; bgzf.n_threads = n_threads;
-		}
-		bgzf.device = [this](const std::vector<BgzfInflater::Block> &blocks, const u8 *win, u8 *dst, u64 out_bytes, std::vector<u32> &status) {
-			// dst is buf + fill: its place in the raw bytes is where upload() would put it
-			const u64 ahead = (u64)(dst - buf) - up_from, lo = blocks.front().in & ~(u64)15, hi = blocks.back().in + blocks.back().in_len;
-			raw_reserve(inf_stream, ahead + out_bytes, ahead);
-			std::vector<InflateJob> jobs(blocks.size());
-			for (size_t i = 0; i < blocks.size(); ++i)
-				jobs[i] = {blocks[i].in - lo, raw_used + ahead + blocks[i].out, (u32)blocks[i].in_len, (u32)blocks[i].isize};
-			status.assign(blocks.size(), 0);
-			inf.run(inf_stream, win + lo, hi - lo, jobs, raw.as<u8>(), status.data());
-			if (out_bytes) LQ_HIP_CHECK(hipMemcpyAsync(dst, raw.as<u8>() + raw_used + ahead, (size_t)out_bytes, hipMemcpyDeviceToHost, inf_stream));
-			LQ_HIP_CHECK(hipStreamSynchronize(inf_stream));
-		};
+		mirror = src->in_mirror || dev_parse;
 	}
 
-	[[noreturn]] void bam_fail(const std::string &what) { throw std::runtime_error("failed to open file '" + path + "': " + what); }
-
-	void set_piece(u64 bytes)
+	// the place in the raw device buffer of the n bytes at dst, a place of the piece at or behind up_from: where upload() would put them.
+	// Room is made, what lies in front of them is kept
+	u8 *mirror_at(const u8 *dst, u64 n)
 	{
-		u8 *nb = (u8*)lqcov_host_alloc(bytes);
-		if (!nb) throw std::runtime_error("no page-locked memory for a piece of the file");
-		if (fill) memcpy(nb, buf, fill);
-		if (buf) lqcov_host_free(buf);
-		buf = nb; cap = bytes;
+		const u64 ahead = (u64)(dst - pc.buf) - pc.up_from;
+		ck.raw_reserve(src->stream, ahead + n, ahead);
+		return ck.raw.as<u8>() + ck.raw_used + ahead;
 	}
+
+	// n bytes of the piece at p go up to that place; the piece is free again
+	void send_up(const u8 *p, u64 n)
+	{
+		LQ_HIP_CHECK(hipMemcpyAsync(mirror_at(p, n), p, (size_t)n, hipMemcpyHostToDevice, src->stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
+	}
+
+	[[noreturn]] void bam_fail(const std::string &what) { throw lq_open_error(path, what); }
 
 	// more bytes behind buf[fill); false: the file has ended
 	bool read_more()
 	{
-		if (use_bgzf()) {
-			while (!eof) {
-				u64 need = 0, got = 0;
-				try { got = bgzf.fill(buf + fill, cap - fill, &need); }
-				catch (const std::runtime_error &e) {
-					if (strncmp(e.what(), "BGZF block", 10) && strcmp(e.what(), "read error")) throw;      // (the device's, not the file's)
-					bam_fail(e.what());
-				}
-				if (got) { fill += got; return true; }
-				if (bgzf.ended) { eof = true; break; }
-				set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
-			}
-			return false;
-		}
-		if (use_gzdev()) {                                        // as gzread: until the piece is full, the stream over, or broken
-			bool any = false;
-			while (!eof) {
-				u64 need = 0, got = 0;
-				gzdev.stream = inf_stream;
-				try { got = gzdev.fill(buf + fill, cap - fill, &need); }
-				catch (const GzipError &e) { bam_fail(e.what()); }
-				catch (const std::runtime_error &e) { if (strcmp(e.what(), "read error")) throw; bam_fail(e.what()); }
-				fill += got; any = any || got;
-				if (gzdev.done) { eof = true; break; }
-				if (fill == cap) break;
-				if (!got) {
-					if (any) break;                                       // (the next call makes room)
-					set_piece(std::max(cap * 2, fill + need));            // a block larger than the room behind what the piece holds
-				}
-			}
-			return any;
-		}
-		while (!eof && fill < cap) {
-			const u64 want = std::min<u64>(cap - fill, 1u << 30);
-			i64 got;
-			if (gz) {
-				got = gzread(gz, buf + fill, (unsigned)want);
-				if (got < 0) throw std::runtime_error("failed to open file '" + path + "': not a complete gzip stream");
-			} else {
-				got = ::pread(fd, buf + fill, want, (off_t)file_pos);
-				if (got < 0) throw std::runtime_error("failed to open file '" + path + "': read error");
-			}
-			if (got == 0) { eof = true; break; }
-			if (mirror()) {                                       // (device parse: the bytes go up as they come)
-				const u64 ahead = fill - up_from;
-				raw_reserve(inf_stream, ahead + (u64)got, ahead);
-				LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used + ahead, buf + fill, (size_t)got, hipMemcpyHostToDevice, inf_stream));
-				LQ_HIP_CHECK(hipStreamSynchronize(inf_stream));
-			}
-			fill += (u64)got; file_pos += (u64)got;
-			return true;
+		while (!pc.eof) {
+			if (pc.fill == pc.cap) pc.resize(pc.cap * 2);             // a record longer than the piece
+			u64 need = 0, got = 0;
+			try { got = src->fill(pc.buf + pc.fill, pc.cap - pc.fill, &need); }
+			catch (const lq_file_error &e) { bam_fail(e.what()); }      // (the file's, not the device's)
+			if (got && mirror && !src->in_mirror) send_up(pc.buf + pc.fill, got);      // (device parse: the bytes go up as they come)
+			pc.fill += got;
+			pc.eof = src->ended;
+			if (got || pc.eof) return got != 0;
+			pc.resize(std::max(pc.cap * 2, pc.fill + need));          // the next bytes want more room than there is behind what the piece holds
 		}
 		return false;
 	}
@@ -266,7 +424,8 @@ struct lqreader {
 	// read, nothing is consumed but bytes in front of a header character; END: kseq returns -1 or -2.
 	int parse_one()
 	{
-		const u8 *p = buf; const u64 n = fill;
+		const u8 *p = pc.buf; const u64 n = pc.fill; const bool eof = pc.eof;
+		u64 &pos = pc.pos; int &last_char = pc.last_char;
 		u64 q = pos; int lc = last_char;
 		Record &r = rec;
 		r.seq.clear(); r.qual.clear(); r.seq_len = 0; r.has_qual = false;
@@ -332,222 +491,72 @@ struct lqreader {
 		return REC;
 	}
 
-	static u32 le32(const u8 *p) { return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
-
-	// the BAM header (magic, l_text, text, n_ref, per reference l_name, name, l_ref) is skipped as it comes: it may be longer than
-	// the piece.  true: the records begin at pos
-	bool bam_header()
-	{
-		for (;;) {
-			const u64 have = fill - pos;
-			switch (hdr_state) {
-			case 0: if (have < 8) return false; hdr_skip = le32(buf + pos + 4); pos += 8; hdr_state = 1; break;
-			case 1: case 4: {
-				const u64 m = std::min(have, hdr_skip);
-				pos += m; hdr_skip -= m;
-				if (hdr_skip) return false;
-				if (hdr_state == 4) --hdr_refs;
-				hdr_state = hdr_state == 1 ? 2 : hdr_refs ? 3 : 5;
-				break;
-			}
-			case 2: if (have < 4) return false; hdr_refs = le32(buf + pos); pos += 4; hdr_state = hdr_refs ? 3 : 5; break;
-			case 3: if (have < 4) return false; hdr_skip = (u64)le32(buf + pos) + 4; pos += 4; hdr_state = 4; break;
-			default: return true;
-			}
-		}
-	}
-
-	// one BAM record at buf[pos ..) into the chunk's descriptors.  NEED_MORE: the record is not whole in the piece yet
+	// one BAM record at buf[pos ..) into the chunk.  NEED_MORE: the record is not whole in the piece yet
 	int parse_bam_one()
 	{
-		if (hdr_state != 5) {
-			const bool in = bam_header();
-			if (on_device()) raw_used += pos - up_from;           // (the header is in the raw bytes already)
-			up_from = pos;                                        // (no descriptor points into the header: it is not uploaded)
-			if (!in) { if (eof) bam_fail("the file ends inside the BAM header"); return NEED_MORE; }
+		if (hdr.state != 5) {
+			const bool in = hdr.advance(pc);
+			if (src->in_mirror) ck.raw_used += pc.pos - pc.up_from;   // (the header is in the raw bytes already)
+			pc.up_from = pc.pos;                                      // (no descriptor points into the header: it is not uploaded)
+			if (!in) { if (pc.eof) bam_fail("the file ends inside the BAM header"); return NEED_MORE; }
 		}
-		const u64 have = fill - pos;
-		const std::string where = "BAM record " + std::to_string(n_seqs + 1) + ": ";
-		if (have == 0 && eof) return END;
-		if (have < 36) { if (eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
-		const u8 *p = buf + pos;
-		const u64 block_size = le32(p), l_name = p[12], n_cigar = (u64)p[16] | (u64)p[17] << 8, l_seq = le32(p + 20);
+		const u64 have = pc.fill - pc.pos;
+		const std::string where = "BAM record " + std::to_string(ck.n_seqs + 1) + ": ";
+		if (have == 0 && pc.eof) return END;
+		if (have < 36) { if (pc.eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
+		const u8 *p = pc.buf + pc.pos;
+		const u64 block_size = BamHeader::le32(p), l_name = p[12], n_cigar = (u64)p[16] | (u64)p[17] << 8, l_seq = BamHeader::le32(p + 20);
 		if (l_seq > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases (bseq.c:80)");
 		const u64 fields = 32 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
 		if (block_size > 0x7fffffffULL || block_size < fields)
 			bam_fail(where + "block_size " + std::to_string((i32)block_size) + " is too small for its fields (" + std::to_string(fields) + " bytes)");
 		if (l_name == 0) bam_fail(where + "l_read_name is 0");
-		if (have < 4 + block_size) { if (eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
+		if (have < 4 + block_size) { if (pc.eof) bam_fail(where + "the file ends inside a record"); return NEED_MORE; }
 		if (p[36 + l_name - 1] != 0) bam_fail(where + "the read name has no NUL at its end");
-		if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
-		const u8 *nm = p + 36;
-		const u64 name_len = strlen((const char*)nm);
-		for (u64 i = 0; i < name_len; ++i) if (nm[i] >= 0x80)
-			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
-		names.insert(names.end(), nm, nm + name_len + 1);
-		name_off.push_back(names.size());
-		// (where a byte of the piece lies in the chunk's raw bytes: add_record)
-		const u64 seq_at = raw_used + (pos + 36 + l_name + 4 * n_cigar - up_from), d = off.back();
+		// the packed sequence, the quality bytes behind it: up_from is the first byte of the next upload, which lands at raw_used
+		const u64 packed = ck.raw_used - pc.up_from + pc.pos + 36 + l_name + 4 * n_cigar, d0 = ck.off.back();
+		rec_ends = ck.append_read(p + 36, strlen((const char*)p + 36), l_seq);
 		if (l_seq) {
-			sseg.push_back({seq_at, d});
-			qseg.push_back({bam_qual ? seq_at + (l_seq + 1) / 2 : LQ_GATHER_FILL, d});
+			ck.sseg.push_back({packed, d0});
+			ck.qseg.push_back({bam_qual ? packed + (l_seq + 1) / 2 : LQ_GATHER_FILL, d0});
 		}
-		off.push_back(d + l_seq);
-		lens.push_back((u32)l_seq);
-		++n_seqs; n_bases += l_seq;
-		rec.name_len = name_len; rec.seq_len = l_seq;
-		pos += 4 + block_size;
+		pc.pos += 4 + block_size;
 		return REC;
 	}
 
-	// device room for `more` raw bytes behind raw_used, what is there -- and `keep` bytes behind raw_used -- kept
-	void raw_reserve(hipStream_t stream, u64 more, u64 keep = 0)
-	{
-		const u64 need = raw_used + more + LQ_GATHER_SRC_PAD;
-		if (need <= raw.cap) return;
-		DBuf nb;
-		nb.ensure((size_t)std::max<u64>(need, 2 * raw_used + LQ_GATHER_SRC_PAD));
-		if (raw_used + keep) {
-			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, raw.p, (size_t)(raw_used + keep), hipMemcpyDeviceToDevice, stream));
-			LQ_HIP_CHECK(hipStreamSynchronize(stream));
-		}
-		raw.swap(nb);
-		nb.release();
-	}
-
-	// buf[up_from .. pos) goes behind the raw bytes of the chunk (the descriptors made so far already point there)
-	void upload(hipStream_t stream)
-	{
-		const u64 len = pos - up_from;
-		if (mirror()) raw_used += len;                            // (they are there already)
-		else if (len) {
-			raw_reserve(stream, len);
-			LQ_HIP_CHECK(hipMemcpyAsync(raw.as<u8>() + raw_used, buf + up_from, (size_t)len, hipMemcpyHostToDevice, stream));
-			LQ_HIP_CHECK(hipStreamSynchronize(stream));           // the piece is free again
-			raw_used += len;
-		}
-		up_from = pos;
-	}
-
-	// the record that straddles the piece's end moves to its front, the file goes on behind it
-	void refill(hipStream_t stream)
-	{
-		upload(stream);
-		if (pos) memmove(buf, buf + pos, (size_t)(fill - pos));
-		fill -= pos; pos = 0; up_from = 0;
-		if (fill == cap) set_piece(cap * 2);                      // a record longer than the piece
-		more();
-	}
-
-	void more() { if (read_more()) { ++pst.pieces; fresh = true; scanned = false; } }
-
-	// ---- the device parse ----
-	static void seg_room(hipStream_t stream, DBuf &b, u64 have, u64 more)
-	{
-		const size_t need = (size_t)(have + more + 1) * sizeof(GatherSeg);
-		if (need <= b.cap) return;
-		DBuf nb;
-		nb.ensure(std::max(need, 2 * (size_t)have * sizeof(GatherSeg)));
-		if (have) {
-			LQ_HIP_CHECK(hipMemcpyAsync(nb.p, b.p, (size_t)have * sizeof(GatherSeg), hipMemcpyDeviceToDevice, stream));
-			LQ_HIP_CHECK(hipStreamSynchronize(stream));
-		}
-		b.swap(nb);
-		nb.release();
-	}
-
-	// the segments parse_one's records have made go behind the chunk's device lists
-	void flush_host_segs(hipStream_t stream)
-	{
-		if (sseg.empty() && qseg.empty()) return;
-		seg_room(stream, d_sseg, n_dss, sseg.size()); seg_room(stream, d_qseg, n_dqs, qseg.size());
-		if (!sseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_sseg.as<GatherSeg>() + n_dss, sseg.data(), sseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
-		if (!qseg.empty()) LQ_HIP_CHECK(hipMemcpyAsync(d_qseg.as<GatherSeg>() + n_dqs, qseg.data(), qseg.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, stream));
-		LQ_HIP_CHECK(hipStreamSynchronize(stream));
-		n_dss += sseg.size(); n_dqs += qseg.size();
-		sseg.clear(); qseg.clear();
-	}
-
-	// the scan's records fx_cur .. e have joined the chunk, their first base at dst0: their segments move behind the chunk's, device to device
-	void take_run(hipStream_t stream, u64 e, u64 dst0)
-	{
-		flush_host_segs(stream);
-		u64 s1 = 0, q1 = 0;
-		fx.seg_start(stream, e, &s1, &q1);
-		const u64 ns = s1 - fx_s, nq = q1 - fx_q;
-		// a byte of the scan lies at fx_org + its position in the piece, and a byte of the piece at raw_used - up_from + its place in the raw bytes
-		const u64 src_add = raw_used + fx_org - up_from, dst_add = dst0 - fx_d;
-		seg_room(stream, d_sseg, n_dss, ns); seg_room(stream, d_qseg, n_dqs, nq);
-		const auto grid = [](u64 n) { return (u32)std::min<u64>((n + LQ_FXSCAN_THREADS - 1) / LQ_FXSCAN_THREADS, LQ_FXSCAN_MAX_BLOCKS); };
-		if (ns) LQ_LAUNCH(k_fx_rebase, grid(ns), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.sseg.as<GatherSeg>() + fx_s, ns, src_add, dst_add, d_sseg.as<GatherSeg>() + n_dss);
-		if (nq) LQ_LAUNCH(k_fx_rebase, grid(nq), LQ_FXSCAN_THREADS, stream, (const GatherSeg*)fx.qseg.as<GatherSeg>() + fx_q, nq, src_add, dst_add, d_qseg.as<GatherSeg>() + n_dqs);
-		LQ_HIP_CHECK(hipGetLastError());
-		n_dss += ns; n_dqs += nq; fx_s = s1; fx_q = q1;
-	}
-
-	// the scan over buf[pos .. fill) if the parser stands at a clean start and the range has not been scanned from here; true: there are rows
-	bool scan(hipStream_t stream)
-	{
-		if (!bol || pos >= fill) return false;
-		if (!fresh && !(host_recs && !skip)) return false;
-		fresh = false; host_recs = 0;
-		fx_org = up_from; fx_cur = 0; fx_s = fx_q = fx_d = 0;
-		fx.run(stream, raw.as<u8>() + raw_used, fill - up_from, pos - up_from, last_char);
-		if (!fx.n_lines) return false;
-		++pst.scans; pst.lines += fx.n_lines;
-		if (fx.n_rows && fb_at_end) ++pst.fallbacks;              // (the scan before stopped in front of these)
-		scanned = true; fb_counted = fb_at_end = false;
-		if (!fx.n_rows) { backoff = backoff ? std::min<u64>(backoff * 2, 1u << 20) : 1; skip = backoff; return false; }
-		backoff = skip = 0;
-		return true;
-	}
-
-	// the waiting rows join the chunk until the chunk rule ends it (true) or they are used up
-	bool take_rows(hipStream_t stream, u64 &size)
-	{
-		const u64 dst0 = off.back();
-		bool ended = false;
-		while (fx_cur < fx.n_rows && !ended) {
-			const FxRow &w = fx.h_rows[fx_cur];
-			if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
-			const u8 *nm = buf + fx_org + w.name_at;
-			for (u64 i = 0; i < w.name_len; ++i) if (nm[i] >= 0x80)
-				throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
-			names.insert(names.end(), nm, nm + w.name_len); names.push_back('\0');
-			name_off.push_back(names.size());
-			off.push_back(off.back() + w.seq_len);
-			lens.push_back(w.seq_len);
-			++n_seqs; n_bases += w.seq_len; ++pst.records_device;
-			++fx_cur;
-			size += 3 * overhead + w.name_len + 2 * (u64)w.seq_len;
-			ended = size >= chunk_size;
-		}
-		take_run(stream, fx_cur, dst0);
-		fx_d += off.back() - dst0;
-		if (fx_cur < fx.n_rows) { pos = fx_org + fx.h_rows[fx_cur].name_at - 1; last_char = 0; }
-		else { pos = fx_org + fx.resume_pos; last_char = fx.resume_last_char; }
-		bol = true;
-		return ended;
-	}
-
+	// parse_one's `rec` joins the chunk, with its segments
 	void add_record()
 	{
 		const Record &r = rec;
-		const u8 *nm = buf + r.name_at;
-		for (u64 i = 0; i < r.name_len; ++i) if (nm[i] >= 0x80)
-			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
-		names.insert(names.end(), nm, nm + r.name_len); names.push_back('\0');
-		name_off.push_back(names.size());
 		// where a byte of the piece lies in the chunk's raw bytes: up_from is the first byte of the next upload, which lands at raw_used
-		u64 d = off.back();
-		for (const Line &l : r.seq) if (l.len) { sseg.push_back({raw_used + (l.at - up_from), d}); d += l.len; }
-		d = off.back();
-		if (r.has_qual) { for (const Line &l : r.qual) { qseg.push_back({raw_used + (l.at - up_from), d}); d += l.len; } }
-		else if (r.seq_len) qseg.push_back({LQ_GATHER_FILL, d});
-		off.push_back(off.back() + r.seq_len);
-		lens.push_back((u32)r.seq_len);
-		++n_seqs; n_bases += r.seq_len;
+		const u64 in_raw = ck.raw_used - pc.up_from, d0 = ck.off.back();
+		rec_ends = ck.append_read(pc.buf + r.name_at, r.name_len, r.seq_len);
+		u64 d = d0;
+		for (const Line &l : r.seq) if (l.len) { ck.sseg.push_back({in_raw + l.at, d}); d += l.len; }
+		d = d0;
+		if (r.has_qual) { for (const Line &l : r.qual) { ck.qseg.push_back({in_raw + l.at, d}); d += l.len; } }
+		else if (r.seq_len) ck.qseg.push_back({LQ_GATHER_FILL, d});
 	}
+
+	// buf[up_from .. pos) goes behind the raw bytes of the chunk (the descriptors made so far already point there)
+	void upload()
+	{
+		const u64 len = pc.pos - pc.up_from;
+		if (len && !mirror) send_up(pc.buf + pc.up_from, len);    // (a mirror holds them already)
+		ck.raw_used += len;
+		pc.up_from = pc.pos;
+	}
+
+	// the record that straddles the piece's end moves to its front, the file goes on behind it
+	void refill()
+	{
+		upload();
+		if (pc.pos) memmove(pc.buf, pc.buf + pc.pos, (size_t)(pc.fill - pc.pos));
+		pc.fill -= pc.pos; pc.pos = 0; pc.up_from = 0;
+		more();
+	}
+
+	void more() { if (read_more()) dp.on_bytes(); }
 
 	// the next chunk into c: records until the chunk rule ends it, or until the file does (*last)
 	void next(lqchunk &c, u32 *n_out, u64 *n_seqs_cum, u64 *n_bases_cum, int *last)
@@ -556,50 +565,31 @@ struct lqreader {
 		if (c.device != device) throw std::invalid_argument("the chunk lives on another device than the reader");
 		lq_cabi::select_device(device);
 		if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
-		inf_stream = c.stream;
 		if (!started) start();
+		src->stream = c.stream;
 		c.resident = false; c.packed = false; c.n_chunks = 0;
-		raw_used = 0; sseg.clear(); qseg.clear(); names.clear(); name_off.assign(1, 0); off.assign(1, 0); lens.clear();
-		n_dss = n_dqs = 0;
-		if (!buf) { set_piece(piece_bytes()); more(); }
-		else if (mirror() && fill > up_from) {                 // what the piece still holds belongs to this chunk: the mirror starts anew
-			raw_reserve(c.stream, fill - up_from);
-			LQ_HIP_CHECK(hipMemcpyAsync(raw.p, buf + up_from, (size_t)(fill - up_from), hipMemcpyHostToDevice, c.stream));
-			LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
-		}
-		u64 size = 0; bool ended = false;
-		while (!over) {
-			if (parse_dev()) {
-				if (fx_cur < fx.n_rows || scan(c.stream)) {
-					if (take_rows(c.stream, size)) { ended = true; break; }
-					continue;
-				}
-			}
-			const u64 pos0 = pos;
+		ck.reset();
+		if (!pc.buf) { pc.resize(piece_bytes()); more(); }
+		else if (mirror && pc.fill > pc.up_from) send_up(pc.buf + pc.up_from, pc.fill - pc.up_from);   // (the mirror starts anew)
+		bool ended = false;
+		while (!over && !ended) {
+			if (dev_parse && (dp.rows_waiting() || dp.scan(c.stream, pc, ck))) { ended = dp.take_rows(c.stream, pc, ck); continue; }
+			const u64 pos0 = pc.pos;
 			const int st = format == 1 ? parse_bam_one() : parse_one();
-			if (st == REC) bol = true;
-			else if (pos != pos0) bol = buf[pos - 1] == '\n';
-			if (st == NEED_MORE) { refill(c.stream); continue; }
+			if (st == REC) dp.bol = true;
+			else if (pc.pos != pos0) dp.bol = pc.buf[pc.pos - 1] == '\n';
+			if (st == NEED_MORE) { refill(); continue; }
 			if (st == END) { over = true; break; }
-			if (parse_dev()) {
-				++pst.records_host; ++host_recs;
-				if (skip) --skip;
-				if (scanned && !fb_counted) { if (eof) fb_at_end = true; else { ++pst.fallbacks; fb_counted = true; } }
-			}
-			if (format == 0) {
-				if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
-				add_record();
-			}
-			size += 3 * overhead + rec.name_len + 2 * rec.seq_len;
-			if (size >= chunk_size) { ended = true; break; }
+			if (dev_parse) dp.on_host_record(pc.eof);
+			if (format == 0) add_record();
+			ended = rec_ends;
 		}
-		if (parse_dev()) flush_host_segs(c.stream);
-		upload(c.stream);
+		if (dev_parse) ck.flush_host_segs(c.stream);
+		upload();
 		done = !ended;
-		if (parse_dev()) lq_chunk_gather_dev(c, off, raw.as<u8>(), d_sseg.as<GatherSeg>(), n_dss, d_qseg.as<GatherSeg>(), n_dqs, upper);
-		else lq_chunk_gather(c, off, raw.as<u8>(), sseg, qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
-		const u32 n = c.n;
-		*n_out = n; *n_seqs_cum = n_seqs; *n_bases_cum = n_bases; *last = done ? 1 : 0;
+		if (dev_parse) lq_chunk_gather_dev(c, ck.off, ck.raw.as<u8>(), ck.d_sseg.as<GatherSeg>(), ck.n_dss, ck.d_qseg.as<GatherSeg>(), ck.n_dqs, upper);
+		else lq_chunk_gather(c, ck.off, ck.raw.as<u8>(), ck.sseg, ck.qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
+		*n_out = c.n; *n_seqs_cum = ck.n_seqs; *n_bases_cum = ck.n_bases; *last = done ? 1 : 0;
 	}
 
 	// LQREADER_PIECE_BYTES: the size of a piece (tests: pieces shorter than a record)
@@ -611,6 +601,18 @@ struct lqreader {
 	}
 };
 
+namespace {
+// a call without a handle: the message is lqreader_last_error(NULL)'s
+template <class F> int one_shot(F &&f)
+{
+	char msg[512] = {0};
+	const int rc = lq_cabi::guarded(msg, sizeof(msg), f);
+	if (rc) g_reader_open_error = msg;
+	return rc;
+}
+
+} // namespace
+
 extern "C" {
 
 lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int is_upper, uint32_t str_overhead, int n_threads)
@@ -619,7 +621,7 @@ lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int i
 		if (!path) throw std::invalid_argument("null path");
 		lq_cabi::select_device(device);
 		std::unique_ptr<lqreader> r(new lqreader());
-		r->path = path; r->device = device; r->chunk_size = chunk_size; r->upper = is_upper != 0; r->overhead = str_overhead;
+		r->path = path; r->device = device; r->ck.chunk_size = chunk_size; r->upper = is_upper != 0; r->ck.overhead = str_overhead;
 		r->n_threads = n_threads <= 0 ? 16 : std::min(n_threads, 16);
 		const char *mode = getenv("LQREADER_INFLATE");
 		if (mode && !strcmp(mode, "device")) r->inflate_mode = LQREADER_INFLATE_DEVICE;
@@ -680,7 +682,7 @@ int lqreader_parse(lqreader *r, int mode)
 int lqreader_parse_stats(const lqreader *r, lqparse_stats *stats)
 {
 	if (!r || !stats) return LQCOV_E_ARG;
-	*stats = r->pst;
+	*stats = r->dp.pst;
 	return 0;
 }
 
@@ -688,8 +690,7 @@ int lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, 
               uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg,
               uint64_t *resume_pos, int *resume_last_char)
 {
-	char msg[512] = {0};
-	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+	return one_shot([&] {
 		if (!n_rows || !n_sseg || !n_qseg || !resume_pos || !resume_last_char || (n && !bytes)) throw std::invalid_argument("null buffers");
 		if (start_pos > n || (last_char != 0 && last_char != '@' && last_char != '>')) throw std::invalid_argument("no parser state");
 		*n_rows = *n_sseg = *n_qseg = 0; *resume_pos = start_pos; *resume_last_char = last_char;
@@ -697,10 +698,7 @@ int lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, 
 		const uint64_t at = start_pos - (last_char ? 1 : 0);
 		if (last_char && (start_pos == 0 || bytes[start_pos - 1] != last_char)) throw std::invalid_argument("no parser state");
 		if ((at && bytes[at - 1] != '\n') || start_pos >= n) return;
-		lq_cabi::select_device(device);
-		hipStream_t stream = nullptr;
-		LQ_HIP_CHECK(hipStreamCreate(&stream));
-		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		lq_cabi::ScopedStream stream(device);
 		DBuf d;
 		d.ensure((size_t)n + LQ_GATHER_SRC_PAD);
 		LQ_HIP_CHECK(hipMemcpyAsync(d.p, bytes, (size_t)n, hipMemcpyHostToDevice, stream));
@@ -714,29 +712,23 @@ int lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, 
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 		*n_rows = fx.n_rows; *n_sseg = fx.n_sseg; *n_qseg = fx.n_qseg; *resume_pos = fx.resume_pos; *resume_last_char = fx.resume_last_char;
 	});
-	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
-	return rc;
 }
 
 int lqreader_inflate_stats(const lqreader *r, lqinflate_stats *stats)
 {
 	if (!r || !stats) return LQCOV_E_ARG;
-	*stats = r->gzdev.stats;
+	*stats = r->src->stats ? *r->src->stats : lqinflate_stats{};
 	return 0;
 }
 
 int lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t span_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
                    lqinflate_stats *stats)
 {
-	char msg[512] = {0};
-	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+	return one_shot([&] {
 		if (!out_len || (comp_len && !comp) || (out_cap && !out)) throw std::invalid_argument("null buffers");
 		if (span_bytes && (span_bytes < 1024 || span_bytes > (1u << 17) || (span_bytes & 15))) throw std::invalid_argument("span_bytes must be a multiple of 16 from 1024 to 131072");
 		*out_len = 0;
-		lq_cabi::select_device(device);
-		hipStream_t stream = nullptr;
-		LQ_HIP_CHECK(hipStreamCreate(&stream));
-		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		lq_cabi::ScopedStream stream(device);
 		DBuf d_out;
 		d_out.ensure((size_t)out_cap + 16);
 		GzipInflater g;
@@ -752,19 +744,16 @@ int lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t 
 				n += got;
 				if (!got && !g.done) throw std::invalid_argument("out_cap is smaller than the inflated stream");
 			}
-		} catch (const GzipError &e) { throw std::runtime_error(std::string("failed to open file '(memory)': ") + e.what()); }
+		} catch (const GzipError &e) { throw lq_open_error("(memory)", e.what()); }
 		*out_len = n;
 		if (stats) *stats = g.stats;
 	});
-	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
-	return rc;
 }
 
 int lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_t n, const uint64_t *in_off, const uint32_t *in_len,
                      const uint64_t *out_off, const uint32_t *isize, uint8_t *out_host, uint32_t *status)
 {
-	char msg[512] = {0};
-	const int rc = lq_cabi::guarded(msg, sizeof(msg), [&] {
+	return one_shot([&] {
 		if (!n) return;
 		if (!in_off || !in_len || !out_off || !isize || !status || (comp_len && !comp)) throw std::invalid_argument("null buffers");
 		std::vector<InflateJob> jobs(n);
@@ -777,10 +766,7 @@ int lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_
 			out_len = std::max(out_len, out_off[i] + isize[i]);
 		}
 		if (out_len && !out_host) throw std::invalid_argument("null buffers");
-		lq_cabi::select_device(device);
-		hipStream_t stream = nullptr;
-		LQ_HIP_CHECK(hipStreamCreate(&stream));
-		struct Closer { hipStream_t s; ~Closer() { (void)hipStreamDestroy(s); } } closer{stream};
+		lq_cabi::ScopedStream stream(device);
 		InflateDev inf; DBuf out;
 		out.ensure((size_t)out_len + 16);
 		if (out_len) LQ_HIP_CHECK(hipMemcpyAsync(out.p, out_host, (size_t)out_len, hipMemcpyHostToDevice, stream));
@@ -788,14 +774,12 @@ int lqinflate_blocks(int device, const uint8_t *comp, uint64_t comp_len, uint32_
 		if (out_len) LQ_HIP_CHECK(hipMemcpyAsync(out_host, out.p, (size_t)out_len, hipMemcpyDeviceToHost, stream));
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	});
-	if (rc) g_reader_open_error = msg;                        // (lqreader_last_error(NULL))
-	return rc;
 }
 
 int lqreader_names(const lqreader *r, const char **names, const uint64_t **name_off, const uint32_t **lens)
 {
 	if (!r || !names || !name_off || !lens) return LQCOV_E_ARG;
-	*names = r->names.data(); *name_off = r->name_off.data(); *lens = r->lens.data();
+	*names = r->ck.names.data(); *name_off = r->ck.name_off.data(); *lens = r->ck.lens.data();
 	return 0;
 }
 

@@ -25,14 +25,12 @@
 static_assert(LQ_FASTQ_PIECE % LQ_FASTQ_TILE == 0, "a piece is whole tiles");
 
 namespace {
-struct IoError : std::runtime_error { using std::runtime_error::runtime_error; };
-
 thread_local std::string g_fastq_error;                       // why lqfastq_open failed, and what lqfastq_close reported
 
 template <class F> int fastq_guard(std::string &err, F &&f)
 {
 	try { f(); return 0; }
-	catch (const IoError &e) { err = e.what(); return LQCOV_E_IO; }
+	catch (const lq_io_error &e) { err = e.what(); return LQCOV_E_IO; }
 	catch (const std::domain_error &e) { err = e.what(); return LQCOV_E_DOMAIN; }
 	catch (const std::invalid_argument &e) { err = e.what(); return LQCOV_E_ARG; }
 	catch (const std::runtime_error &e) { err = e.what(); return LQCOV_E_DEVICE; }
@@ -156,7 +154,7 @@ struct lqfastq {
 		if (!total) return 0;                                  // (nothing to write: no file either, as write_fastq)
 		if (fd < 0) {
 			fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_APPEND | O_CLOEXEC, 0666);
-			if (fd < 0) throw IoError("failed to open file '" + path + "': " + strerror(errno));
+			if (fd < 0) throw lq_open_error(path, strerror(errno));
 			th = std::thread([this] { thread_main(); });
 		}
 		dev.ensure((size_t)piece);
@@ -166,7 +164,7 @@ struct lqfastq {
 			{
 				std::unique_lock<std::mutex> lk(mu);
 				cv.wait(lk, [&] { return !len[k] || stop; });
-				if (stop) throw IoError(werr.empty() ? "the writer has stopped" : werr);
+				if (stop) throw lq_io_error(werr.empty() ? "the writer has stopped" : werr);
 			}
 			LQ_HIP_CHECK(hipEventRecord(ev0, c.stream));
 			fastq_launch(c, total, a, b, dev.as<u8>());

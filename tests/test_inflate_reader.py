@@ -7,7 +7,8 @@ everything a caller sees must be the host mode's:
   2. a bgzip multi-line FASTQ and a bgzip FASTA give the chunks and borders of the gzread path at two chunk sizes;
   3. run_file(bam, inflate="device") leaves the sdust table, the subsample and the adapter rows of the host mode;
   4. a flipped CRC byte, a flipped deflate byte and a file cut inside a block give LQCOV_E_IO with the host mode's message and offset;
-  5. lqreader_inflate after the first lqreader_next is LQCOV_E_STATE; a plain .gz FASTQ in device mode reads as before."""
+  5. lqreader_inflate after the first lqreader_next is LQCOV_E_STATE; a plain .gz FASTQ in device mode reads as before;
+  6. a missing path, a damaged block and a BAM stream cut inside a record are LQCOV_E_IO, a name that is not ASCII is LQCOV_E_DOMAIN."""
 import ctypes as C
 import gzip
 import struct
@@ -169,6 +170,58 @@ def check_state_and_plain_gzip(lib, tmp_path):
         chunkpass.FileChunks(plain, lib=lib, inflate="gpu")
 
 
+# ---- 6. which code an error gets: the file's are LQCOV_E_IO, a name that is not ASCII is LQCOV_E_DOMAIN in each of the three record paths ----
+def check_error_codes(lib, tmp_path, monkeypatch):
+    E_IO, E_DOMAIN = -2, -5
+
+    def fails(path, **kw):
+        fc = chunkpass.FileChunks(path, lib=lib, **kw)
+        with pytest.raises(api.LqcovError) as e:
+            list(fc)
+        return e.value.code, str(e.value).split(": ", 1)[1], fc                     # (behind "lqcov error <code>: ")
+
+    missing = str(tmp_path / "none" / "x.fq")
+    assert fails(missing)[:2] == (E_IO, "failed to open file '%s'" % missing)
+    w = chunkpass.FastqWriter(str(tmp_path / "none" / "out.fq"), lib=lib)          # (a path the library is to write)
+    ch = chunkpass.ReadChunk([["a", "ACGT", "IIII"]], lib=lib)
+    with pytest.raises(api.LqcovError) as e:
+        w.write(ch)
+    assert e.value.code == E_IO and ("failed to open file '%s': " % w.path) in str(e.value)
+    with pytest.raises(api.LqcovError):
+        w.close()
+    ch.close()
+    reads = [[b"r%d" % i, b"ACGTNACGTN" * (3 + i)] for i in range(12)]
+    stream = BW.bam_stream(reads)
+    # one damaged byte: the second block's CRC32
+    whole = bytearray(BW.bgzf(stream, 300))
+    second = struct.unpack_from("<H", whole, 16)[0] + 1
+    third = second + struct.unpack_from("<H", whole, second + 16)[0] + 1
+    whole[third - 8] ^= 0x01
+    path = str(tmp_path / "crc.bam")
+    open(path, "wb").write(bytes(whole))
+    for mode in ("host", "device"):
+        assert fails(path, inflate=mode)[:2] == (E_IO, "failed to open file '%s': BGZF block at file offset %d: CRC32 mismatch" % (path, second)), mode
+    # whole blocks, the BAM stream cut inside the last record
+    path = str(tmp_path / "cut.bam")
+    open(path, "wb").write(BW.bgzf(stream[:-7], 300))
+    for mode in ("host", "device"):
+        assert fails(path, inflate=mode)[:2] == (E_IO, "failed to open file '%s': BAM record 12: the file ends inside a record" % path), mode
+    # a name byte of 0x80 or more
+    what = "a read name holds a byte of 0x80 or more (read 3): not ASCII"
+    recs = [[b"n%d" % i, b"ACGT" * (5 + i), b"I" * (20 + 4 * i)] for i in range(5)]
+    recs[2][0] = b"n\xe9"
+    fq = str(tmp_path / "name.fq")
+    open(fq, "wb").write(TF.fastq_bytes(recs))
+    assert fails(fq)[:2] == (E_DOMAIN, what)
+    bam = str(tmp_path / "name.bam")
+    BW.write_bam(bam, [r[:2] for r in recs])
+    assert fails(bam)[:2] == (E_DOMAIN, what)
+    monkeypatch.setenv("LQREADER_PIECE_BYTES", "4096")
+    code, msg, fc = fails(fq, parse="device")
+    assert (code, msg) == (E_DOMAIN, what)
+    assert fc.parse_stats["records_device"] == 2 and fc.parse_stats["records_host"] == 0       # (it was the scan's rows that met it)
+
+
 def test_emulated_device_inflate_bam(emu_lib, tmp_path, monkeypatch):
     check_bam(emu_lib, tmp_path, monkeypatch)
 
@@ -187,6 +240,10 @@ def test_emulated_device_inflate_errors(emu_lib, tmp_path):
 
 def test_emulated_device_inflate_state_and_plain_gzip(emu_lib, tmp_path):
     check_state_and_plain_gzip(emu_lib, tmp_path)
+
+
+def test_emulated_error_codes(emu_lib, tmp_path, monkeypatch):
+    check_error_codes(emu_lib, tmp_path, monkeypatch)
 
 
 @pytest.mark.gpu
@@ -212,3 +269,8 @@ def test_gpu_device_inflate_errors(gpu_lib, tmp_path):
 @pytest.mark.gpu
 def test_gpu_device_inflate_state_and_plain_gzip(gpu_lib, tmp_path):
     check_state_and_plain_gzip(gpu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_gpu_error_codes(gpu_lib, tmp_path, monkeypatch):
+    check_error_codes(gpu_lib, tmp_path, monkeypatch)
