@@ -249,6 +249,15 @@ int lqcov_get_part_minimizers(lqcov_handle *h, int part, uint64_t *xy, uint64_t 
 /* chains of the last lqcov_part_map call: 9 int32 per chain
  * (query, rid, rev, score, cnt, qs, qe, rs, re), unordered. */
 int lqcov_get_chains(lqcov_handle *h, int32_t *out, uint64_t cap, uint64_t *n_total);
+/* The seed plan of a built part (made by lqcov_part_build when the queries are set; read-only, nothing is computed): the seed
+ * hits that can be part of a chain at all, as the first pass will write them.  info[0] = 1 if the plan holds filtered
+ * survivors (0: no filter ran, the first pass writes every hit, and there are no rows), info[1] = the hits a chain needs at
+ * least (n_min), info[2], info[3] = the queries [q_begin, q_end) the plan holds right now, in the engine's own order
+ * (lqcov_query_order).  off[0 .. q_end - q_begin] (up to off_cap entries): where every query's rows start.  rows (up to
+ * row_cap rows): 5 uint32 per survivor, in the order the plan keeps them -- query (engine order), target, relative strand,
+ * diagonal (target position - query coordinate + query length + 256), minimizer index inside the query.  *n_rows: the rows
+ * the plan holds; pass NULL buffers to get the sizes. */
+int lqcov_part_seed_survivors(lqcov_handle *h, int part, uint32_t info[4], uint64_t *off, uint64_t off_cap, uint32_t *rows, uint64_t row_cap, uint64_t *n_rows);
 
 /* Saturated uint16 match counters with the index parts spread over ranks (esterr.c:127-138: once a counter is at 65535 the
  * others depend on the order in which lq_cnt_match met the chains, hit.c:52-88 -- on one handle the engine replays that by

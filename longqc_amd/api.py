@@ -125,6 +125,7 @@ def load_library(path: Optional[str] = None):
         "lqcov_get_query_minimizers": (C.c_int, [H, C.c_void_p, C.c_void_p, u64p]),
         "lqcov_get_part_minimizers": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, u64p]),
         "lqcov_get_chains": (C.c_int, [H, C.c_void_p, C.c_uint64, u64p]),
+        "lqcov_part_seed_survivors": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
         "lqcov_sat_record_bytes": (C.c_uint32, []),
         "lqcov_counter_max": (C.c_uint32, [H]),
         "lqcov_counter_offsets": (C.c_int, [H, C.c_void_p]),
@@ -524,6 +525,18 @@ class Engine:
         out = np.zeros((n.value, 9), dtype=np.int32)
         self._ck(self.lib.lqcov_get_chains(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def part_seed_survivors(self, part: int) -> dict:
+        """tests: the seed plan of a built part -- dict(bucketed, n_min, q_begin, q_end, off = uint64[q_end - q_begin + 1],
+        rows = uint32[n, 5]: query (engine order), rid, relative strand, diagonal, minimizer index inside the query)"""
+        info = np.zeros(4, dtype=np.uint32)
+        n = C.c_uint64()
+        self._ck(self.lib.lqcov_part_seed_survivors(self.h, part, info.ctypes.data, None, 0, None, 0, C.byref(n)))
+        off = np.zeros(int(info[3]) - int(info[2]) + 1, dtype=np.uint64)
+        rows = np.zeros((n.value, 5), dtype=np.uint32)
+        self._ck(self.lib.lqcov_part_seed_survivors(self.h, part, info.ctypes.data, off.ctypes.data, off.shape[0], rows.ctypes.data, rows.shape[0], C.byref(n)))
+        assert n.value == rows.shape[0]
+        return dict(bucketed=bool(info[0]), n_min=int(info[1]), q_begin=int(info[2]), q_end=int(info[3]), off=off, rows=rows)
 
     # -- saturated counters with the parts spread over ranks (multigpu.PartRunner) --
     def counter_max(self) -> int:

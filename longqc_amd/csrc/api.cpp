@@ -559,6 +559,14 @@ int lqcov_get_chains(lqcov_handle *h, int32_t *out, uint64_t cap, uint64_t *n_to
 	});
 }
 
+int lqcov_part_seed_survivors(lqcov_handle *h, int part, uint32_t info[4], uint64_t *off, uint64_t off_cap, uint32_t *rows, uint64_t row_cap, uint64_t *n_rows)
+{
+	return guard(h, [&] {
+		const u64 n = h->part_seed_survivors(h->part(part), info, off, off_cap, rows, row_cap);
+		if (n_rows) *n_rows = n;
+	});
+}
+
 uint32_t lqcov_sat_record_bytes(void) { return (uint32_t)sizeof(SatRec); }
 
 uint32_t lqcov_counter_max(const lqcov_handle *h) { return h ? h->cnt_max : 0u; }

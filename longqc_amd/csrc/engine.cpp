@@ -1911,6 +1911,36 @@ bool lqcov_handle::plan_usable(const SeedPlan &S) const
 	return S.valid && S.mid_occ == mid_occ && S.n_q == q.n && S.n_qm == q.n_mini && S.h_aqf.empty() == K.ties_klib && !(S.bucketed && S.q_begin != 0);
 }
 
+// The survivors the part's plan holds right now, as the tests read them (lqcov_part_seed_survivors): info = {bucketed, n_min,
+// q_begin, q_end}, off = h_aqf[q_begin .. q_end], rows = the records of `surv` in the order they lie there, five words each:
+// query (engine order), rid, relative strand, diagonal, minimizer index inside the query.  Returns the rows the plan holds.
+u64 lqcov_handle::part_seed_survivors(Part &pt, u32 info[4], u64 *off, u64 off_cap, u32 *rows, u64 row_cap)
+{
+	if (!pt.built) throw std::logic_error("part not built");
+	const SeedPlan &S = pt.plan;
+	if (!plan_usable(S)) throw std::logic_error("the part has no valid seed plan (queries set before lqcov_part_build, LQCOV_PLAN_AHEAD, not LQCOV_TIES=klib)");
+	const u32 nq = S.q_end - S.q_begin;
+	if (info) { info[0] = S.bucketed ? 1u : 0u; info[1] = S.rec_nmin; info[2] = S.q_begin; info[3] = S.q_end; }
+	if (S.n_q == 0) return 0;
+	if (off) for (u64 i = 0; i <= nq && i < off_cap; ++i) off[i] = S.h_aqf[S.q_begin + i];
+	if (!S.bucketed) return 0;
+	const u64 n = S.h_aqf[S.q_end] - S.h_aqf[S.q_begin];
+	const u64 m = rows ? std::min(n, row_cap) : 0;
+	if (!m) return n;
+	std::vector<u64> rec(m);
+	d2h(rec.data(), S.surv.as<u64>(), m, stream);
+	const u32 jb = S.rec_jb, db = S.rec_db;
+	u32 qi = S.q_begin;
+	for (u64 i = 0; i < m; ++i) {
+		while (qi + 1 < S.q_end && S.h_aqf[qi + 1] - S.h_aqf[S.q_begin] <= i) ++qi;
+		const u64 r = rec[i];
+		u32 *o = rows + 5 * i;
+		o[0] = qi; o[1] = (u32)(r >> (jb + db + 1)); o[2] = (u32)(r >> (jb + db)) & 1u;
+		o[3] = (u32)(r >> jb) & ((1u << db) - 1u); o[4] = (u32)r & ((1u << jb) - 1u);
+	}
+	return n;
+}
+
 // the plan's buffers <-> the handle's work buffers of the same names
 void lqcov_handle::swap_plan(SeedPlan &S)
 {

@@ -289,6 +289,7 @@ struct lqcov_handle {
 	bool seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u32 n_min, u32 jb, u32 db, SeedJob &J);
 	bool seed_group(Part &pt, SeedPlan &S, bool swapped, hipStream_t s, Prim &pr, u32 q_begin);
 	void swap_plan(SeedPlan &S);
+	u64 part_seed_survivors(Part &pt, u32 info[4], u64 *off, u64 off_cap, u32 *rows, u64 row_cap);   // tests: the plan's survivors, decoded (lqcov_part_seed_survivors)
 	void map_part(Part &pt);
 	void map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_aq, const std::vector<u64> &h_aqf, const std::vector<u64> &h_qmoff, bool dbg);
 	void batch_buffers(MapLane &L, u64 nA);

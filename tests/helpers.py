@@ -124,3 +124,36 @@ def limits_dataset(d, seed=0, glen=12000, n_targets=20, n_queries=5, err=0.02, n
     tf, qf = os.path.join(str(d), "lim_all.fq"), os.path.join(str(d), "lim_sub.fq")
     synth.write_fastq(tf, readset("t", tseqs)); synth.write_fastq(qf, readset("q", qseqs))
     return tf, qf
+
+
+def seed_filter_dataset(d, seed=0, n_long=30, n_short=120):
+    """the set of tests/test_seed_filter.py -> (target names, target reads, query names, query reads): limits_dataset (overlaps
+    on both strands, tandem repeats) without its query of 6.8 kb, plus unrelated random targets -- n_long of 1.5-3.5 kb, whose
+    chance hits with -k 9 fall several to a pair and spread over its diagonals, and n_short of 300-900 bases, a good third of
+    whose pairs hold exactly one chance hit -- and copies of two queries under their own names (the self diagonal of -Y).  Half
+    of the random reads are named to sort below the queries, half above (-X)."""
+    from longqc_amd import synth
+    tf, qf = limits_dataset(d, seed=seed)
+    tn, ts, _ = read_fastx(tf)
+    qn, qs, _ = read_fastx(qf)
+    del qn[4], qs[4]                                            # (the long pair's query: one pair of thousands of hits)
+    rng = np.random.default_rng(7300 + seed)
+    for i in range(n_long + n_short):
+        L = int(rng.integers(1500, 3500)) if i < n_long else int(rng.integers(300, 900))
+        tn.append("%s%03d" % ("a" if i % 2 else "u", i)); ts.append(synth._ACGT[rng.integers(0, 4, size=L, dtype=np.uint8)])
+    for i in (0, 4):
+        tn.append(qn[i]); ts.append(qs[i].copy())
+    return tn, ts, qn, qs
+
+
+def seed_filter_long_pair(seed=0, L=9000):
+    """a target and a query of about 9 kb that overlap at 6 % errors, under eight unrelated targets of 1.2 kb and two unrelated
+    queries of 2 kb: with bw 0 the long pair's diagonals take more than 8192 bins of two, and the histograms of all the other
+    pairs of a query still fit one bucket's space -> (target names, target reads, query names, query reads)"""
+    from longqc_amd import synth
+    rng = np.random.default_rng(7400 + seed)
+    rnd = lambda n: synth._ACGT[rng.integers(0, 4, size=n, dtype=np.uint8)]
+    g = rnd(L + 600)
+    ts = [synth._mutate(g[:L], rng, 0.06, (3, 3, 4))] + [rnd(1200) for _ in range(8)]
+    qs = [synth._mutate(g[600:], rng, 0.06, (3, 3, 4)), rnd(2000), rnd(2000)]
+    return ["t%03d" % i for i in range(len(ts))], ts, ["q%03d" % i for i in range(len(qs))], qs
