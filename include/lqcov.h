@@ -508,6 +508,37 @@ int  lqreader_parse_stats(const lqreader *r, lqparse_stats *stats);
 int  lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, int last_char, uint32_t *rows, uint64_t n_rows_cap,
                uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg,
                uint64_t *resume_pos, int *resume_last_char);
+/* Inflated bytes that stay on the device, opt-in: lqreader_host_copy(r, LQREADER_HOSTCOPY_NEEDED) -- before the first
+ * lqreader_next, LQCOV_E_STATE afterwards; the default is LQREADER_HOSTCOPY_ALL, or what the environment variable LQREADER_HOSTCOPY
+ * ("needed") says when the reader is opened.  The mode is active for a FASTA/FASTQ file that the device both inflates and parses
+ * (lqreader_inflate and lqreader_parse in their device modes, a BGZF or gzip file); any other reader accepts it and ignores it.
+ * When it is active the inflated bytes are not copied back: k_crc32_ranges makes every member's CRC32 from the chunk's raw device
+ * buffer (BGZF: one value per block; gzip spans: the bytes a launch accepted, folded into the member's value by length; what zlib
+ * inflates on the host is checked there as before), k_fx_names gathers the names of the records the device vouches for, and the
+ * host fetches only what its own parser has to look at: the bytes from the parser's position to the end of the piece, when the
+ * scan stops in front of them.  Chunks, borders, counts, names, statistics and errors are those of LQREADER_HOSTCOPY_ALL.
+ * lqreader_copy_stats says what moved.
+ * lqcrc32_ranges is the array-level call of k_crc32_ranges: crc_out[i] = zlib's crc32(0, bytes + off[i], len[i]) for i < n, 0 for an
+ * empty range; the ranges may touch or overlap.  LQCOV_E_ARG: null buffers, a range outside [0, n_bytes).
+ * lqfx_names is the array-level call of k_fx_names: rows as lqfx_scan writes them (4 words per row; the name of row i is
+ * bytes[rows[4 i] .. + rows[4 i + 1])); names_out gets every name followed by one NUL, name_off_out the n_rows + 1 offsets, *first_bad
+ * the first row whose name holds a byte of 0x80 or more (n_rows: none).  LQCOV_E_ARG: null buffers, a name outside bytes, names_cap
+ * smaller than the blob.  The message of both: lqreader_last_error(NULL). */
+#define LQREADER_HOSTCOPY_ALL    0
+#define LQREADER_HOSTCOPY_NEEDED 1
+typedef struct lqcopy_stats {
+	uint64_t active;             /* 1: the mode is LQREADER_HOSTCOPY_NEEDED and this reader can honour it */
+	uint64_t bytes_inflated;     /* inflated bytes of the file so far (device inflate only) */
+	uint64_t bytes_to_host;      /* of those: copied from the raw device buffer into the piece (rows and names are not counted) */
+	uint64_t bytes_crc_device;   /* bytes whose CRC32 k_crc32_ranges made */
+	uint64_t bytes_crc_host;     /* bytes whose CRC32 zlib made on the host */
+	uint64_t names_device;       /* names that came from k_fx_names */
+} lqcopy_stats;
+int  lqreader_host_copy(lqreader *r, int mode);
+int  lqreader_copy_stats(const lqreader *r, lqcopy_stats *stats);
+int  lqcrc32_ranges(int device, const uint8_t *bytes, uint64_t n_bytes, uint32_t n, const uint64_t *off, const uint64_t *len, uint32_t *crc_out);
+int  lqfx_names(int device, const uint8_t *bytes, uint64_t n, const uint32_t *rows, uint64_t n_rows, char *names_out, uint64_t names_cap,
+                uint64_t *name_off_out, uint64_t *first_bad);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 /* ---- the chunk loop's files: trimmed reads (longQC.py:345-346) and the FASTQ a BAM file is converted to (:302-303) ------------------ */

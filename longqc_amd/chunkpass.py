@@ -55,6 +55,10 @@ def _lib(lib=None):
             "lqreader_parse": (C.c_int, [H, C.c_int]),
             "lqreader_parse_stats": (C.c_int, [H, P]),
             "lqfx_scan": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint64, C.c_int, P, C.c_uint64, P, P, C.c_uint64, P, P, P, P, P]),
+            "lqreader_host_copy": (C.c_int, [H, C.c_int]),
+            "lqreader_copy_stats": (C.c_int, [H, P]),
+            "lqcrc32_ranges": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
+            "lqfx_names": (C.c_int, [C.c_int, P, C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P]),
             "lqchunk_fastq": (C.c_int, [H, C.c_char_p, P, P, P, P, C.c_uint64, P]),
             "lqfastq_open": (H, [C.c_char_p, C.c_int, C.c_uint64]),
             "lqfastq_write": (C.c_int, [H, H, C.c_char_p, P, P, P, P]),
@@ -183,6 +187,53 @@ def scan_records(data, start_pos: int = 0, last_char: int = 0, device: int = 0, 
     if rc != 0:
         raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
     return rows[:n_rows.value].copy(), sseg[:n_s.value].copy(), qseg[:n_q.value].copy(), (r_pos.value, r_lc.value)
+
+
+HOSTCOPY_MODES = {"all": 0, "needed": 1}
+COPY_STATS = ("active", "bytes_inflated", "bytes_to_host", "bytes_crc_device", "bytes_crc_host", "names_device")
+
+
+def host_copy_mode(host_copy):
+    """"all" | "needed" | None (the environment variable LQREADER_HOSTCOPY, "all" without it) -> the mode's name"""
+    mode = os.environ.get("LQREADER_HOSTCOPY", "all") if host_copy is None else host_copy
+    if mode not in HOSTCOPY_MODES:
+        raise ValueError("host_copy must be 'all' or 'needed', not %r" % (mode,))
+    return mode
+
+
+def crc32_ranges(data, off, length, device: int = 0, lib=None):
+    """zlib.crc32 of data[off[i] : off[i] + length[i]] for every i, made on the device (lqcrc32_ranges: k_crc32_ranges).  The ranges may
+    start anywhere, have any length, touch and overlap; an empty range gives 0.  -> uint32[n].  A range outside data raises LqcovError
+    (-1)."""
+    lib = _lib(lib)
+    buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), dtype=np.uint8)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off, length = np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(length, dtype=np.uint64)
+    n = off.shape[0]
+    if length.shape[0] != n:
+        raise ValueError("off and length differ in length")
+    out = np.zeros(max(n, 1), np.uint32)
+    rc = lib.lqcrc32_ranges(device, buf.ctypes.data if buf.shape[0] else None, buf.shape[0], n, off.ctypes.data, length.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return out[:n]
+
+
+def gather_names(data, rows, device: int = 0, lib=None):
+    """The names of scan_records' rows, gathered on the device (lqfx_names: k_fx_names): -> (blob: every name followed by one NUL,
+    bytes; name_off uint64[n + 1]: where each starts, the last one the blob's length; first_bad: the first row whose name holds a
+    byte of 0x80 or more, n if none)"""
+    lib = _lib(lib)
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 4)
+    n = rows.shape[0]
+    cap = int(rows[:, 1].astype(np.uint64).sum()) + n
+    names, name_off, first_bad = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.uint64), C.c_uint64()
+    rc = lib.lqfx_names(device, buf.ctypes.data if buf.shape[0] else None, buf.shape[0], rows.ctypes.data if n else None, n, names.ctypes.data, cap,
+                        name_off.ctypes.data, C.byref(first_bad))
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return names[:int(name_off[n])].tobytes(), name_off, int(first_bad.value)
 
 
 class ReadChunk:
@@ -359,11 +410,17 @@ class FileChunks:
     length: LQREADER_GZ_SPAN_BYTES); inflate_stats (a dict of INFLATE_STATS) says after iteration what that took.
     parse="device": the records of a FASTA/FASTQ file are found on the device (k_fx_*, lqreader_parse) wherever it vouches for them,
     by the host parser elsewhere; "host": by the host parser; None: the environment variable LQREADER_PARSE, "host" without it.  The
-    chunks are the same; parse_stats (a dict of PARSE_STATS) says after iteration who found what.  A BAM file ignores the mode."""
+    chunks are the same; parse_stats (a dict of PARSE_STATS) says after iteration who found what.  A BAM file ignores the mode.
+    host_copy="needed": where the device both inflates and parses a FASTA/FASTQ file, the inflated bytes stay there -- the members'
+    CRC32 (k_crc32_ranges) and the names (k_fx_names) are made on the device and the host fetches only what its own parser must see;
+    "all": every inflated byte comes back; None: the environment variable LQREADER_HOSTCOPY, "all" without it.  Any other file or
+    mode ignores it.  The chunks are the same; copy_stats (a dict of COPY_STATS) says after iteration what moved."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
-                 lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None, parse: Optional[str] = None):
+                 lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None, parse: Optional[str] = None,
+                 host_copy: Optional[str] = None):
         self.lib = _lib(lib)
+        self.host_copy, self.copy_stats = host_copy_mode(host_copy), dict.fromkeys(COPY_STATS, 0)
         self.inflate = inflate_mode(inflate)
         self.parse, self.parse_stats = parse_mode(parse), dict.fromkeys(PARSE_STATS, 0)
         self.path, self.is_upper, self.device, self.n_threads = path, is_upper, device, n_threads
@@ -380,7 +437,7 @@ class FileChunks:
         try:
             self.format = lib.lqreader_format(r)
             for rc in (lib.lqreader_bam_qualities(r, 1) if not self.is_sequel else 0, lib.lqreader_inflate(r, INFLATE_MODES[self.inflate]),
-                       lib.lqreader_parse(r, PARSE_MODES[self.parse])):
+                       lib.lqreader_parse(r, PARSE_MODES[self.parse]), lib.lqreader_host_copy(r, HOSTCOPY_MODES[self.host_copy])):
                 if rc != 0:
                     raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
             chunk = ReadChunk(None, device=self.device, lib=lib)
@@ -398,6 +455,9 @@ class FileChunks:
             ps = (C.c_uint64 * len(PARSE_STATS))()
             if lib.lqreader_parse_stats(r, ps) == 0:
                 self.parse_stats = dict(zip(PARSE_STATS, (int(w) for w in ps)))
+            cs = (C.c_uint64 * len(COPY_STATS))()
+            if lib.lqreader_copy_stats(r, cs) == 0:
+                self.copy_stats = dict(zip(COPY_STATS, (int(w) for w in cs)))
             lib.lqreader_close(r)
             if chunk is not None:
                 chunk.close()
@@ -564,9 +624,10 @@ class SampleQCPass:
         return result
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
-                 is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None):
-        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse:
-        FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
+                 is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None,
+                 host_copy: Optional[str] = None):
+        """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse,
+        host_copy: FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
         trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
         appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
         `trimmed` stays None and `trimmed_chunks` empty.  fastx_out=<path>: every chunk is appended to that file untrimmed -- the
@@ -585,7 +646,7 @@ class SampleQCPass:
                 self.fastx_writer = FastqWriter(fastx_out, device=self.device, lib=self.lib)
                 writers.append(self.fastx_writer)
             for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
-                                                        inflate=inflate, parse=parse):
+                                                        inflate=inflate, parse=parse, host_copy=host_copy):
                 if fastx_out is not None:
                     self.fastx_writer.write(chunk)                                                      # longQC.py:302-303
                 results.append(self.add_resident(chunk, trim=trim))

@@ -6,7 +6,8 @@
 // is in device mode).  The second way, opt-in: `device` set, the listed blocks are inflated by k_bgzf_inflate (kernels_inflate.hpp) --
 // the owner's hook uploads the compressed bytes, launches and brings the inflated bytes back to dst and one status per block -- and
 // the pool only checks the CRC32 of what came back, which vouches for the kernel and for the copy alike.  The errors are the same
-// three, for the same blocks.
+// three, for the same blocks.  Where the hook leaves the bytes on the device (reader.cpp, lqreader_host_copy) it fills dev_crc with
+// the blocks' CRC32 as the device computed them, and those are compared instead.
 #pragma once
 #include "lq_cabi.hpp"
 #include <zlib.h>
@@ -31,6 +32,7 @@ struct BgzfInflater {
 	// device mode: inflate `blocks` (their bytes: win) into dst[0 .. out_bytes) -> status[i]: 0 fine, 1 not a deflate stream, other: the
 	// stream does not give isize bytes (LQ_INF_* of kernels_inflate.hpp)
 	std::function<void(const std::vector<Block> &blocks, const u8 *win, u8 *dst, u64 out_bytes, std::vector<u32> &status)> device;
+	std::vector<u32> dev_crc;                                 // `device` may fill it, one CRC32 per block: dst then holds nothing
 
 	[[noreturn]] static void fail(u64 at, const char *what)
 	{
@@ -117,7 +119,9 @@ struct BgzfInflater {
 	void inflate_all(const std::vector<Block> &blocks, u8 *dst, u64 out_bytes)
 	{
 		std::vector<u32> status;
+		dev_crc.clear();
 		if (device) device(blocks, win.data(), dst, out_bytes, status);
+		const bool crc_known = dev_crc.size() == blocks.size() && !blocks.empty();
 		const u32 nt = (u32)std::min<u64>((u64)std::max(n_threads, 1), blocks.size());
 		std::atomic<u64> turn{0};
 		std::vector<u64> bad_at(nt, LQ_U64MAX); std::vector<const char*> bad(nt, nullptr);
@@ -127,7 +131,7 @@ struct BgzfInflater {
 					const Block &b = blocks[i];
 					const char *what = nullptr;
 					if (status[i]) what = status[i] == 1 ? "corrupt deflate stream" : "ISIZE does not match the inflated bytes";
-					else if ((u32)crc32(crc32(0L, Z_NULL, 0), dst + b.out, (uInt)b.isize) != b.crc) what = "CRC32 mismatch";
+					else if ((crc_known ? dev_crc[i] : (u32)crc32(crc32(0L, Z_NULL, 0), dst + b.out, (uInt)b.isize)) != b.crc) what = "CRC32 mismatch";
 					if (what && b.at < bad_at[w]) { bad_at[w] = b.at; bad[w] = what; }
 				}
 				return;

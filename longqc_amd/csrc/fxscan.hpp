@@ -1,6 +1,7 @@
 // longqc_amd/csrc/fxscan.hpp -- the host side of kernels_fxscan.hpp: one record scan over a range of bytes on the device.  The tables
 // stay on the device (sseg, qseg, info: what the reader rebases into a chunk's lists); the rows, the counts and the resume state
-// come back.  Three waits per scan: the number of lines, the number of records, the rows.
+// come back.  Three waits per scan: the number of lines, the number of records, the rows.  names(): the names of rows, gathered on
+// the device (k_fx_names), for a host that does not hold the bytes; two waits, the blob's length and the blob.
 #pragma once
 #include "kernels_fxscan.hpp"
 #include <vector>
@@ -67,6 +68,33 @@ struct FxScan {
 		LQ_HIP_CHECK(hipMemcpyAsync(h_res, resume.p, 8, hipMemcpyDeviceToHost, stream));
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 		resume_pos = h_res[0]; resume_last_char = (int)h_res[1];
+	}
+
+	// the names of d_rows[0 .. n) (rows on the device; positions count from d): h_names = every name and a NUL, h_name_off its n + 1
+	// offsets, first_bad the first row whose name holds a byte of 0x80 or more (n: none)
+	DBuf ncols, d_names, d_name_off;
+	std::vector<char> h_names; std::vector<u64> h_name_off; u64 first_bad = 0;
+	void names(hipStream_t stream, const u8 *d, const FxRow *d_rows, u64 n)
+	{
+		h_names.clear(); h_name_off.assign((size_t)n + 1, 0); first_bad = n;
+		if (!n) return;
+		const u64 n_tiles = (n + LQ_FXSCAN_LINE_TILE - 1) / LQ_FXSCAN_LINE_TILE;
+		ncols.ensure((size_t)n_tiles * 8); totals.ensure(16 * 8); d_name_off.ensure((size_t)(n + 1) * 8);
+		u64 *tot = totals.as<u64>();
+		LQ_LAUNCH(k_fx_names, grid(n_tiles), LQ_FXSCAN_THREADS, stream, d, d_rows, n, ncols.as<u64>(), 0, (char*)nullptr, (u64*)nullptr, (unsigned long long*)(tot + 13));
+		LQ_LAUNCH(k_fx_tilescan, 1, LQ_FXSCAN_THREADS, stream, ncols.as<u64>(), n_tiles, 1u, tot + 12);
+		LQ_HIP_CHECK(hipGetLastError());
+		u64 bytes = 0;
+		LQ_HIP_CHECK(hipMemcpyAsync(&bytes, tot + 12, 8, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		d_names.ensure((size_t)bytes);
+		LQ_LAUNCH(k_fx_names, grid(n_tiles), LQ_FXSCAN_THREADS, stream, d, d_rows, n, ncols.as<u64>(), 1, d_names.as<char>(), d_name_off.as<u64>(), (unsigned long long*)(tot + 13));
+		LQ_HIP_CHECK(hipGetLastError());
+		h_names.resize((size_t)bytes);
+		LQ_HIP_CHECK(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)bytes, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(h_name_off.data(), d_name_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(&first_bad, tot + 13, 8, hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	}
 
 	// where record r's segments start in sseg / qseg (r == n_rows: their ends)

@@ -18,9 +18,13 @@
 // the bit offset, inflateSetDictionary for the window): a span that reports an error, a marker in front of the member's first byte,
 // a block that does not fit a span's region even after the region was doubled once.  zlib's verdict decides, and its bytes go on
 // as if the device had made them.
+// keep_on_device (reader.cpp, lqreader_host_copy): the accepted bytes do not come back.  Their CRC32 is k_crc32_ranges' over the
+// caller's device buffer, folded into the member's by length; the member's last 32 KiB then exist only as the device's window behind
+// the last accepted span (d_wins), and come to hwin when zlib needs them as its dictionary.
 #pragma once
 #include "lq_cabi.hpp"
 #include "kernels_gzip.hpp"
+#include "kernels_crc32.hpp"
 #include <zlib.h>
 #include <unistd.h>
 #include <functional>
@@ -36,6 +40,10 @@ struct GzipInflater {
 	std::function<u8*(u8 *dst, u64 n)> dev_room;
 	lqinflate_stats stats{};
 	bool done = false;                                        // nothing more comes
+	bool keep_on_device = false;                              // what a launch accepts is not copied to dst
+	lqcopy_stats *copied = nullptr;                           // the owner's account of what moved and who made the CRC32
+	CrcDev crcdev;
+	bool hwin_dev = false;                                    // hwin is stale: the window is d_wins[win_slot]
 
 	enum { HEADER = 0, BODY, ZBLOCK, TRAILER };
 	int state = HEADER;
@@ -89,8 +97,32 @@ struct GzipInflater {
 		return cw_len;
 	}
 
+	u64 hist() const { return std::min<u64>(isize, LQ_GZ_WIN); }      // hwin's size, where hwin is on the host
+
+	void fetch_hwin()                                         // the window comes to the host
+	{
+		const u64 h = hist();
+		hwin.resize((size_t)h);
+		if (h) {
+			LQ_HIP_CHECK(hipMemcpyAsync(hwin.data(), d_wins.as<u8>() + win_slot * LQ_GZ_WIN + (LQ_GZ_WIN - h), (size_t)h, hipMemcpyDeviceToHost, stream));
+			LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		}
+		hwin_dev = false;
+	}
+
+	void made_on_device(const u8 *d_p, u64 n)                 // n bytes of the member have come out and lie at d_p on the device
+	{
+		const u64 zero = 0; u32 c = 0;
+		crcdev.run(stream, d_p, 1, &zero, &n, &c);
+		crc = (u32)crc32_combine(crc, c, (z_off_t)n);
+		isize += n;
+		hwin_dev = true;
+		if (copied) copied->bytes_crc_device += n;
+	}
+
 	void made(const u8 *p, u64 n)                             // n bytes of the member have come out
 	{
+		if (copied) copied->bytes_crc_host += n;
 		for (u64 o = 0; o < n; o += 1u << 30) crc = (u32)crc32(crc, p + o, (uInt)std::min<u64>(n - o, 1u << 30));
 		isize += n;
 		if (n >= LQ_GZ_WIN) hwin.assign(p + n - LQ_GZ_WIN, p + n);
@@ -158,7 +190,7 @@ struct GzipInflater {
 				continue;
 			}
 			first_member = false;
-			pos_bit = (at + q) * 8; hwin.clear(); crc = (u32)crc32(0L, Z_NULL, 0); isize = 0; dwin_ok = false; doubled = false;
+			pos_bit = (at + q) * 8; hwin.clear(); hwin_dev = false; crc = (u32)crc32(0L, Z_NULL, 0); isize = 0; dwin_ok = false; doubled = false;
 			state = BODY;
 			return;
 		}
@@ -210,7 +242,7 @@ struct GzipInflater {
 		std::vector<GzJob> jobs;
 		for (u32 s = 0; s < n_spans; ++s) if (start[s] != LQ_GZ_NONE && (s == 0 || start[s] > first_bit)) {
 			if (!jobs.empty()) jobs.back().stop_bit = start[s];
-			jobs.push_back({(u64)jobs.size() * reg, start[s], LQ_GZ_NONE, reg, s == 0 ? (u32)hwin.size() : LQ_GZ_NONE});
+			jobs.push_back({(u64)jobs.size() * reg, start[s], LQ_GZ_NONE, reg, s == 0 ? (u32)hist() : LQ_GZ_NONE});
 		}
 		const u32 nj = (u32)jobs.size();
 		stats.spans_found += nj - 1;
@@ -231,14 +263,16 @@ struct GzipInflater {
 			if (r.status == LQ_GZ_INPUT && !cw_eof) { r.status = LQ_GZ_OK; short_window = r.end_bit == r.start_bit; }      // the window's end, not the file's
 			if (r.end_bit == r.start_bit) { why = r.status; break; }       // not one whole block
 			if (cum + r.n_out > room) { no_room = true; if (acc.empty()) *need = r.n_out; break; }
-			acc.push_back({jobs[j].sym_off, cum, r.n_out, (u32)std::min<u64>(hwin.size() + cum, LQ_GZ_WIN)});
+			acc.push_back({jobs[j].sym_off, cum, r.n_out, (u32)std::min<u64>(hist() + cum, LQ_GZ_WIN)});
 			cum += r.n_out; expect = r.end_bit;
 			if (r.saw_final) { final = true; break; }
 			if (r.status != LQ_GZ_OK) { why = r.status; break; }
 		}
 		u32 n_acc = (u32)acc.size();
+		u8 *d_out = nullptr;
 		if (n_acc) {
-			u8 *d_out = dev_room(dst, cum);
+			d_out = dev_room(dst, cum);
+			if (hwin_dev && !dwin_ok) fetch_hwin();
 			d_acc.ensure((size_t)n_acc * sizeof(GzAcc)); d_status.ensure((size_t)n_acc * 4); d_markers.ensure(8);
 			const u64 slots = (u64)n_acc + 1;
 			if (d_wins.cap < slots * LQ_GZ_WIN) {                     // (the window of the launch before moves with it)
@@ -259,7 +293,7 @@ struct GzipInflater {
 			std::vector<u32> status(n_acc); unsigned long long markers = 0;
 			LQ_HIP_CHECK(hipMemcpyAsync(status.data(), d_status.p, (size_t)n_acc * 4, hipMemcpyDeviceToHost, stream));
 			LQ_HIP_CHECK(hipMemcpyAsync(&markers, d_markers.p, 8, hipMemcpyDeviceToHost, stream));
-			if (cum) LQ_HIP_CHECK(hipMemcpyAsync(dst, d_out, (size_t)cum, hipMemcpyDeviceToHost, stream));
+			if (cum && !keep_on_device) LQ_HIP_CHECK(hipMemcpyAsync(dst, d_out, (size_t)cum, hipMemcpyDeviceToHost, stream));
 			LQ_HIP_CHECK(hipStreamSynchronize(stream));
 			stats.markers_resolved += markers;
 			for (u32 k = 0; k < n_acc; ++k) if (status[k]) {          // a marker in front of the member: zlib's from that span on
@@ -267,10 +301,13 @@ struct GzipInflater {
 				final = false; no_room = false; why = LQ_GZ_INVALID;
 				break;
 			}
-			dwin_ok = n_acc == acc.size(); win_slot = n_acc;
+			// (the window behind the last span that counts is whole whatever a later span's markers pointed at: where the bytes stay on
+			// the device it is the only copy of the member's last bytes)
+			dwin_ok = keep_on_device || n_acc == acc.size(); win_slot = n_acc;
 		}
 		if (n_acc) {
-			made(dst, cum);
+			if (keep_on_device) made_on_device(d_out, cum);
+			else { made(dst, cum); if (copied) copied->bytes_to_host += cum; }
 			stats.spans_accepted += n_acc - 1; stats.bytes_device += cum;
 			const u64 in_bits = expect - first_bit;
 			if (in_bits >= 8 * (u64)span_bytes) ratio = std::min(std::max((double)cum * 8 / (double)in_bits, 1.0), 1000.0);
@@ -309,6 +346,7 @@ struct GzipInflater {
 				if (fetch(z_next, &byte, 1) == 1) { inflatePrime(&z, 8 - (int)r, byte >> r); ++z_next; }
 			}
 			z_first = z_next;
+			if (hwin_dev) fetch_hwin();
 			if (!hwin.empty()) inflateSetDictionary(&z, hwin.data(), (uInt)hwin.size());
 			z_active = true;
 			z_in.resize(1 << 16);

@@ -19,6 +19,9 @@
 //   k_fx_emit        counts (phase 0), then the 16-byte row of every vouched record in file order (phase 1) and one GatherSeg per line
 //                    that gives bytes (phase 2, one lane per line).
 //   k_fx_tilescan    the exclusive scan of the per-tile counts (one block; a piece has a few thousand tiles).
+//   k_fx_names       the names of the vouched records as the chunk keeps them -- each followed by one NUL, and n + 1 offsets -- and the
+//                    first row whose name holds a byte of 0x80 or more: with them the host needs no byte of a vouched record
+//                    (lqreader_host_copy).  Counts per tile of rows (phase 0), k_fx_tilescan, the copy (phase 1).
 //   k_fx_rebase, k_fx_tileseg   the reader's and lq_chunk_gather's: segments moved into a chunk's lists, the gather's per-tile table.
 // Grids are capped and the tiles strided over the blocks, as in every chunk-step kernel.  LDS: one word per wave for the block scans.
 #pragma once
@@ -319,6 +322,35 @@ k_fx_emit(const u8 *base, u32 org, const uint4 *L4, const uint2 *L2, u32 n_lines
 			const u32 at2 = has_qual ? L4[e + 1].x : L4[m].x + 1;
 			resume[0] = at2 - org; resume[1] = has_qual ? 0 : base[L4[m].x];
 		}
+	}
+}
+
+// d: the bytes the rows' positions count from.  phase 0: cols[t] = the bytes of tile t's names, a NUL behind each; *first_bad = n_rows.
+// phase 1 (cols scanned): names[name_off[i] ..) = the name of row i and a NUL, name_off[n_rows] = the blob's length; *first_bad = the
+// first row whose name holds a byte of 0x80 or more.  One lane per row: a name is a few tens of bytes.
+static __global__ void __launch_bounds__(LQ_FXSCAN_THREADS, 8)
+k_fx_names(const u8 *d, const FxRow *rows, u64 n_rows, u64 *cols, int phase, char *names, u64 *name_off, unsigned long long *first_bad)
+{
+	__shared__ u64 wsum[LQ_FXSCAN_THREADS / 64];
+	if (!phase && blockIdx.x == 0 && threadIdx.x == 0) *first_bad = n_rows;
+	const u64 n_tiles = (n_rows + LQ_FXSCAN_LINE_TILE - 1) / LQ_FXSCAN_LINE_TILE;
+	for (u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+		const u64 i = t * LQ_FXSCAN_LINE_TILE + threadIdx.x;
+		const bool live = i < n_rows;
+		u32 at = 0, len = 0;
+		if (live) { const FxRow w = rows[i]; at = w.name_at; len = w.name_len; }
+		u64 tot;
+		const u64 ex = lq_fx_block_scan(live ? (u64)len + 1 : 0, wsum, &tot);
+		if (!phase) { if (threadIdx.x == 0) cols[t] = tot; continue; }
+		if (!live) continue;
+		const u64 o = cols[t] + ex;
+		name_off[i] = o;
+		if (i + 1 == n_rows) name_off[n_rows] = o + len + 1;
+		const u8 *src = d + at;
+		u32 high = 0;
+		for (u32 k = 0; k < len; ++k) { const u8 c = src[k]; names[o + k] = (char)c; high |= c; }
+		names[o + len] = 0;
+		if (high & 0x80) atomicMin(first_bad, (unsigned long long)i);
 	}
 }
 

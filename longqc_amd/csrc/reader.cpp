@@ -23,6 +23,11 @@
 // they come back into the piece for the host to parse and to check their CRC32.  The raw buffer then mirrors the piece from up_from to
 // fill.  A bgzip FASTA/FASTQ is inflated the same way, any other gzip file by speculative spans (gzip.hpp, kernels_gzip.hpp).
 //
+// lqreader_host_copy(r, LQREADER_HOSTCOPY_NEEDED), for a FASTA/FASTQ file that the device both inflates and parses: the inflated bytes
+// stay in the raw buffer.  k_crc32_ranges (kernels_crc32.hpp) makes the members' CRC32 there, k_fx_names (kernels_fxscan.hpp) the names
+// of the records the scan vouches for, and the piece on the host holds only what host_bytes() has fetched: buf[v_lo .. v_hi), brought
+// up to [pos - 1, fill) whenever parse_one is about to look.
+//
 // The parts: a Source (pread, gzread, BGZF blocks or gzip spans, chosen once) fills the Piece; parse_one, parse_bam_one (BamHeader) or
 // DeviceParse (fxscan.hpp) finds the records, and each joins the chunk through ChunkParts::append_read: names, offsets, counts, the
 // chunk rule.  What a Source finds wrong with its file is an lq_file_error; read_more gives it the path (LQCOV_E_IO by type).
@@ -30,6 +35,7 @@
 #include "fastx_mem.hpp"
 #include "bgzf.hpp"
 #include "kernels_inflate.hpp"
+#include "kernels_crc32.hpp"
 #include "gzip.hpp"
 #include "fxscan.hpp"
 #include <zlib.h>
@@ -162,10 +168,11 @@ struct ChunkParts {
 	}
 
 	// one more read, whichever parser found it; true: the chunk rule ends the chunk with it
-	bool append_read(const u8 *name, u64 name_len, u64 seq_len)
+	// (ascii: the name is known to hold no byte of 0x80 or more)
+	bool append_read(const u8 *name, u64 name_len, u64 seq_len, bool ascii = false)
 	{
 		if (lens.size() == 0xffffffffULL) throw std::domain_error("more than 2^32-1 reads in one chunk");
-		for (u64 i = 0; i < name_len; ++i) if (name[i] >= 0x80)
+		for (u64 i = 0; i < name_len && !ascii; ++i) if (name[i] >= 0x80)
 			throw std::domain_error("a read name holds a byte of 0x80 or more (read " + std::to_string(n_seqs + 1) + "): not ASCII");
 		names.insert(names.end(), name, name + name_len); names.push_back('\0');
 		name_off.push_back(names.size());
@@ -237,6 +244,7 @@ struct DeviceParse {
 	u64 cur = 0, org = 0, seg_s = 0, seg_q = 0, base_d = 0;   // the last scan's rows from cur on wait for a chunk: the piece byte its positions count from, record cur's first segments and base
 	bool fresh = true, scanned = false, fb_counted = false, fb_at_end = false;      // bytes have come since the last scan; this piece has been scanned; that scan counts as a fallback / would if more records followed
 	u64 host_recs = 0, skip = 0, backoff = 0;                 // records the host parser has made since the last scan; scans that found nothing wait for 1, 2, 4 .. of them
+	lqcopy_stats *names_dev = nullptr;                        // not null: the piece does not hold the rows' names, k_fx_names brings them (the owner's account)
 
 	bool rows_waiting() const { return cur < fx.n_rows; }
 	void on_bytes() { ++pst.pieces; fresh = true; scanned = false; }
@@ -263,6 +271,7 @@ struct DeviceParse {
 		scanned = true; fb_counted = fb_at_end = false;
 		if (!fx.n_rows) { backoff = backoff ? std::min<u64>(backoff * 2, 1u << 20) : 1; skip = backoff; return false; }
 		backoff = skip = 0;
+		if (names_dev) fx.names(stream, ck.raw.as<u8>() + ck.raw_used, fx.rows.as<FxRow>(), fx.n_rows);
 		return true;
 	}
 
@@ -273,8 +282,10 @@ struct DeviceParse {
 		const u64 dst0 = ck.off.back();
 		bool ended = false;
 		while (cur < fx.n_rows && !ended) {
-			const FxRow &w = fx.h_rows[cur++];
-			ended = ck.append_read(pc.buf + org + w.name_at, w.name_len, w.seq_len);
+			const FxRow &w = fx.h_rows[cur];
+			if (names_dev) { ended = ck.append_read((const u8*)fx.h_names.data() + fx.h_name_off[cur], w.name_len, w.seq_len, cur < fx.first_bad); ++names_dev->names_device; }
+			else ended = ck.append_read(pc.buf + org + w.name_at, w.name_len, w.seq_len);
+			++cur;
 			++pst.records_device;
 		}
 		ck.flush_host_segs(stream);
@@ -306,6 +317,11 @@ struct lqreader {
 	bool gzip = false, bgzf_text = false;                     // the file begins with gzip's magic; it is BGZF and not BAM
 	bool bam_qual = false;                                       // the qualities come from the file
 	int inflate_mode = LQREADER_INFLATE_HOST, parse_mode = LQREADER_PARSE_HOST;   // lqreader_inflate's, lqreader_parse's
+	int host_copy = LQREADER_HOSTCOPY_ALL;                    // lqreader_host_copy's
+	bool keep = false;                                        // ... and it is active: the inflated bytes stay on the device
+	u64 v_lo = 0, v_hi = 0;                                   // keep: buf[v_lo .. v_hi) is what the host holds of the piece
+	lqcopy_stats cst = {0, 0, 0, 0, 0, 0};
+	CrcDev crcdev; DBuf raw_next;
 	bool started = false;                                     // lqreader_next has been called: the modes are final, and with them
 	bool dev_parse = false, mirror = false;                   // ... the device parse is on; the raw buffer holds buf[up_from .. fill)
 	bool over = false;                                        // no more records: the end of the file, or a truncated quality string (kseq: -2)
@@ -362,6 +378,9 @@ struct lqreader {
 	{
 		started = true;
 		dev_parse = parse_mode == LQREADER_PARSE_DEVICE && format == 0;
+		keep = host_copy == LQREADER_HOSTCOPY_NEEDED && dev_parse && inflate_mode == LQREADER_INFLATE_DEVICE && gzip;
+		cst.active = keep;
+		if (keep) dp.names_dev = &cst;
 		if (inflate_mode == LQREADER_INFLATE_DEVICE && (format == 1 || bgzf_text)) {
 			if (format == 0) src.reset(new BgzfSource(open_fd(), n_threads));
 			BgzfSource &b = static_cast<BgzfSource&>(*src);          // (a BAM file's source is one since open_file)
@@ -374,13 +393,24 @@ struct lqreader {
 					jobs[i] = {blocks[i].in - lo, at + blocks[i].out, (u32)blocks[i].in_len, (u32)blocks[i].isize};
 				status.assign(blocks.size(), 0);
 				inf.run(src->stream, win + lo, hi - lo, jobs, ck.raw.as<u8>(), status.data());
+				if (keep) {                                               // the bytes stay: their CRC32 comes instead
+					std::vector<u64> off(blocks.size()), len(blocks.size());
+					for (size_t i = 0; i < blocks.size(); ++i) { off[i] = at + blocks[i].out; len[i] = blocks[i].isize; }
+					std::vector<u32> &crc = static_cast<BgzfSource&>(*src).z.dev_crc;
+					crc.assign(blocks.size(), 0);
+					crcdev.run(src->stream, ck.raw.as<u8>(), (u32)blocks.size(), off.data(), len.data(), crc.data());
+					cst.bytes_crc_device += out_bytes;
+					return;
+				}
 				if (out_bytes) LQ_HIP_CHECK(hipMemcpyAsync(dst, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, src->stream));
 				LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
+				cst.bytes_to_host += out_bytes; cst.bytes_crc_host += out_bytes;
 			};
 		} else if (inflate_mode == LQREADER_INFLATE_DEVICE && gzip) {
 			SpanSource *s = new SpanSource(open_fd());
 			src.reset(s);
 			s->z.dev_room = [this](u8 *dst, u64 n) { return mirror_at(dst, n); };
+			s->z.keep_on_device = keep; s->z.copied = &cst;
 		}
 		mirror = src->in_mirror || dev_parse;
 	}
@@ -401,6 +431,31 @@ struct lqreader {
 		LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
 	}
 
+	// keep: what parse_one may look at -- the byte in front of pos and everything behind it -- comes from the mirror, as far as the
+	// host does not hold it yet
+	void host_bytes()
+	{
+		if (!keep) return;
+		const u64 lo = pc.pos > pc.up_from ? pc.pos - 1 : pc.pos;
+		if (lo < v_lo || lo > v_hi) v_lo = v_hi = lo;
+		if (v_hi >= pc.fill) return;
+		const u64 n = pc.fill - v_hi;
+		LQ_HIP_CHECK(hipMemcpyAsync(pc.buf + v_hi, ck.raw.as<u8>() + ck.raw_used + (v_hi - pc.up_from), (size_t)n, hipMemcpyDeviceToHost, src->stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
+		cst.bytes_to_host += n;
+		v_hi = pc.fill;
+	}
+
+	// keep: a new chunk's mirror starts with the bytes behind the last chunk's, raw[from .. from + fill - up_from), which the host may not hold
+	void move_mirror(u64 from)
+	{
+		const u64 n = pc.fill - pc.up_from;
+		raw_next.ensure((size_t)(n + LQ_GATHER_SRC_PAD));            // (the two blocks take turns; raw_reserve grows the one in use)
+		LQ_HIP_CHECK(hipMemcpyAsync(raw_next.p, ck.raw.as<u8>() + from, (size_t)n, hipMemcpyDeviceToDevice, src->stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(src->stream));
+		ck.raw.swap(raw_next);
+	}
+
 	[[noreturn]] void bam_fail(const std::string &what) { throw lq_open_error(path, what); }
 
 	// more bytes behind buf[fill); false: the file has ended
@@ -412,6 +467,7 @@ struct lqreader {
 			try { got = src->fill(pc.buf + pc.fill, pc.cap - pc.fill, &need); }
 			catch (const lq_file_error &e) { bam_fail(e.what()); }      // (the file's, not the device's)
 			if (got && mirror && !src->in_mirror) send_up(pc.buf + pc.fill, got);      // (device parse: the bytes go up as they come)
+			if (src->in_mirror) cst.bytes_inflated += got;
 			pc.fill += got;
 			pc.eof = src->ended;
 			if (got || pc.eof) return got != 0;
@@ -551,7 +607,8 @@ struct lqreader {
 	void refill()
 	{
 		upload();
-		if (pc.pos) memmove(pc.buf, pc.buf + pc.pos, (size_t)(pc.fill - pc.pos));
+		if (pc.pos) memmove(pc.buf, pc.buf + pc.pos, (size_t)(pc.fill - pc.pos));      // (keep: parse_one has just seen these bytes)
+		v_lo = v_lo > pc.pos ? v_lo - pc.pos : 0; v_hi = v_hi > pc.pos ? v_hi - pc.pos : 0;
 		pc.fill -= pc.pos; pc.pos = 0; pc.up_from = 0;
 		more();
 	}
@@ -568,13 +625,18 @@ struct lqreader {
 		if (!started) start();
 		src->stream = c.stream;
 		c.resident = false; c.packed = false; c.n_chunks = 0;
+		const u64 raw_end = ck.raw_used;                          // (behind the last chunk's raw bytes: the bytes of the piece that it left)
 		ck.reset();
 		if (!pc.buf) { pc.resize(piece_bytes()); more(); }
-		else if (mirror && pc.fill > pc.up_from) send_up(pc.buf + pc.up_from, pc.fill - pc.up_from);   // (the mirror starts anew)
+		else if (mirror && pc.fill > pc.up_from) {                // (the mirror starts anew)
+			if (keep) move_mirror(raw_end);
+			else send_up(pc.buf + pc.up_from, pc.fill - pc.up_from);
+		}
 		bool ended = false;
 		while (!over && !ended) {
 			if (dev_parse && (dp.rows_waiting() || dp.scan(c.stream, pc, ck))) { ended = dp.take_rows(c.stream, pc, ck); continue; }
 			const u64 pos0 = pc.pos;
+			host_bytes();
 			const int st = format == 1 ? parse_bam_one() : parse_one();
 			if (st == REC) dp.bol = true;
 			else if (pc.pos != pos0) dp.bol = pc.buf[pc.pos - 1] == '\n';
@@ -627,6 +689,8 @@ lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int i
 		if (mode && !strcmp(mode, "device")) r->inflate_mode = LQREADER_INFLATE_DEVICE;
 		const char *pm = getenv("LQREADER_PARSE");
 		if (pm && !strcmp(pm, "device")) r->parse_mode = LQREADER_PARSE_DEVICE;
+		const char *hc = getenv("LQREADER_HOSTCOPY");
+		if (hc && !strcmp(hc, "needed")) r->host_copy = LQREADER_HOSTCOPY_NEEDED;
 		r->open_file();
 		return r.release();
 	} catch (const std::exception &e) { g_reader_open_error = e.what(); return nullptr; }
@@ -677,6 +741,63 @@ int lqreader_parse(lqreader *r, int mode)
 	if (r->started) { r->err = "lqreader_parse after the first lqreader_next"; return LQCOV_E_STATE; }
 	r->parse_mode = mode;
 	return 0;
+}
+
+int lqreader_host_copy(lqreader *r, int mode)
+{
+	if (!r || (mode != LQREADER_HOSTCOPY_ALL && mode != LQREADER_HOSTCOPY_NEEDED)) return LQCOV_E_ARG;
+	if (r->started) { r->err = "lqreader_host_copy after the first lqreader_next"; return LQCOV_E_STATE; }
+	r->host_copy = mode;
+	return 0;
+}
+
+int lqreader_copy_stats(const lqreader *r, lqcopy_stats *stats)
+{
+	if (!r || !stats) return LQCOV_E_ARG;
+	*stats = r->cst;
+	return 0;
+}
+
+int lqcrc32_ranges(int device, const uint8_t *bytes, uint64_t n_bytes, uint32_t n, const uint64_t *off, const uint64_t *len, uint32_t *crc_out)
+{
+	return one_shot([&] {
+		if (!n) return;
+		if (!off || !len || !crc_out || (n_bytes && !bytes)) throw std::invalid_argument("null buffers");
+		for (u32 i = 0; i < n; ++i)
+			if (off[i] > n_bytes || len[i] > n_bytes - off[i]) throw std::invalid_argument("a range lies outside the bytes");
+		lq_cabi::ScopedStream stream(device);
+		DBuf d;
+		d.ensure((size_t)n_bytes + LQ_GATHER_SRC_PAD);
+		if (n_bytes) LQ_HIP_CHECK(hipMemcpyAsync(d.p, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, stream));
+		CrcDev crc;
+		crc.run(stream, d.as<u8>(), n, off, len, crc_out);
+	});
+}
+
+int lqfx_names(int device, const uint8_t *bytes, uint64_t n, const uint32_t *rows, uint64_t n_rows, char *names_out, uint64_t names_cap,
+               uint64_t *name_off_out, uint64_t *first_bad)
+{
+	return one_shot([&] {
+		if (!name_off_out || !first_bad || (n && !bytes) || (n_rows && !rows)) throw std::invalid_argument("null buffers");
+		name_off_out[0] = 0; *first_bad = n_rows;
+		if (!n_rows) return;
+		u64 blob = 0;
+		for (u64 i = 0; i < n_rows; ++i) {
+			if (rows[4 * i] > n || rows[4 * i + 1] > n - rows[4 * i]) throw std::invalid_argument("a name lies outside the bytes");
+			blob += (u64)rows[4 * i + 1] + 1;
+		}
+		if (blob > names_cap || !names_out) throw std::invalid_argument("names_cap is smaller than the names");
+		lq_cabi::ScopedStream stream(device);
+		DBuf d, d_rows;
+		d.ensure((size_t)n + LQ_GATHER_SRC_PAD); d_rows.ensure((size_t)n_rows * sizeof(FxRow));
+		if (n) LQ_HIP_CHECK(hipMemcpyAsync(d.p, bytes, (size_t)n, hipMemcpyHostToDevice, stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(d_rows.p, rows, (size_t)n_rows * sizeof(FxRow), hipMemcpyHostToDevice, stream));
+		FxScan fx;
+		fx.names(stream, d.as<u8>(), (const FxRow*)d_rows.as<FxRow>(), n_rows);
+		memcpy(names_out, fx.h_names.data(), fx.h_names.size());
+		memcpy(name_off_out, fx.h_name_off.data(), (size_t)(n_rows + 1) * 8);
+		*first_bad = fx.first_bad;
+	});
 }
 
 int lqreader_parse_stats(const lqreader *r, lqparse_stats *stats)

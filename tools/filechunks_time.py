@@ -13,9 +13,14 @@ and the spread, the device mode's inflate_stats; the modes must count the same r
 (d) --parse host,device: the record scan on the device (lqreader_parse, k_fx_*) against the host parser, alternated, one warm-up pass
 and --reps timed ones per mode, medians and the spread: the bare FileChunks loop and run_file on the one-line FASTQ, the bare loop on
 the same reads as FASTA wrapped at 60 columns and on the FASTQ as level-6 gzip with inflate="device"; parse_stats of the device mode.
+(e) --inflate device --parse device --host-copy all,needed: the FASTQ as bgzip (64-KiB members, level 6) and as one level-6 gzip
+member, the bare FileChunks loop with the inflated bytes copied back ("all", the path of (c) and (d)) and left on the device
+("needed": k_crc32_ranges, k_fx_names), alternated, one warm-up pass and --reps timed ones per mode, medians and the spread, copy_stats,
+parse_stats and inflate_stats of each; beside them the host default (inflate="host", parse="host") on the same files.
 Usage: python tools/filechunks_time.py [--reads 500000] [--chunk-mb 512] [--nsample 5000] [--reps 3] [--workers 16] [--only loop|gather]
        python tools/filechunks_time.py --reads 50000 --inflate host,device [--reps 3]
-       python tools/filechunks_time.py --reads 50000 --parse host,device [--reps 3]"""
+       python tools/filechunks_time.py --reads 50000 --parse host,device [--reps 3]
+       python tools/filechunks_time.py --reads 50000 --inflate device --parse device --host-copy all,needed [--reps 3]"""
 import argparse
 import dataclasses
 import json
@@ -171,6 +176,35 @@ def parse_modes(path, cs, reps, modes, nsample, wdir):
     return out
 
 
+def hostcopy_modes(path, cs, reps, modes, inflate, parse):
+    import zlib
+    from tests import bam_writer
+    bg, gz = path + ".bgz.gz", path + ".gz"
+    t0 = time.time()
+    c = zlib.compressobj(6, zlib.DEFLATED, 31)
+    with open(path, "rb") as f, open(gz, "wb") as g, open(bg, "wb") as b:
+        for block in iter(lambda: f.read(65280 * 256), b""):
+            g.write(c.compress(block))
+            b.write(bam_writer.bgzf(block, eof=False))
+        g.write(c.flush())
+        b.write(bam_writer.bgzf(b""))
+    out = {"compress_s": round(time.time() - t0, 1), "inflate": inflate, "parse": parse}
+    for label, p in (("fastq_bgzip", bg), ("fastq_gzip", gz)):
+        cases = [("host_copy=" + m, dict(inflate=inflate, parse=parse, host_copy=m)) for m in modes] + [("host_default", dict(inflate="host", parse="host"))]
+        runs, counts, stats = {k: [] for k, _ in cases}, {}, {}
+        for it in range(reps + 1):                                  # alternated; the first pass of every mode is the warm-up
+            for k, kw in cases:
+                fc = chunkpass.FileChunks(p, chunk_size=cs, **kw)
+                t = time.perf_counter()
+                tot = [(ns, nb) for _, ns, nb in fc][-1]
+                if it:
+                    runs[k].append({"wall_s": time.perf_counter() - t})
+                counts[k], stats[k] = tot, dict(copy_stats=fc.copy_stats, parse_stats=fc.parse_stats, inflate_stats=fc.inflate_stats)
+        out[label] = {"file_bytes": os.path.getsize(p), "same_counts": len(set(counts.values())) == 1,
+                      "modes": {k: dict(summary(runs[k]), reads_bases=counts[k], **stats[k]) for k, _ in cases}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=500000)
@@ -181,6 +215,7 @@ def main():
     ap.add_argument("--only", choices=("loop", "gather"), default=None)
     ap.add_argument("--inflate", default=None, help="host,device: time FileChunks on the file as a plain .gz in these modes, and nothing else")
     ap.add_argument("--parse", default=None, help="host,device: time FileChunks and run_file with the record scan in these modes, and nothing else")
+    ap.add_argument("--host-copy", default=None, help="all,needed: with --inflate device --parse device, time FileChunks on the file as bgzip and as gzip in these modes, and nothing else")
     a = ap.parse_args()
     cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
     cs = int(a.chunk_mb * 1024 ** 2)
@@ -197,7 +232,10 @@ def main():
                "file_bytes": os.path.getsize(path), "chunk_size": cs, "nsample": a.nsample, "setup_s": round(time.time() - t0, 1)}
         del F, flat
         sum(ch.n for ch, _, _ in chunkpass.FileChunks(path, chunk_size=cs))       # device start-up, the file in the page cache
-        if a.inflate:
+        if a.host_copy:
+            res["metric"] = "seconds from the bgzip / gzip FASTQ file to its chunks on the device, by host_copy mode"
+            res["host_copy"] = hostcopy_modes(path, cs, a.reps, a.host_copy.split(","), a.inflate or "device", a.parse or "device")
+        elif a.inflate:
             res["metric"] = "seconds from the gzip FASTQ file to its chunks on the device"
             res["inflate"] = inflate_modes(path, cs, a.reps, a.inflate.split(","))
         elif a.parse:
@@ -212,7 +250,7 @@ def main():
                 same = same and o_new == o_old
             res.update(run_file=summary(news), python_reader_and_add_chunk=summary(olds), same_results=same, reps=a.reps, chunks=o_new[2])
             res["value"] = res["run_file"]["wall_s"]["median"]
-        if a.only != "loop" and not a.inflate and not a.parse:
+        if a.only != "loop" and not a.inflate and not a.parse and not a.host_copy:
             res["gather"] = gather_only(path, cs, a.reps, n_bases)
     print(json.dumps(res))
     if os.environ.get("OUT"):

@@ -5,7 +5,10 @@ deflated blocks, empty blocks, files without the EOF marker, piece sizes, thread
 chunk's records must be the written list cut by lq_utils.parse_bam_chunk's rule.
 --inflate device: the blocks are inflated by k_bgzf_inflate (FileChunks(inflate="device")); the files then also take level 9 and the
 strategies Z_FIXED, Z_RLE and Z_HUFFMAN_ONLY, and every case is read in host mode as well: the two modes must give the same chunks.
-    python tools/fuzz_bam.py [--n 300] [--seed 1] [--inflate device]        (the emulator build: no GPU needed)"""
+    python tools/fuzz_bam.py [--n 300] [--seed 1] [--inflate device]        (the emulator build: no GPU needed)
+--host-copy needed: the reads of every case also go, as FASTQ text, into a BGZF file of the same block layout -- the text input the
+mode is for -- and FileChunks(inflate="device", parse="device") must give the same chunks, or the same error, with host_copy="needed"
+as with "all" and as the host modes (a BAM file itself ignores the mode: its record walk is the host's)."""
 import argparse
 import os
 import random
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
     ap.add_argument("--inflate", choices=("host", "device"), default="host")
+    ap.add_argument("--host-copy", choices=("all", "needed"), default="all")
     args = ap.parse_args()
     from longqc_amd import api, chunkpass
     from tests import bam_writer as BW
@@ -87,6 +91,20 @@ def main():
                                                                                          is_sequel=sequel, inflate="host")]
             except api.LqcovError as e:
                 got, ok = repr(e), False
+            if ok and args.host_copy == "needed":
+                text = b"".join(b"@" + r[0] + b"\n" + r[1] + b"\n+\n" + (b"!" * len(r[1]) if q is None else bytes(x + 33 for x in q)) + b"\n" for r, q in zip(reads, quals))
+                tpath = os.path.join(d, "f.fq.gz")
+                open(tpath, "wb").write(BW.bgzf(text, block_payload=kw["block_payload"], level=min(kw["level"], 6), eof=kw["eof"], empty_block_every=kw["empty_block_every"]))
+                res = []
+                for mode in (dict(inflate="host", parse="host"), dict(inflate="device", parse="device", host_copy="all"), dict(inflate="device", parse="device", host_copy="needed")):
+                    try:
+                        fc = chunkpass.FileChunks(tpath, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads, **mode)
+                        res.append([(ch.records(), a, b) for ch, a, b in fc])
+                    except api.LqcovError as e:
+                        res.append(str(e))
+                ok = res[0] == res[1] == res[2] and fc.copy_stats["active"] == (1 if os.path.getsize(tpath) else 0)      # (no byte: not a gzip file)
+                if not ok:
+                    got = "the text of the reads: host_copy=needed differs"
             if not ok:
                 bad += 1
                 print("case %d: %d reads, %s, piece %s, %d threads, chunk_size %d, is_sequel %s: %s" % (

@@ -11,8 +11,12 @@ records, the counts and the error must be the same.
 --parse device: the token soup and the damaged records of the default mode, each read by FileChunks with parse="host" and with
 parse="device" (the record scan k_fx_*, csrc/kernels_fxscan.hpp) at a random piece length and chunk size: the chunks, names, records and
 the error must be the same; and chunkpass.scan_records' rows must be a prefix of the records the host parser reads.
-    python tools/fuzz_reader.py --parse device [--n 2000] [--seed 1]         (the emulator build, or the GPU's with --lib)"""
+    python tools/fuzz_reader.py --parse device [--n 2000] [--seed 1]         (the emulator build, or the GPU's with --lib)
+--parse device --host-copy needed: the same inputs as bgzip (even cases, blocks of a random size) or gzip files, read by the host
+modes and by FileChunks(inflate="device", parse="device", host_copy="needed"), where the inflated bytes stay on the device
+(k_crc32_ranges, k_fx_names): the same chunks, names, records and errors."""
 import argparse
+import gzip
 import ctypes as C
 import os
 import sys
@@ -113,15 +117,24 @@ def soup(rng, toks):
     return bytes(data)
 
 
-def parse_cases(lib, n, seed):
+def parse_cases(lib, n, seed, host_copy="all"):
     from longqc_amd import api, chunkpass
+    from tests import bam_writer
+    needed = host_copy == "needed"
+    kw_dev = dict(parse="device", inflate="device", host_copy="needed") if needed else dict(parse="device")
+    kw_host = dict(parse="host", inflate="host") if needed else dict(parse="host")
     rng = np.random.default_rng(seed)
     toks = [b">", b"@", b"+", b"\n", b"\n", b"\n", b"\r\n", b"\r", b"\r\r\n", b" ", b"\t", b"ACGT", b"acgtnN", b"U", b"!!!!", b"IIII", b"@@", b">>", b"+\n", b"name", b"x y", b""]
 
-    def read(path, mode, cs):
+    active = 0
+
+    def read(path, kw, cs):
+        nonlocal active
         try:
-            fc = chunkpass.FileChunks(path, chunk_size=cs, lib=lib, str_overhead=49, parse=mode)
-            return [(ch.records(), list(ch.names), ns, nb) for ch, ns, nb in fc], None
+            fc = chunkpass.FileChunks(path, chunk_size=cs, lib=lib, str_overhead=49, **kw)
+            out = [(ch.records(), list(ch.names), ns, nb) for ch, ns, nb in fc]
+            active += fc.copy_stats["active"]
+            return out, None
         except api.LqcovError as e:
             return None, (e.code, str(e))
 
@@ -130,10 +143,15 @@ def parse_cases(lib, n, seed):
         fn = os.path.join(d, "f.txt")
         for it in range(n):
             data = soup(rng, toks)
-            open(fn, "wb").write(data)
+            if not needed:
+                open(fn, "wb").write(data)
+            elif it % 2 == 0:
+                open(fn, "wb").write(bam_writer.bgzf(data, block_payload=int(rng.choice((1, 7, 37, 100, 65280))), level=int(rng.choice((0, 1, 6)))))
+            else:
+                open(fn, "wb").write(gzip.compress(data, int(rng.choice((1, 6)))))
             os.environ["LQREADER_PIECE_BYTES"] = str(rng.choice((16, 40, 100, 1 << 20)))
             cs = int(rng.choice((1 << 40, 1, 300)))
-            host, dev = read(fn, "host", cs), read(fn, "device", cs)
+            host, dev = read(fn, kw_host, cs), read(fn, kw_dev, cs)
             ok = host == dev
             if ok and host[0] is not None:
                 names = [x for c in host[0] for x in c[1]]
@@ -146,6 +164,8 @@ def parse_cases(lib, n, seed):
                 if bad >= 5:
                     break
     print("%d inputs, %d on which the host and the device parse disagree; the device vouched for %d of %d records" % (it + 1, bad, vouched, total))
+    if needed:
+        print("host_copy=needed was active for %d of them" % active)
     return 1 if bad else 0
 
 
@@ -156,11 +176,12 @@ def main():
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
     ap.add_argument("--inflate", choices=("host", "device"), default="host")
     ap.add_argument("--parse", choices=("host", "device"), default="host")
+    ap.add_argument("--host-copy", choices=("all", "needed"), default="all", help="with --parse device: bgzip and gzip inputs, the inflated bytes stay on the device")
     args = ap.parse_args()
     from longqc_amd import api
     lib = api.load_library(args.lib)
     if args.parse == "device":
-        sys.exit(parse_cases(lib, args.n if args.n != 20000 else 2000, args.seed))
+        sys.exit(parse_cases(lib, args.n if args.n != 20000 else 2000, args.seed, args.host_copy))
     if args.inflate == "device":
         sys.exit(gzip_cases(lib, args.n if args.n != 20000 else 300, args.seed))
     rng = np.random.default_rng(args.seed)
