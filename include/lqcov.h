@@ -379,6 +379,20 @@ void     lqchunk_destroy(lqchunk *c);
 const char *lqchunk_last_error(const lqchunk *c);
 int lqchunk_load(lqchunk *c, uint32_t n, const uint8_t *seq, const uint64_t *seq_off, const uint8_t *qual);
 int lqchunk_sdust(lqchunk *c, int W, int T, uint32_t *masked, double *qual_psum, uint32_t *n_above_q7);
+/* The same table with long reads cut into pieces that are scanned side by side (opt-in; k_sdust_pieces): a read of A/C/G/T alone (either
+ * case) with at least two pieces' bases is cut into pieces of `piece` bases (0: the default, 4096), each scanned from empty state 2 W +
+ * 2 bases before its first base, and what the pieces save is ORed into a bit mask of the read; every other read -- one with an N or
+ * any other byte, one shorter than two pieces -- takes lqchunk_sdust's walk, a thread per read.  masked, qual_psum and n_above_q7 are
+ * lqchunk_sdust's arrays, value for value; *n_serial (may be NULL) is the number of reads that took the serial walk.  The same checks
+ * and codes as lqchunk_sdust; LQCOV_E_ARG also for 0 < piece < 2 W + 2.
+ * lqchunk_sdust_intervals returns what the reference's library call sdust() returns for the reads the pieces serve: the maximal runs of
+ * the mask, read i's in iv[n_off[i] .. n_off[i + 1]) as start << 32 | finish (ascending, disjoint, not adjacent, inside the read; the
+ * sum of finish - start is masked[i]).  Here a read of any length is served, also one of a single piece; flagged[i] (n bytes, may be
+ * NULL) is 1 for a read with a byte other than A/C/G/T, which only the serial walk can count: it reports no interval.  Two calls: with iv == NULL only n_off (n + 1 entries), flagged and *iv_need are written; with iv != NULL and iv_cap >=
+ * *iv_need the intervals too (a smaller iv_cap: LQCOV_E_ARG).  The runs are taken from a copy of the mask on the host and kept for the
+ * second call; every lqchunk_sdust_split call classifies and scans anew. */
+int lqchunk_sdust_split(lqchunk *c, int W, int T, uint32_t piece, uint32_t *masked, double *qual_psum, uint32_t *n_above_q7, uint32_t *n_serial);
+int lqchunk_sdust_intervals(lqchunk *c, int W, int T, uint32_t piece, uint64_t *n_off, uint8_t *flagged, uint64_t *iv, size_t iv_cap, size_t *iv_need);
 int lqchunk_adapt(lqchunk *c, const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
                   uint32_t length, int32_t *out5, int32_t *out3);
 int lqchunk_gc(lqchunk *c, uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,

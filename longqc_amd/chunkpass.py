@@ -31,6 +31,8 @@ def _lib(lib=None):
             "lqchunk_last_error": (C.c_char_p, [H]),
             "lqchunk_load": (C.c_int, [H, C.c_uint32, P, P, P]),
             "lqchunk_sdust": (C.c_int, [H, C.c_int, C.c_int, P, P, P]),
+            "lqchunk_sdust_split": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, P]),
+            "lqchunk_sdust_intervals": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, C.c_size_t, P]),
             "lqchunk_adapt": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32, P, P]),
             "lqchunk_gc": (C.c_int, [H, C.c_uint32, P, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
             "lqchunk_pack": (C.c_int, [H]),
@@ -157,6 +159,17 @@ def inflate_gzip(data, span_bytes: Optional[int] = None, device: int = 0, lib=No
     return out[:n.value].tobytes(), _stats_dict(st)
 
 
+split_mode = sdust.split_mode                                       # "serial" | "pieces" | None (LQSDUST_SPLIT): how ReadChunk.sdust scans long reads
+
+
+def _piece(piece):
+    """piece as the C ABI takes it: 0 for None (the default), else the number of bases, which must fit 32 bits"""
+    p = int(piece or 0)
+    if not 0 <= p <= 0xffffffff:
+        raise ValueError("piece must be None or a number of bases from 0 to 2^32 - 1, not %r" % (piece,))
+    return p
+
+
 PARSE_MODES = {"host": 0, "device": 1}
 PARSE_STATS = ("pieces", "scans", "records_device", "records_host", "lines", "fallbacks")
 GATHER_FILL = 0xffffffffffffffff                                    # src of a quality segment without source bytes ('!')
@@ -248,6 +261,7 @@ class ReadChunk:
         if not self.h:
             raise api.LqcovError(-3, self.lib.lqchunk_last_error(None).decode() or "lqchunk_create failed (no HIP device?)")
         self.n, self.names, self.lens, self.off = 0, [], np.zeros(0, np.int64), np.zeros(1, np.uint64)
+        self.n_serial = 0                                           # reads of the last sdust(split="pieces") that took the serial walk
         self.qflat, self.packed, self.from_file, self._name_blob = None, False, False, None
         if reads is not None:
             self.load(reads)
@@ -358,12 +372,32 @@ class ReadChunk:
         return out[:n.value].tobytes()
 
     # -- the steps, as arrays --
-    def sdust(self, w: int = 64, t: int = 20):
-        """-> (masked bases, sums of 10^(-q/10), qualities above Q7) per read: lqchunk_sdust"""
+    def sdust(self, w: int = 64, t: int = 20, split: Optional[str] = None, piece: Optional[int] = None):
+        """-> (masked bases, sums of 10^(-q/10), qualities above Q7) per read: lqchunk_sdust.  split (split_mode's) "pieces": the same
+        arrays from lqchunk_sdust_split -- reads of A/C/G/T alone are cut into pieces of `piece` bases (None: the default, 4096; at least
+        2 w + 2) that are scanned side by side; n_serial then says how many reads took the serial walk all the same"""
         n = self.n
         masked, psum, qv = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint32)
-        self._ck(self.lib.lqchunk_sdust(self.h, w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data))
+        if split_mode(split) == "pieces":
+            ns = C.c_uint32()
+            self._ck(self.lib.lqchunk_sdust_split(self.h, w, t, _piece(piece), masked.ctypes.data, psum.ctypes.data, qv.ctypes.data, C.byref(ns)))
+            self.n_serial = ns.value
+        else:
+            self._ck(self.lib.lqchunk_sdust(self.h, w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data))
         return masked, psum, qv
+
+    def sdust_intervals(self, w: int = 64, t: int = 20, piece: Optional[int] = None):
+        """The masked intervals of the reads the pieces serve, what the reference's sdust() returns for them: lqchunk_sdust_intervals.
+        -> (iv_off uint64[n + 1], iv uint64[k, 2]: (start, finish) of read i's intervals at iv[iv_off[i] : iv_off[i + 1]], ascending,
+        disjoint and not adjacent; flagged bool[n]: the read holds a byte other than A/C/G/T and reports no interval -- only the serial
+        walk can count such a read; reads of any length are served)"""
+        n = self.n
+        iv_off, flagged, need = np.zeros(n + 1, np.uint64), np.zeros(max(n, 1), np.uint8), C.c_size_t()
+        self._ck(self.lib.lqchunk_sdust_intervals(self.h, w, t, _piece(piece), iv_off.ctypes.data, flagged.ctypes.data, None, 0, C.byref(need)))
+        iv = np.zeros(max(need.value, 1), np.uint64)
+        self._ck(self.lib.lqchunk_sdust_intervals(self.h, w, t, _piece(piece), iv_off.ctypes.data, flagged.ctypes.data, iv.ctypes.data, need.value, C.byref(need)))
+        iv = iv[:need.value]
+        return iv_off, np.stack([iv >> np.uint64(32), iv & np.uint64(0xffffffff)], axis=1).astype(np.int64), flagged[:n].astype(bool)
 
     def adapt(self, adp5: Optional[bytes], adp3: Optional[bytes], length: int = 150):
         """-> (n x 4 int32 of d, s, e, L for the 5' windows, the same for the 3' windows), None for an adapter not given: lqchunk_adapt"""
@@ -575,12 +609,13 @@ class SampleQCPass:
     coverage() maps the subsample against the stored chunks."""
 
     def __init__(self, work_dir: str, preset: str, adp5=None, adp3=None, nsample=5000, gc_draw: str = "device", device: int = 0,
-                 fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None):
+                 fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None,
+                 sdust_split: Optional[str] = None):
         if preset not in sampleqc.PRESET_MED_SCORE:
             raise ValueError("unknown preset %r" % preset)
         self.preset, self.fast, self.inds, self.device, self.lib = preset, fast, inds, device, lib
         self.adp5, self.adp3, self.nsample = adp5, adp3, nsample
-        self.mask = sdust.LqMaskMI355X(work_dir, suffix, device=device, lib=lib)
+        self.mask = sdust.LqMaskMI355X(work_dir, suffix, device=device, lib=lib, split=sdust_split)     # sdust_split: split_mode's
         self.adapters = adapter.AdapterStats(adp5, adp3)
         self.gc = gcfrac.LqGCMI355X(chunk_size=150, draw=gc_draw, seed=gc_seed, device=device, lib=lib)
         self.store = PackedStore(device, lib)
@@ -625,14 +660,17 @@ class SampleQCPass:
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
                  is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None,
-                 host_copy: Optional[str] = None):
+                 host_copy: Optional[str] = None, sdust_split: Optional[str] = None):
         """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse,
         host_copy: FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
         trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
         appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
         `trimmed` stays None and `trimmed_chunks` empty.  fastx_out=<path>: every chunk is appended to that file untrimmed -- the
         FASTQ that longQC.py:302-303 converts a BAM file to, for any input.  Both files are complete, and their errors raised, when
-        the call returns."""
+        the call returns.  sdust_split: split_mode's, for this file (None: what the constructor was given); the table is the same."""
+        mask_split = self.mask.split
+        if sdust_split is not None:
+            self.mask.split = split_mode(sdust_split)
         results, self.trimmed_chunks = [], []
         to_file = isinstance(trim, (str, os.PathLike))
         if to_file and not (self.adp5 or self.adp3):
@@ -655,6 +693,8 @@ class SampleQCPass:
         except BaseException:
             _close_writers(writers, quiet=True)                    # (the loop's error is the one to report)
             raise
+        finally:
+            self.mask.split = mask_split                           # (sdust_split held for this file)
         _close_writers(writers)
         return results
 

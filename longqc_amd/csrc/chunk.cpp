@@ -23,7 +23,7 @@ void lq_chunk_set(lqchunk &c, u32 n, const u8 *seq, const u64 *seq_off, const u8
 	c.h_seq = seq ? seq + seq_off[0] : nullptr;
 	c.h_qual = qual ? qual + seq_off[0] : nullptr;
 	c.has_qual = qual != nullptr;
-	c.resident = false; c.packed = false; c.n_chunks = 0;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false;
 }
 
 void lq_chunk_ready(lqchunk &c)
@@ -99,7 +99,7 @@ static void gather_begin(lqchunk &c, const std::vector<u64> &off)
 	lq_cabi::select_device(c.device);
 	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
 	const u32 n = (u32)(off.size() - 1);
-	c.resident = false; c.packed = false; c.n_chunks = 0;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false;
 	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
 	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
 	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
@@ -226,6 +226,31 @@ int lqchunk_sdust(lqchunk *c, int W, int T, uint32_t *masked, double *qual_psum,
 		need_loaded(*c);
 		if (c->n && (!masked || !qual_psum || !n_above_q7)) throw std::invalid_argument("null buffers");
 		lq_chunk_sdust(*c, W, T, masked, qual_psum, n_above_q7);
+	});
+}
+
+int lqchunk_sdust_split(lqchunk *c, int W, int T, uint32_t piece, uint32_t *masked, double *qual_psum, uint32_t *n_above_q7, uint32_t *n_serial)
+{
+	return chunk_guard(c, [&] {
+		need_loaded(*c);
+		if (c->n && (!masked || !qual_psum || !n_above_q7)) throw std::invalid_argument("null buffers");
+		lq_chunk_sdust_split(*c, W, T, piece, masked, qual_psum, n_above_q7, n_serial);
+	});
+}
+
+int lqchunk_sdust_intervals(lqchunk *c, int W, int T, uint32_t piece, uint64_t *n_off, uint8_t *flagged, uint64_t *iv, size_t iv_cap, size_t *iv_need)
+{
+	return chunk_guard(c, [&] {
+		need_loaded(*c);
+		if (!n_off || !iv_need) throw std::invalid_argument("null buffers");
+		lq_chunk_sdust_intervals(*c, W, T, piece);
+		const size_t need = c->h_iv.size();
+		*iv_need = need;
+		for (u32 i = 0; i <= c->n; ++i) n_off[i] = c->h_ivoff[i];
+		if (flagged && c->n) memcpy(flagged, c->h_dflag.data(), c->n);
+		if (!iv) return;                                          // (the first of the two calls: the size)
+		if (iv_cap < need) throw std::invalid_argument("iv_cap is smaller than the number of intervals (iv_need)");
+		if (need) memcpy(iv, c->h_iv.data(), need * 8);
 	});
 }
 

@@ -28,6 +28,12 @@ struct lqchunk {
 	bool has_qual = false;
 	DBuf seq, qual, d_off;
 	DBuf pi, masked, psum, qv, q2p; bool tab_ready = false;   // sdust: scratch, results, meanQ's table
+	// sdust in pieces (kernels_dust_split.hpp): the flags, the mask, the work list, and the flagged reads set one behind the other for k_sdust
+	DBuf dflag, dmask, ditem, slist, soff, sseq, smasked, spsum, sqv;
+	hipStream_t stream2 = nullptr;                            // k_sdust_qual runs here, beside the pieces
+	std::vector<u8> h_dflag;                                  // the flags of the mask on the device
+	std::vector<u64> h_iv, h_ivoff;                           // lqchunk_sdust_intervals: the runs of that mask, per read
+	bool iv_valid = false; int iv_W = 0, iv_T = 0; u32 iv_piece = 0;   // h_iv, h_ivoff and h_dflag are lqchunk_sdust_intervals' for these arguments and the reads loaded now
 	DBuf woff, adp5, adp3, out;                               // adapter search: window offsets, adapters, result rows
 	DBuf draw_off, gc, pos, win, kept;                        // GC counts
 	DBuf coff, tile_read, codes, amb, flags;                  // packed form
@@ -35,7 +41,11 @@ struct lqchunk {
 	DBuf fq_names, fq_noff, fq_be, fq_rec, fq_tile, fq_text;  // k_fastq_format's names and tables (writer.cpp), lqchunk_fastq's text
 	std::vector<u64> h_coff;                                  // packed chunks before read i
 	u64 n_chunks = 0; bool packed = false;
-	~lqchunk() { if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); } }
+	~lqchunk()
+	{
+		if (stream2) { hipStreamSynchronize(stream2); hipStreamDestroy(stream2); }
+		if (stream) { hipStreamSynchronize(stream); hipStreamDestroy(stream); }
+	}
 };
 
 // describe the reads (nothing goes to the device and nothing is checked but the order of the offsets: each step keeps its own checks,
@@ -52,6 +62,11 @@ void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std
 // in destination order, room for one more behind each; the per-tile work list is made on the device (k_fx_tileseg)
 void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper);
 void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
+// the same table with the reads of A/C/G/T alone cut into pieces of `piece` bases (0: LQ_DUST_SPLIT_PIECE), the others walked by k_sdust;
+// n_serial (may be null): how many those were
+void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, double *psum, u32 *qv, u32 *n_serial);
+// the maximal runs of the pieces' mask per read (start << 32 | finish; none for a flagged read), kept in c.h_iv / c.h_ivoff / c.h_dflag
+void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece);
 void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
 void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,
                  u32 *gc, u32 *pos_out, u16 *win_gc, u32 *kept);

@@ -3,6 +3,7 @@
 // thread walks one read (kernels_dust.hpp); rows are formatted on the host with libc/libm like the reference.
 #include "engine.hpp"
 #include "kernels_dust.hpp"
+#include "kernels_dust_split.hpp"
 #include "fastx.hpp"
 #include "chunk.hpp"
 using lq_cabi::guarded;
@@ -44,6 +45,162 @@ void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv
 	LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream));
 	LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream));
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+}
+
+// ---- the scan in pieces (kernels_dust_split.hpp) -----------------------------------------------------------------------------
+static void dust_checks(const lqchunk &c, int W)
+{
+	if (W < 3 || W > 66) throw std::domain_error("sdust window outside [3, 66] (the window ring holds 64 words; the reference's default is 64)");
+	for (u32 i = 0; i < c.n; ++i) if (c.off[i + 1] - c.off[i] > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases");
+}
+
+static u32 dust_piece(const lqchunk &c, int W, u32 piece)
+{
+	if (c.total > 0xffffffffULL) throw std::domain_error("sdust in pieces: a chunk of 2^32 bases or more (the mask's bit numbers have 32 bits)");
+	if (piece == 0) piece = LQ_DUST_SPLIT_PIECE;
+	if (piece < (u32)(2 * W + 2)) throw std::invalid_argument("sdust piece shorter than 2 W + 2 bases");
+	return std::min<u32>(piece, 0x40000000u);                   // (a longer piece cuts no read)
+}
+
+static void dust_q2p(lqchunk &c)
+{
+	if (c.tab_ready) return;
+	double tab[127]; lq_make_q2p(tab);
+	c.q2p.ensure(127 * 8);
+	LQ_HIP_CHECK(hipMemcpyAsync(c.q2p.p, tab, sizeof(tab), hipMemcpyHostToDevice, c.stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+	c.tab_ready = true;
+}
+
+// classify, cut and walk the pieces: afterwards c.dmask holds the mask of the unflagged reads, c.dflag / c.h_dflag the flags and c.ditem
+// the items before every read.  Everything is queued on c.stream; the flags have come back.  -> the number of flagged reads.  all_lengths:
+// a short read is not flagged (the intervals: the pieces are the only walk that gives them, and a read of one piece is served as well)
+static u32 dust_mask(lqchunk &c, int W, int T, u32 piece, bool all_lengths, std::vector<u32> *serial)
+{
+	const u32 n = c.n;
+	c.iv_valid = false;                                         // (the flags and the mask that the kept intervals came from go)
+	c.dflag.ensure(n + 4); c.h_dflag.resize(n);
+	LQ_HIP_CHECK(hipMemsetAsync(c.dflag.p, 0, n, c.stream));
+	const u64 n_tiles = (c.total + LQ_DUST_SPLIT_TILE - 1) / LQ_DUST_SPLIT_TILE;
+	const u32 cgrid = (u32)std::min<u64>(std::max<u64>(std::max<u64>((n_tiles + 3) / 4, ((u64)n + LQ_DUST_SPLIT_THREADS - 1) / LQ_DUST_SPLIT_THREADS), 1), LQ_DUST_SPLIT_MAX_BLOCKS);
+	LQ_LAUNCH(k_sdust_classify, cgrid, LQ_DUST_SPLIT_THREADS, c.stream, c.seq.as<u8>(), c.d_off.as<u64>(), n, all_lengths ? (u64)0 : LQ_DUST_SPLIT_MIN(piece), c.dflag.as<u8>());
+	LQ_HIP_CHECK(hipGetLastError());
+	LQ_HIP_CHECK(hipMemcpyAsync(c.h_dflag.data(), c.dflag.p, n, hipMemcpyDeviceToHost, c.stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+	u32 k = 0;
+	for (u32 i = 0; i < n; ++i) if (c.h_dflag[i]) { ++k; if (serial) serial->push_back(i); }
+	std::vector<u64> item((size_t)n + 1);
+	item[0] = 0;
+	for (u32 i = 0; i < n; ++i) item[i + 1] = item[i] + (c.h_dflag[i] ? 0 : (c.off[i + 1] - c.off[i] + piece - 1) / piece);
+	if (item[n] > 0x7fffffffULL) throw std::domain_error("more than 2^31-1 pieces in one chunk");
+	const u64 n_items = item[n], n_words = (c.total + 31) / 32 + 1;
+	c.dmask.ensure(n_words * 4);
+	LQ_HIP_CHECK(hipMemsetAsync(c.dmask.p, 0, n_words * 4, c.stream));
+	if (n_items) {
+		c.ditem.ensure(((size_t)n + 1) * 8);
+		LQ_HIP_CHECK(hipMemcpyAsync(c.ditem.p, item.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
+		const u32 n_thr = (u32)std::min<u64>((n_items + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_SPLIT_MAX_THREADS);
+		c.pi.ensure((u64)n_thr * LQ_DUST_PCAP * sizeof(DustPI));
+		LQ_LAUNCH(k_sdust_pieces, nblk_d(n_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, c.stream, c.seq.as<u8>(), c.d_off.as<u64>(), c.ditem.as<u64>(), n, (u32)n_items,
+		          piece, (i32)W, (i32)T, c.pi.as<DustPI>(), c.dmask.as<u32>());
+		LQ_HIP_CHECK(hipGetLastError());
+		LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (`item` dies here)
+	}
+	return k;
+}
+
+void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, double *psum, u32 *qv, u32 *n_serial)
+{
+	dust_checks(c, W);
+	piece = dust_piece(c, W, piece);
+	const u32 n = c.n;
+	if (n_serial) *n_serial = 0;
+	if (n == 0) return;
+	lq_chunk_ready(c);
+	if (!c.stream2) LQ_HIP_CHECK(hipStreamCreate(&c.stream2));
+	dust_q2p(c);
+	c.masked.ensure(n * 4 + 4); c.psum.ensure(n * 8 + 8); c.qv.ensure(n * 4 + 4);
+	// the quality columns need nothing of the rest: a launch of their own on the second stream, beside the pieces
+	const u32 q_thr = (u32)std::min<u64>(((u64)n + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_MAX_THREADS);
+	LQ_LAUNCH(k_sdust_qual, nblk_d(q_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, c.stream2, c.has_qual ? c.qual.as<u8>() : (const u8*)nullptr, c.d_off.as<u64>(), n,
+	          c.q2p.as<double>(), c.psum.as<double>(), c.qv.as<u32>());
+	LQ_HIP_CHECK(hipGetLastError());
+	std::vector<u32> serial;
+	std::vector<u64> soff;
+	try {
+		const u32 k = dust_mask(c, W, T, piece, false, &serial);
+		if (n_serial) *n_serial = k;
+		if (k) {                                                  // the flagged reads, set one behind the other, through k_sdust as it is
+			soff.resize((size_t)k + 1);
+			soff[0] = 0;
+			for (u32 j = 0; j < k; ++j) soff[j + 1] = soff[j] + (c.off[serial[j] + 1] - c.off[serial[j]]);
+			c.slist.ensure((size_t)k * 4); c.soff.ensure(((size_t)k + 1) * 8); c.sseq.ensure(soff[k] + 16);
+			c.smasked.ensure(k * 4 + 4); c.spsum.ensure(k * 8 + 8); c.sqv.ensure(k * 4 + 4);
+			LQ_HIP_CHECK(hipMemcpyAsync(c.slist.p, serial.data(), (size_t)k * 4, hipMemcpyHostToDevice, c.stream));
+			LQ_HIP_CHECK(hipMemcpyAsync(c.soff.p, soff.data(), ((size_t)k + 1) * 8, hipMemcpyHostToDevice, c.stream));
+			LQ_LAUNCH(k_sdust_compact, std::min<u32>(k, LQ_DUST_SPLIT_MAX_BLOCKS), LQ_DUST_SPLIT_THREADS, c.stream, c.seq.as<u8>(), c.d_off.as<u64>(),
+			          c.slist.as<u32>(), c.soff.as<u64>(), k, c.sseq.as<u8>());
+			const u32 n_thr = (u32)std::min<u64>(((u64)k + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_MAX_THREADS);
+			c.pi.ensure((u64)n_thr * LQ_DUST_PCAP * sizeof(DustPI));
+			LQ_LAUNCH(k_sdust, nblk_d(n_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, c.stream, c.sseq.as<u8>(), (const u8*)nullptr, c.soff.as<u64>(), k, (i32)W, (i32)T,
+			          c.q2p.as<double>(), c.pi.as<DustPI>(), c.smasked.as<u32>(), c.spsum.as<double>(), c.sqv.as<u32>());
+			LQ_LAUNCH(k_sdust_scatter, std::min<u32>((k + LQ_DUST_SPLIT_THREADS - 1) / LQ_DUST_SPLIT_THREADS, LQ_DUST_SPLIT_MAX_BLOCKS), LQ_DUST_SPLIT_THREADS, c.stream,
+			          c.smasked.as<u32>(), c.slist.as<u32>(), k, c.masked.as<u32>());
+			LQ_HIP_CHECK(hipGetLastError());
+		}
+		if (k < n) {
+			LQ_LAUNCH(k_sdust_mask_count, (u32)std::min<u64>(((u64)n + 3) / 4, LQ_DUST_SPLIT_MAX_BLOCKS), LQ_DUST_SPLIT_THREADS, c.stream, c.dmask.as<u32>(), c.d_off.as<u64>(),
+			          c.dflag.as<u8>(), n, c.masked.as<u32>());
+			LQ_HIP_CHECK(hipGetLastError());
+		}
+		LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream2));
+		LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream2));
+	} catch (...) {                                              // (nothing of this call stays queued behind the caller's buffers)
+		(void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(c.stream2);
+		throw;
+	}
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));                 // (`serial` and `soff` die here)
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream2));
+}
+
+void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece)
+{
+	dust_checks(c, W);
+	piece = dust_piece(c, W, piece);
+	const u32 n = c.n;
+	if (n == 0) { c.h_iv.clear(); c.h_ivoff.assign(1, 0); c.h_dflag.clear(); c.iv_valid = false; return; }
+	// the second of the two calls (iv == NULL, then iv != NULL) finds the first one's runs: the same W, T and piece on the same reads
+	if (c.iv_valid && c.iv_W == W && c.iv_T == T && c.iv_piece == piece) return;
+	lq_chunk_ready(c);
+	dust_mask(c, W, T, piece, true, nullptr);
+	const u64 n_words = (c.total + 31) / 32 + 1;
+	std::vector<u32> m((size_t)n_words);
+	LQ_HIP_CHECK(hipMemcpyAsync(m.data(), c.dmask.p, n_words * 4, hipMemcpyDeviceToHost, c.stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+	c.h_iv.clear(); c.h_ivoff.assign((size_t)n + 1, 0);
+	for (u32 r = 0; r < n; ++r) {
+		const u64 a = c.off[r], b = c.off[r + 1];
+		if (!c.h_dflag[r])
+			for (u64 g = a; g < b;) {                             // word-wise: the next set bit, then the next clear one
+				u32 w = m[g >> 5] >> (g & 31);
+				if (!w) { g = (g | 31) + 1; continue; }
+				g += __builtin_ctz(w);
+				if (g >= b) break;
+				u64 e = g;
+				while (e < b) {
+					const u32 v = ~(m[e >> 5] >> (e & 31));           // (the shift brings zeros in: they end the run at the word's end at the latest)
+					const u32 room = 32 - (u32)(e & 31), z = v ? (u32)__builtin_ctz(v) : 32u;
+					if (z < room) { e += z; break; }
+					e += room;
+				}
+				if (e > b) e = b;
+				c.h_iv.push_back((g - a) << 32 | (e - a));
+				g = e;
+			}
+		c.h_ivoff[r + 1] = c.h_iv.size();
+	}
+	c.iv_valid = true; c.iv_W = W; c.iv_T = T; c.iv_piece = piece;
 }
 
 extern "C" {
@@ -95,6 +252,9 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 		std::vector<u32> masked, qv;
 		std::vector<double> psum;
 		const bool timing = getenv("LQCOV_TIMING") != nullptr;
+		const char *split_env = getenv("LQSDUST_SPLIT");          // "pieces": long reads of A/C/G/T alone are cut (kernels_dust_split.hpp); the table is the same
+		const bool split = split_env && !strcmp(split_env, "pieces");
+		if (split_env && !split && strcmp(split_env, "serial")) throw std::invalid_argument("LQSDUST_SPLIT must be 'serial' or 'pieces'");
 		double t_wait = 0, t_dev = 0, t_rows = 0, t_parse = 0;
 		// The reader runs ahead on a thread of its own (round 6): mini-batch i + 1 is parsed while mini-batch i is on the device --
 		// the two took 0.63 s and 0.64 s one after the other for configs[1]'s 744 Mbases.  Two batches in flight, handed over in order.
@@ -127,7 +287,8 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 			masked.resize(n); qv.resize(n); psum.resize(n);
 			double t1 = lq_now_s(); t_wait += t1 - t0;
 			lq_chunk_set(D, n, rb.seq.data(), rb.seq_off.data(), rb.any_qual ? rb.qual.data() : nullptr);
-			lq_chunk_sdust(D, W, T, masked.data(), psum.data(), qv.data());
+			if (split) lq_chunk_sdust_split(D, W, T, 0, masked.data(), psum.data(), qv.data(), nullptr);
+			else lq_chunk_sdust(D, W, T, masked.data(), psum.data(), qv.data());
 			t0 = lq_now_s(); t_dev += t0 - t1;
 			for (u32 i = 0; i < n; ++i) {
 				const int len = (int)(rb.seq_off[i + 1] - rb.seq_off[i]);

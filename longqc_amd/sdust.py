@@ -23,6 +23,20 @@ def _lib(lib=None):
     return lib
 
 
+SPLIT_MODES = ("serial", "pieces")
+SPLIT_PIECE = 4096                                         # LQ_DUST_SPLIT_PIECE: bases per piece unless the caller says otherwise
+SPLIT_MIN_PIECES = 2                                       # LQ_DUST_SPLIT_MIN_PIECES: a read of fewer pieces' bases takes the serial walk
+
+
+def split_mode(split):
+    """"serial" | "pieces" | None (the environment variable LQSDUST_SPLIT, "serial" without it) -> the mode's name.  "pieces": reads
+    of A/C/G/T alone with two pieces' bases or more are cut into pieces scanned side by side (k_sdust_pieces); the table is the same"""
+    mode = os.environ.get("LQSDUST_SPLIT", "serial") if split is None else split
+    if mode not in SPLIT_MODES:
+        raise ValueError("split must be 'serial' or 'pieces', not %r" % (mode,))
+    return mode
+
+
 def run_sdust(fin: str, fout: str, device: int = 0, w: Optional[int] = None, t: Optional[int] = None, lib=None) -> None:
     """== lq_mask._sdust(psdust, fin, fout): `sdust <fin>` with stdout -> fout (lq_mask.py:17-23)"""
     lib = _lib(lib)
@@ -46,12 +60,24 @@ def run_sdust(fin: str, fout: str, device: int = 0, w: Optional[int] = None, t: 
 
 
 def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional[Sequence[Optional[np.ndarray]]] = None,
-               device: int = 0, w: int = 64, t: int = 20, lib=None, chunk=None) -> List[str]:
+               device: int = 0, w: int = 64, t: int = 20, lib=None, chunk=None, split: Optional[str] = None,
+               piece: Optional[int] = None) -> List[str]:
     """Reads in memory (no temporary FASTQ as in lq_mask.py:108-114) -> the rows `sdust` would print for them.
     chunk: a chunkpass.ReadChunk that holds these reads on the device already -- seqs and quals are not looked at, nothing is
-    gathered or uploaded."""
+    gathered or uploaded.  split, piece: split_mode's; "pieces" scans long reads in pieces of `piece` bases (lqchunk_sdust_split) --
+    the rows are the same."""
+    split = split_mode(split)
     if chunk is not None:
-        return _rows(names, chunk.n, chunk.off, chunk.qual_first(), *chunk.sdust(w, t))
+        return _rows(names, chunk.n, chunk.off, chunk.qual_first(), *chunk.sdust(w, t, split=split, piece=piece))
+    if split == "pieces":                                  # (the pieces live on a resident chunk: one for this call)
+        from . import chunkpass
+        qs = quals if quals is not None else [None] * len(seqs)
+        reads = [[nm, bytes(s), bytes(q) if q is not None and q.shape[0] else None] for nm, s, q in zip(names, seqs, qs)]
+        ch = chunkpass.ReadChunk(reads, device=device, lib=lib)
+        try:
+            return _rows(names, ch.n, ch.off, ch.qual_first(), *ch.sdust(w, t, split=split, piece=piece))
+        finally:
+            ch.close()
     lib = _lib(lib)
     n = len(seqs)
     off = np.zeros(n + 1, dtype=np.uint64)
@@ -93,7 +119,8 @@ class LqMaskMI355X:
     row per read in submission order.  Reads are LongQC's [name, seq, qual, ...] records (str or bytes); no temporary
     FASTQ files, no process pool: every chunk is one call into the device.  The plots of LqMask are out of scope."""
 
-    def __init__(self, work_dir: str, suffix: Optional[str] = None, device: int = 0, lib=None):
+    def __init__(self, work_dir: str, suffix: Optional[str] = None, device: int = 0, lib=None, split: Optional[str] = None):
+        self.split = split_mode(split)                         # "pieces": long reads are scanned in pieces, the rows are the same
         self.suffix = "_" + suffix if suffix else ""
         os.makedirs(work_dir, exist_ok=True)
         self.wdir, self.device, self.lib = work_dir, device, lib
@@ -111,12 +138,12 @@ class LqMaskMI355X:
     def submit_sdust(self, reads, chunk_n, chunk=None):
         """chunk: the chunkpass.ReadChunk made of `reads` (its device copy is scanned; `reads` is not gathered again)"""
         if chunk is not None:
-            self._chunks[chunk_n] = sdust_rows(chunk.names, None, None, chunk=chunk)
+            self._chunks[chunk_n] = sdust_rows(chunk.names, None, None, chunk=chunk, split=self.split)
             return
         names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
         seqs = [self._arr(r[1]) for r in reads]
         quals = [self._arr(r[2]) if len(r) > 2 and r[2] else None for r in reads]
-        self._chunks[chunk_n] = sdust_rows(names, seqs, quals, device=self.device, lib=self.lib)
+        self._chunks[chunk_n] = sdust_rows(names, seqs, quals, device=self.device, lib=self.lib, split=self.split)
 
     def close_pool(self):
         with open(self.outf, "w") as out:                      # lq_mask.py:83-88 concatenates the chunk tables in submission order
