@@ -491,7 +491,7 @@ int  lqinflate_gzip(int device, const uint8_t *comp, uint64_t comp_len, uint32_t
                     lqinflate_stats *stats);
 /* The record scan on the device, opt-in: lqreader_parse(r, LQREADER_PARSE_DEVICE) -- before the first lqreader_next,
  * LQCOV_E_STATE afterwards; the default is LQREADER_PARSE_HOST, or what the environment variable LQREADER_PARSE ("device") says when
- * the reader is opened; a BAM reader accepts the mode and ignores it.  Every piece of the file is then uploaded as it is read (with
+ * the reader is opened; a BAM reader accepts the mode and ignores it (its switch is lqreader_bam_walk, below).  Every piece of the file is then uploaded as it is read (with
  * lqreader_inflate's device mode it is there already), k_fx_* find the records of the piece there and write the segment lists that
  * k_chunk_gather reads; the host gets 16 bytes per record (where the name is, its length, the sequence's length, whether there is a
  * quality string), copies the names out of the piece and applies the chunk rule.  The device answers only for records it can vouch
@@ -525,7 +525,8 @@ int  lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos,
 /* Inflated bytes that stay on the device, opt-in: lqreader_host_copy(r, LQREADER_HOSTCOPY_NEEDED) -- before the first
  * lqreader_next, LQCOV_E_STATE afterwards; the default is LQREADER_HOSTCOPY_ALL, or what the environment variable LQREADER_HOSTCOPY
  * ("needed") says when the reader is opened.  The mode is active for a FASTA/FASTQ file that the device both inflates and parses
- * (lqreader_inflate and lqreader_parse in their device modes, a BGZF or gzip file); any other reader accepts it and ignores it.
+ * (lqreader_inflate and lqreader_parse in their device modes, a BGZF or gzip file) and for a BAM file that the device both inflates
+ * and walks (lqreader_inflate and lqreader_bam_walk in their device modes); any other reader accepts it and ignores it.
  * When it is active the inflated bytes are not copied back: k_crc32_ranges makes every member's CRC32 from the chunk's raw device
  * buffer (BGZF: one value per block; gzip spans: the bytes a launch accepted, folded into the member's value by length; what zlib
  * inflates on the host is checked there as before), k_fx_names gathers the names of the records the device vouches for, and the
@@ -553,6 +554,31 @@ int  lqreader_copy_stats(const lqreader *r, lqcopy_stats *stats);
 int  lqcrc32_ranges(int device, const uint8_t *bytes, uint64_t n_bytes, uint32_t n, const uint64_t *off, const uint64_t *len, uint32_t *crc_out);
 int  lqfx_names(int device, const uint8_t *bytes, uint64_t n, const uint32_t *rows, uint64_t n_rows, char *names_out, uint64_t names_cap,
                 uint64_t *name_off_out, uint64_t *first_bad);
+/* The record walk of an unaligned BAM on the device, opt-in: lqreader_bam_walk(r, LQREADER_BAMWALK_DEVICE) -- before
+ * the first lqreader_next, LQCOV_E_STATE afterwards; the default is LQREADER_BAMWALK_HOST, or what the environment variable
+ * LQREADER_BAMWALK ("device") says when the reader is opened; a FASTA/FASTQ reader accepts the mode and ignores it.  Every piece of
+ * inflated bytes is then on the device as it comes (uploaded, or with lqreader_inflate's device mode there already), k_bam_* find
+ * the records of the piece there and write the segment lists that k_bam_gather / k_bam_qual read; the host gets 16 bytes per record
+ * and applies the chunk rule.  The device answers only for records it can vouch for: offset o of a piece of n bytes is vouched iff
+ * o + 36 <= n, refID = pos = next_refID = next_pos = -1 (bytes o+4 .. o+11 and o+24 .. o+31 are 0xff), l_read_name >= 1, l_seq and
+ * block_size <= 2^31 - 1, block_size >= 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq, o + 4 + block_size <= n and the
+ * byte o + 36 + l_read_name - 1 is 0; the records it reports are the longest run of vouched offsets of the chain start, next(start),
+ * .. with next(o) = o + 4 + block_size.  Everything else -- the BAM header, aligned records, broken records, the record that
+ * straddles the piece's end, the end of the file -- is the host walk's as before; chunks, borders, counts, names and errors are the
+ * host walk's.  lqreader_parse_stats reports for it in the same fields (lines: the candidates the scans examined).  With
+ * lqreader_inflate's device mode as well, lqreader_host_copy(r, LQREADER_HOSTCOPY_NEEDED) is active for the BAM: the blocks' CRC32 and
+ * the names are made on the device, the host fetches what the header and its own walk look at.
+ * lqbam_scan is the array-level call: bytes[0 .. n) on the host, the inflated bytes of a piece, a parser that stands at start_pos, a
+ * record boundary behind the BAM header.  rows, sseg, qseg, the counts and the errors are lqfx_scan's (rows: name offset, strlen of
+ * the name, l_seq, flags: bit 0 with_qual; one sseg per record with bases, src the first byte of the packed sequence; one qseg, src
+ * the first quality byte with with_qual, else all ones); lqfx_names accepts the rows.  *resume_pos: the first offset of the chain
+ * that is not vouched, or n. */
+#define LQREADER_BAMWALK_HOST   0
+#define LQREADER_BAMWALK_DEVICE 1
+int  lqreader_bam_walk(lqreader *r, int mode);
+int  lqbam_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, int with_qual, uint32_t *rows, uint64_t n_rows_cap,
+                uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg,
+                uint64_t *resume_pos);
 int  lqchunk_get_reads(lqchunk *c, uint32_t n_idx, const uint32_t *idx, uint8_t *seq_out, uint8_t *qual_out);
 
 /* ---- the chunk loop's files: trimmed reads (longQC.py:345-346) and the FASTQ a BAM file is converted to (:302-303) ------------------ */

@@ -58,6 +58,8 @@ def _lib(lib=None):
             "lqreader_parse_stats": (C.c_int, [H, P]),
             "lqfx_scan": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint64, C.c_int, P, C.c_uint64, P, P, C.c_uint64, P, P, P, P, P]),
             "lqreader_host_copy": (C.c_int, [H, C.c_int]),
+            "lqreader_bam_walk": (C.c_int, [H, C.c_int]),
+            "lqbam_scan": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint64, C.c_int, P, C.c_uint64, P, P, C.c_uint64, P, P, P, P]),
             "lqreader_copy_stats": (C.c_int, [H, P]),
             "lqcrc32_ranges": (C.c_int, [C.c_int, P, C.c_uint64, C.c_uint32, P, P, P]),
             "lqfx_names": (C.c_int, [C.c_int, P, C.c_uint64, P, C.c_uint64, P, C.c_uint64, P, P]),
@@ -200,6 +202,36 @@ def scan_records(data, start_pos: int = 0, last_char: int = 0, device: int = 0, 
     if rc != 0:
         raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
     return rows[:n_rows.value].copy(), sseg[:n_s.value].copy(), qseg[:n_q.value].copy(), (r_pos.value, r_lc.value)
+
+
+BAMWALK_MODES = {"host": 0, "device": 1}
+
+
+def bam_walk_mode(bam_walk):
+    """"host" | "device" | None (the environment variable LQREADER_BAMWALK, "host" without it) -> the mode's name"""
+    mode = os.environ.get("LQREADER_BAMWALK", "host") if bam_walk is None else bam_walk
+    if mode not in BAMWALK_MODES:
+        raise ValueError("bam_walk must be 'host' or 'device', not %r" % (mode,))
+    return mode
+
+
+def scan_bam_records(data, start_pos: int = 0, with_qual: bool = False, device: int = 0, lib=None):
+    """The record walk of an unaligned BAM on the device over bytes in memory (lqbam_scan: k_bam_candidates, k_bam_link, k_fx_jump,
+    k_bam_emit).  data: inflated BAM bytes; a parser stands at data[start_pos], a record boundary behind the BAM header.  -> (rows
+    uint32[n, 4]: name offset, name length (up to the first NUL), l_seq, flags (bit 0: with_qual) of every record the device vouches
+    for, in file order; sseg, qseg uint64[k, 2]: (src, dst) per record with bases -- src the first byte of the packed sequence / of
+    the quality bytes, GATHER_FILL without with_qual; resume: the first offset of the chain that is not vouched, or len(data))"""
+    lib = _lib(lib)
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = buf.shape[0]
+    cap = n // 36 + 2
+    rows, sseg, qseg = np.zeros((cap, 4), np.uint32), np.zeros((cap, 2), np.uint64), np.zeros((cap, 2), np.uint64)
+    n_rows, n_s, n_q, r_pos = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = lib.lqbam_scan(device, buf.ctypes.data if n else None, n, int(start_pos), int(bool(with_qual)), rows.ctypes.data, cap, sseg.ctypes.data,
+                        qseg.ctypes.data, cap, C.byref(n_rows), C.byref(n_s), C.byref(n_q), C.byref(r_pos))
+    if rc != 0:
+        raise api.LqcovError(rc, lib.lqreader_last_error(None).decode())
+    return rows[:n_rows.value].copy(), sseg[:n_s.value].copy(), qseg[:n_q.value].copy(), r_pos.value
 
 
 HOSTCOPY_MODES = {"all": 0, "needed": 1}
@@ -445,15 +477,19 @@ class FileChunks:
     parse="device": the records of a FASTA/FASTQ file are found on the device (k_fx_*, lqreader_parse) wherever it vouches for them,
     by the host parser elsewhere; "host": by the host parser; None: the environment variable LQREADER_PARSE, "host" without it.  The
     chunks are the same; parse_stats (a dict of PARSE_STATS) says after iteration who found what.  A BAM file ignores the mode.
+    bam_walk="device": the records of a BAM file are found on the device (k_bam_*, lqreader_bam_walk) wherever it vouches for them --
+    unaligned records that are whole inside a piece -- by the host walk elsewhere; "host": by the host walk; None: the environment
+    variable LQREADER_BAMWALK, "host" without it.  The chunks are the same; parse_stats reports.  A FASTA/FASTQ file ignores the mode.
     host_copy="needed": where the device both inflates and parses a FASTA/FASTQ file, the inflated bytes stay there -- the members'
     CRC32 (k_crc32_ranges) and the names (k_fx_names) are made on the device and the host fetches only what its own parser must see;
-    "all": every inflated byte comes back; None: the environment variable LQREADER_HOSTCOPY, "all" without it.  Any other file or
-    mode ignores it.  The chunks are the same; copy_stats (a dict of COPY_STATS) says after iteration what moved."""
+    "all": every inflated byte comes back; None: the environment variable LQREADER_HOSTCOPY, "all" without it.  A BAM file honours
+    it where the device both inflates and walks it (inflate and bam_walk "device").  Any other file or mode ignores it.  The chunks are the same; copy_stats (a dict of COPY_STATS) says after iteration what moved."""
 
     def __init__(self, path: str, chunk_size=0.5 * 1024 ** 3, is_upper: bool = True, device: int = 0, str_overhead: Optional[int] = None,
                  lib=None, n_threads: int = 0, is_sequel: bool = True, inflate: Optional[str] = None, parse: Optional[str] = None,
-                 host_copy: Optional[str] = None):
+                 host_copy: Optional[str] = None, bam_walk: Optional[str] = None):
         self.lib = _lib(lib)
+        self.bam_walk = bam_walk_mode(bam_walk)
         self.host_copy, self.copy_stats = host_copy_mode(host_copy), dict.fromkeys(COPY_STATS, 0)
         self.inflate = inflate_mode(inflate)
         self.parse, self.parse_stats = parse_mode(parse), dict.fromkeys(PARSE_STATS, 0)
@@ -471,7 +507,8 @@ class FileChunks:
         try:
             self.format = lib.lqreader_format(r)
             for rc in (lib.lqreader_bam_qualities(r, 1) if not self.is_sequel else 0, lib.lqreader_inflate(r, INFLATE_MODES[self.inflate]),
-                       lib.lqreader_parse(r, PARSE_MODES[self.parse]), lib.lqreader_host_copy(r, HOSTCOPY_MODES[self.host_copy])):
+                       lib.lqreader_parse(r, PARSE_MODES[self.parse]), lib.lqreader_host_copy(r, HOSTCOPY_MODES[self.host_copy]),
+                       lib.lqreader_bam_walk(r, BAMWALK_MODES[self.bam_walk])):
                 if rc != 0:
                     raise api.LqcovError(rc, lib.lqreader_last_error(r).decode())
             chunk = ReadChunk(None, device=self.device, lib=lib)
@@ -660,9 +697,9 @@ class SampleQCPass:
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
                  is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None,
-                 host_copy: Optional[str] = None, sdust_split: Optional[str] = None):
+                 host_copy: Optional[str] = None, sdust_split: Optional[str] = None, bam_walk: Optional[str] = None):
         """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse,
-        host_copy: FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
+        host_copy, bam_walk: FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
         trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
         appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
         `trimmed` stays None and `trimmed_chunks` empty.  fastx_out=<path>: every chunk is appended to that file untrimmed -- the
@@ -684,7 +721,7 @@ class SampleQCPass:
                 self.fastx_writer = FastqWriter(fastx_out, device=self.device, lib=self.lib)
                 writers.append(self.fastx_writer)
             for chunk, _n_seqs, _n_bases in FileChunks(path, chunk_size, is_upper, self.device, str_overhead, lib=self.lib, is_sequel=is_sequel,
-                                                        inflate=inflate, parse=parse, host_copy=host_copy):
+                                                        inflate=inflate, parse=parse, host_copy=host_copy, bam_walk=bam_walk):
                 if fastx_out is not None:
                     self.fastx_writer.write(chunk)                                                      # longQC.py:302-303
                 results.append(self.add_resident(chunk, trim=trim))

@@ -75,8 +75,8 @@ static void gather_launch(lqchunk &c, const u8 *raw, std::vector<GatherSeg> &seg
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (tile_seg dies here, and the two device lists serve the next launch)
 }
 
-// the same launch from segments that lie on the device (segs: room for one more entry): the work list is made there too
-static void gather_launch_dev(lqchunk &c, const u8 *raw, GatherSeg *segs, u64 n_segs, u8 *dst, bool upper)
+// the same launch from segments that lie on the device (segs: room for one more entry): the work list is made there too; kind as above
+static void gather_launch_dev(lqchunk &c, const u8 *raw, GatherSeg *segs, u64 n_segs, u8 *dst, bool upper, int kind)
 {
 	const u64 total = c.total;
 	if (!total) return;
@@ -89,7 +89,9 @@ static void gather_launch_dev(lqchunk &c, const u8 *raw, GatherSeg *segs, u64 n_
 	const u32 tgrid = (u32)std::min<u64>((n_tiles + 1 + LQ_FXSCAN_THREADS - 1) / LQ_FXSCAN_THREADS, LQ_FXSCAN_TILESEG_MAX_BLOCKS);
 	LQ_LAUNCH(k_fx_tileseg, tgrid, LQ_FXSCAN_THREADS, c.stream, (const GatherSeg*)segs, (u32)n_segs, n_tiles, LQ_GATHER_TILE, c.gtile.as<u32>());
 	const u32 grid = (u32)std::min<u64>(n_tiles, LQ_GATHER_MAX_BLOCKS);
-	LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, (const GatherSeg*)segs, (const u32*)c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
+	if (kind == 1) LQ_LAUNCH(k_bam_gather, grid, LQ_GATHER_THREADS, c.stream, raw, (const GatherSeg*)segs, (const u32*)c.gtile.as<u32>(), n_tiles, total, dst);
+	else if (kind == 2) LQ_LAUNCH(k_bam_qual, grid, LQ_GATHER_THREADS, c.stream, raw, (const GatherSeg*)segs, (const u32*)c.gtile.as<u32>(), n_tiles, total, dst);
+	else LQ_LAUNCH(k_chunk_gather, grid, LQ_GATHER_THREADS, c.stream, raw, (const GatherSeg*)segs, (const u32*)c.gtile.as<u32>(), n_tiles, total, dst, upper ? 1 : 0);
 	LQ_HIP_CHECK(hipGetLastError());
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));             // (`end` dies here)
 }
@@ -109,11 +111,11 @@ static void gather_begin(lqchunk &c, const std::vector<u64> &off)
 	LQ_HIP_CHECK(hipMemcpyAsync(c.d_off.p, c.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c.stream));
 }
 
-void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper)
+void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper, int bam)
 {
 	gather_begin(c, off);
-	gather_launch_dev(c, raw, sseg, n_sseg, c.seq.as<u8>(), upper);
-	gather_launch_dev(c, raw, qseg, n_qseg, c.qual.as<u8>(), false);
+	gather_launch_dev(c, raw, sseg, n_sseg, c.seq.as<u8>(), upper, bam ? 1 : 0);
+	gather_launch_dev(c, raw, qseg, n_qseg, c.qual.as<u8>(), false, bam == 2 ? 2 : 0);
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
 	c.resident = true;
 }

@@ -59,8 +59,9 @@ void lq_chunk_ready(lqchunk &c);
 // names every read's packed sequence (kernels_bam.hpp) and qseg is LQ_GATHER_FILL throughout; 2 qseg names the reads' quality bytes.
 void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std::vector<GatherSeg> &sseg, std::vector<GatherSeg> &qseg, bool upper, int bam = 0);
 // the same from segment lists that lie on the device already (the reader's device parse, kernels_fxscan.hpp): n_sseg / n_qseg entries
-// in destination order, room for one more behind each; the per-tile work list is made on the device (k_fx_tileseg)
-void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper);
+// in destination order, room for one more behind each; the per-tile work list is made on the device (k_fx_tileseg).  bam: as
+// lq_chunk_gather's (the reader's device walk of a BAM file, kernels_bamscan.hpp)
+void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper, int bam = 0);
 void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
 // the same table with the reads of A/C/G/T alone cut into pieces of `piece` bases (0: LQ_DUST_SPLIT_PIECE), the others walked by k_sdust;
 // n_serial (may be null): how many those were

@@ -28,6 +28,11 @@
 // of the records the scan vouches for, and the piece on the host holds only what host_bytes() has fetched: buf[v_lo .. v_hi), brought
 // up to [pos - 1, fill) whenever parse_one is about to look.
 //
+// lqreader_bam_walk(r, LQREADER_BAMWALK_DEVICE), for a BAM file: the records of a piece are found on the device (bamscan.hpp,
+// kernels_bamscan.hpp) wherever it vouches for them -- unaligned records that are whole inside the piece -- through DeviceParse's loop,
+// and parse_bam_one takes what the device leaves; with lqreader_inflate's device mode lqreader_host_copy is then active for the BAM
+// too.
+//
 // The parts: a Source (pread, gzread, BGZF blocks or gzip spans, chosen once) fills the Piece; parse_one, parse_bam_one (BamHeader) or
 // DeviceParse (fxscan.hpp) finds the records, and each joins the chunk through ChunkParts::append_read: names, offsets, counts, the
 // chunk rule.  What a Source finds wrong with its file is an lq_file_error; read_more gives it the path (LQCOV_E_IO by type).
@@ -38,6 +43,7 @@
 #include "kernels_crc32.hpp"
 #include "gzip.hpp"
 #include "fxscan.hpp"
+#include "bamscan.hpp"
 #include <zlib.h>
 #include <cstdlib>
 #include <memory>
@@ -53,7 +59,7 @@ struct Record {
 	std::vector<Line> seq, qual;
 };
 
-enum { REC = 0, NEED_MORE = 1, END = 2 };
+enum { REC = 0, NEED_MORE = 1, END = 2, HDR = 3 };           // (HDR: parse_bam_one has put the BAM header behind it, nothing else)
 
 // k_bgzf_inflate over host arrays: the compressed bytes go up, the kernel writes into d_out (16-byte aligned), the statuses come back
 struct InflateDev {
@@ -239,7 +245,8 @@ struct BamHeader {
 
 // ---- lqreader_parse(r, LQREADER_PARSE_DEVICE): the records of a piece are found on the device (fxscan.hpp) wherever it vouches for them ----
 struct DeviceParse {
-	FxScan fx; lqparse_stats pst = {0, 0, 0, 0, 0, 0};
+	BamScan fx; lqparse_stats pst = {0, 0, 0, 0, 0, 0};
+	int bam = 0;                                              // 0: a FASTA/FASTQ file (fx.run); 1, 2: a BAM file without / with the file's qualities (fx.run_bam)
 	bool bol = true;                                          // the byte at pos -- with last_char, the header character in front of it -- is a line's first
 	u64 cur = 0, org = 0, seg_s = 0, seg_q = 0, base_d = 0;   // the last scan's rows from cur on wait for a chunk: the piece byte its positions count from, record cur's first segments and base
 	bool fresh = true, scanned = false, fb_counted = false, fb_at_end = false;      // bytes have come since the last scan; this piece has been scanned; that scan counts as a fallback / would if more records followed
@@ -264,7 +271,8 @@ struct DeviceParse {
 		if (!fresh && !(host_recs && !skip)) return false;
 		fresh = false; host_recs = 0;
 		org = pc.up_from; cur = 0; seg_s = seg_q = base_d = 0;
-		fx.run(stream, ck.raw.as<u8>() + ck.raw_used, pc.fill - pc.up_from, pc.pos - pc.up_from, pc.last_char);
+		if (bam) fx.run_bam(stream, ck.raw.as<u8>() + ck.raw_used, pc.fill - pc.up_from, pc.pos - pc.up_from, bam == 2);
+		else fx.run(stream, ck.raw.as<u8>() + ck.raw_used, pc.fill - pc.up_from, pc.pos - pc.up_from, pc.last_char);
 		if (!fx.n_lines) return false;
 		++pst.scans; pst.lines += fx.n_lines;
 		if (fx.n_rows && fb_at_end) ++pst.fallbacks;              // (the scan before stopped in front of these)
@@ -301,7 +309,7 @@ struct DeviceParse {
 		LQ_HIP_CHECK(hipGetLastError());
 		ck.n_dss += ns; ck.n_dqs += nq; seg_s = s1; seg_q = q1;
 		base_d += ck.off.back() - dst0;
-		if (cur < fx.n_rows) { pc.pos = org + fx.h_rows[cur].name_at - 1; pc.last_char = 0; }
+		if (cur < fx.n_rows) { pc.pos = org + fx.h_rows[cur].name_at - (bam ? 36 : 1); pc.last_char = 0; }      // (the record's first byte)
 		else { pc.pos = org + fx.resume_pos; pc.last_char = fx.resume_last_char; }
 		bol = true;
 		return ended;
@@ -318,6 +326,7 @@ struct lqreader {
 	bool bam_qual = false;                                       // the qualities come from the file
 	int inflate_mode = LQREADER_INFLATE_HOST, parse_mode = LQREADER_PARSE_HOST;   // lqreader_inflate's, lqreader_parse's
 	int host_copy = LQREADER_HOSTCOPY_ALL;                    // lqreader_host_copy's
+	int bam_walk = LQREADER_BAMWALK_HOST;                     // lqreader_bam_walk's
 	bool keep = false;                                        // ... and it is active: the inflated bytes stay on the device
 	u64 v_lo = 0, v_hi = 0;                                   // keep: buf[v_lo .. v_hi) is what the host holds of the piece
 	lqcopy_stats cst = {0, 0, 0, 0, 0, 0};
@@ -377,7 +386,8 @@ struct lqreader {
 	void start()
 	{
 		started = true;
-		dev_parse = parse_mode == LQREADER_PARSE_DEVICE && format == 0;
+		dev_parse = format == 1 ? bam_walk == LQREADER_BAMWALK_DEVICE : parse_mode == LQREADER_PARSE_DEVICE;
+		if (format == 1) { dp.bam = bam_qual ? 2 : 1; dp.bol = false; }      // (the scan waits for the header's end)
 		keep = host_copy == LQREADER_HOSTCOPY_NEEDED && dev_parse && inflate_mode == LQREADER_INFLATE_DEVICE && gzip;
 		cst.active = keep;
 		if (keep) dp.names_dev = &cst;
@@ -547,14 +557,15 @@ struct lqreader {
 		return REC;
 	}
 
-	// one BAM record at buf[pos ..) into the chunk.  NEED_MORE: the record is not whole in the piece yet
+	// one BAM record at buf[pos ..) into the chunk.  NEED_MORE: the record is not whole in the piece yet; HDR (device walk): the header is over
 	int parse_bam_one()
 	{
 		if (hdr.state != 5) {
 			const bool in = hdr.advance(pc);
-			if (src->in_mirror) ck.raw_used += pc.pos - pc.up_from;   // (the header is in the raw bytes already)
+			if (mirror) ck.raw_used += pc.pos - pc.up_from;           // (the header is in the raw bytes already)
 			pc.up_from = pc.pos;                                      // (no descriptor points into the header: it is not uploaded)
 			if (!in) { if (pc.eof) bam_fail("the file ends inside the BAM header"); return NEED_MORE; }
+			if (dev_parse) return HDR;                                // (the first record is the scan's to find like any other)
 		}
 		const u64 have = pc.fill - pc.pos;
 		const std::string where = "BAM record " + std::to_string(ck.n_seqs + 1) + ": ";
@@ -638,9 +649,11 @@ struct lqreader {
 			const u64 pos0 = pc.pos;
 			host_bytes();
 			const int st = format == 1 ? parse_bam_one() : parse_one();
-			if (st == REC) dp.bol = true;
+			if (format == 1) dp.bol = hdr.state == 5;                 // (a BAM parser stands at a record boundary once the header is behind it)
+			else if (st == REC) dp.bol = true;
 			else if (pc.pos != pos0) dp.bol = pc.buf[pc.pos - 1] == '\n';
 			if (st == NEED_MORE) { refill(); continue; }
+			if (st == HDR) continue;
 			if (st == END) { over = true; break; }
 			if (dev_parse) dp.on_host_record(pc.eof);
 			if (format == 0) add_record();
@@ -649,7 +662,7 @@ struct lqreader {
 		if (dev_parse) ck.flush_host_segs(c.stream);
 		upload();
 		done = !ended;
-		if (dev_parse) lq_chunk_gather_dev(c, ck.off, ck.raw.as<u8>(), ck.d_sseg.as<GatherSeg>(), ck.n_dss, ck.d_qseg.as<GatherSeg>(), ck.n_dqs, upper);
+		if (dev_parse) lq_chunk_gather_dev(c, ck.off, ck.raw.as<u8>(), ck.d_sseg.as<GatherSeg>(), ck.n_dss, ck.d_qseg.as<GatherSeg>(), ck.n_dqs, upper, dp.bam);
 		else lq_chunk_gather(c, ck.off, ck.raw.as<u8>(), ck.sseg, ck.qseg, upper, format == 1 ? (bam_qual ? 2 : 1) : 0);
 		*n_out = c.n; *n_seqs_cum = ck.n_seqs; *n_bases_cum = ck.n_bases; *last = done ? 1 : 0;
 	}
@@ -689,6 +702,8 @@ lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int i
 		if (mode && !strcmp(mode, "device")) r->inflate_mode = LQREADER_INFLATE_DEVICE;
 		const char *pm = getenv("LQREADER_PARSE");
 		if (pm && !strcmp(pm, "device")) r->parse_mode = LQREADER_PARSE_DEVICE;
+		const char *bw = getenv("LQREADER_BAMWALK");
+		if (bw && !strcmp(bw, "device")) r->bam_walk = LQREADER_BAMWALK_DEVICE;
 		const char *hc = getenv("LQREADER_HOSTCOPY");
 		if (hc && !strcmp(hc, "needed")) r->host_copy = LQREADER_HOSTCOPY_NEEDED;
 		r->open_file();
@@ -740,6 +755,14 @@ int lqreader_parse(lqreader *r, int mode)
 	if (!r || (mode != LQREADER_PARSE_HOST && mode != LQREADER_PARSE_DEVICE)) return LQCOV_E_ARG;
 	if (r->started) { r->err = "lqreader_parse after the first lqreader_next"; return LQCOV_E_STATE; }
 	r->parse_mode = mode;
+	return 0;
+}
+
+int lqreader_bam_walk(lqreader *r, int mode)
+{
+	if (!r || (mode != LQREADER_BAMWALK_HOST && mode != LQREADER_BAMWALK_DEVICE)) return LQCOV_E_ARG;
+	if (r->started) { r->err = "lqreader_bam_walk after the first lqreader_next"; return LQCOV_E_STATE; }
+	r->bam_walk = mode;
 	return 0;
 }
 
@@ -832,6 +855,30 @@ int lqfx_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, 
 		if (fx.n_qseg) LQ_HIP_CHECK(hipMemcpyAsync(qseg, fx.qseg.p, (size_t)fx.n_qseg * sizeof(GatherSeg), hipMemcpyDeviceToHost, stream));
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 		*n_rows = fx.n_rows; *n_sseg = fx.n_sseg; *n_qseg = fx.n_qseg; *resume_pos = fx.resume_pos; *resume_last_char = fx.resume_last_char;
+	});
+}
+
+int lqbam_scan(int device, const uint8_t *bytes, uint64_t n, uint64_t start_pos, int with_qual, uint32_t *rows, uint64_t n_rows_cap,
+               uint64_t *sseg, uint64_t *qseg, uint64_t seg_cap, uint64_t *n_rows, uint64_t *n_sseg, uint64_t *n_qseg, uint64_t *resume_pos)
+{
+	return one_shot([&] {
+		if (!n_rows || !n_sseg || !n_qseg || !resume_pos || (n && !bytes)) throw std::invalid_argument("null buffers");
+		if (start_pos > n) throw std::invalid_argument("no parser state");
+		*n_rows = *n_sseg = *n_qseg = 0; *resume_pos = start_pos;
+		if (start_pos >= n) return;
+		lq_cabi::ScopedStream stream(device);
+		DBuf d;
+		d.ensure((size_t)n + LQ_GATHER_SRC_PAD);
+		LQ_HIP_CHECK(hipMemcpyAsync(d.p, bytes, (size_t)n, hipMemcpyHostToDevice, stream));
+		BamScan bs;
+		bs.run_bam(stream, d.as<u8>(), n, start_pos, with_qual != 0);
+		if (bs.n_rows > n_rows_cap || bs.n_sseg > seg_cap || bs.n_qseg > seg_cap) throw std::invalid_argument("the tables are smaller than the scan's result");
+		if (bs.n_rows && (!rows || (bs.n_sseg && !sseg) || (bs.n_qseg && !qseg))) throw std::invalid_argument("null buffers");
+		if (bs.n_rows) memcpy(rows, bs.h_rows.data(), (size_t)bs.n_rows * sizeof(FxRow));
+		if (bs.n_sseg) LQ_HIP_CHECK(hipMemcpyAsync(sseg, bs.sseg.p, (size_t)bs.n_sseg * sizeof(GatherSeg), hipMemcpyDeviceToHost, stream));
+		if (bs.n_qseg) LQ_HIP_CHECK(hipMemcpyAsync(qseg, bs.qseg.p, (size_t)bs.n_qseg * sizeof(GatherSeg), hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		*n_rows = bs.n_rows; *n_sseg = bs.n_sseg; *n_qseg = bs.n_qseg; *resume_pos = bs.resume_pos;
 	});
 }
 

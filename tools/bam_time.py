@@ -13,7 +13,11 @@ statistics; it moves 1.5 B per base).  One JSON line (also written to $OUT/bam_t
 reads as a bgzip FASTQ (BGZF blocks of 65 280 bytes; "host" is gzread's one thread for it), the modes alternated within every
 repetition, the median and the spread per mode; $OUT/bam_time_inflate.json.  Around a `rocprofv3 --kernel-trace --stats` run with
 --inflate device, k_bgzf_inflate's time per launch comes from the statistics.
-Usage: python tools/bam_time.py [--reads 500000] [--chunk-mb 512] [--reps 3] [--workers 16] [--only bam] [--inflate host,device]"""
+--walk host,device and --host-copy all,needed (with --inflate): FileChunks' bam_walk and host_copy modes as well -- every combination
+of the three lists is a mode of its own ("device/device/needed": inflate, walk, host copy), alternated within every repetition on
+the BAM and on the tagged BAM (the bgzip FASTQ is left out: it has no record walk); both are meaningful with --inflate device.
+Usage: python tools/bam_time.py [--reads 500000] [--chunk-mb 512] [--reps 3] [--workers 16] [--only bam] [--inflate host,device]
+       [--walk host,device] [--host-copy all,needed]"""
 import argparse
 import dataclasses
 import json
@@ -78,10 +82,10 @@ def write_fastq_gz(path, F, pool):
     return len(text)
 
 
-def one_pass(path, cs, threads, inflate=None):
+def one_pass(path, cs, threads, inflate=None, walk=None, host_copy=None):
     t = time.perf_counter()
     n, nb = 0, 0
-    for ch, _n_seqs, nb in chunkpass.FileChunks(path, chunk_size=cs, n_threads=threads, inflate=inflate):
+    for ch, _n_seqs, nb in chunkpass.FileChunks(path, chunk_size=cs, n_threads=threads, inflate=inflate, bam_walk=walk, host_copy=host_copy):
         n += ch.n
     return n, nb, time.perf_counter() - t
 
@@ -123,6 +127,28 @@ def inflate_modes(a, F, cs, res, d, pool):
     res["value"] = res["bam_16_threads_%s" % modes[-1]]["median_s"]
 
 
+def walk_modes(a, F, cs, res, d, pool):
+    """--walk / --host-copy: every (inflate, walk, host copy) alternated on the BAM and on the tagged BAM"""
+    modes = [(i, w, h) for i in a.inflate.split(",") for w in a.walk.split(",") for h in a.host_copy.split(",")]
+    n_reads, n_bases = len(F), int(F.n_bases)
+    for key, tags in (("bam_16_threads", False), ("bam_tags_16_threads", True)):
+        path = os.path.join(d, key + ".bam")
+        stream = bam_stream(F, tags)
+        write_bgzf(path, stream, pool)
+        res[key + "_bytes"], res[key + "_inflated_bytes"] = os.path.getsize(path), len(stream)
+        del stream
+        ts = {m: [] for m in modes}
+        for rep in range(a.reps + 1):                               # (the first pass of every mode is the warm-up)
+            for m in modes:
+                n, nb, t = one_pass(path, cs, 16, *m)
+                assert (n, nb) == (n_reads, n_bases), (key, m, n, nb)
+                if rep:
+                    ts[m].append(t)
+        for m in modes:
+            res["%s_%s" % (key, "/".join(m))] = dict(summary(ts[m], n_bases), runs_s=[round(t, 4) for t in ts[m]])
+    res["value"] = res["bam_16_threads_%s" % "/".join(modes[-1])]["median_s"]
+
+
 def summary(ts, n_bases):
     med = statistics.median(ts)
     return {"median_s": round(med, 3), "min_s": round(min(ts), 3), "max_s": round(max(ts), 3), "s_per_gbase": round(med / n_bases * 1e9, 3)}
@@ -136,9 +162,15 @@ def main():
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--only", choices=("bam",), default=None)
     ap.add_argument("--inflate", default=None, help="host, device or host,device: compare FileChunks' inflate modes instead")
+    ap.add_argument("--walk", default=None, help="host, device or host,device: FileChunks' bam_walk modes (with --inflate)")
+    ap.add_argument("--host-copy", default=None, help="all, needed or all,needed: FileChunks' host_copy modes (with --inflate)")
     a = ap.parse_args()
     if a.inflate and not set(a.inflate.split(",")) <= {"host", "device"}:
         ap.error("--inflate takes host, device or host,device")
+    if (a.walk or a.host_copy) and not a.inflate:
+        ap.error("--walk and --host-copy go with --inflate")
+    if (a.walk and not set(a.walk.split(",")) <= {"host", "device"}) or (a.host_copy and not set(a.host_copy.split(",")) <= {"all", "needed"}):
+        ap.error("--walk takes host,device and --host-copy all,needed")
     cfg = dataclasses.replace(synth.CONFIGS["cfg3"], n_reads=a.reads)
     cs = int(a.chunk_mb * 1024 ** 2)
     t0 = time.time()
@@ -149,12 +181,16 @@ def main():
     ok = True
     if a.inflate:
         with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(a.workers) as pool:
-            inflate_modes(a, F, cs, res, d, pool)
+            if a.walk or a.host_copy:
+                a.walk, a.host_copy = a.walk or "host", a.host_copy or "all"
+                walk_modes(a, F, cs, res, d, pool)
+            else:
+                inflate_modes(a, F, cs, res, d, pool)
         res["setup_and_run_s"] = round(time.time() - t0, 1)
         print(json.dumps(res))
         if os.environ.get("OUT"):
             os.makedirs(os.environ["OUT"], exist_ok=True)
-            with open(os.path.join(os.environ["OUT"], "bam_time_inflate.json"), "w") as f:
+            with open(os.path.join(os.environ["OUT"], "bam_time_walk.json" if a.walk else "bam_time_inflate.json"), "w") as f:
                 f.write(json.dumps(res) + "\n")
         return 0
     with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(a.workers) as pool:

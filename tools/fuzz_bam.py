@@ -8,7 +8,11 @@ strategies Z_FIXED, Z_RLE and Z_HUFFMAN_ONLY, and every case is read in host mod
     python tools/fuzz_bam.py [--n 300] [--seed 1] [--inflate device]        (the emulator build: no GPU needed)
 --host-copy needed: the reads of every case also go, as FASTQ text, into a BGZF file of the same block layout -- the text input the
 mode is for -- and FileChunks(inflate="device", parse="device") must give the same chunks, or the same error, with host_copy="needed"
-as with "all" and as the host modes (a BAM file itself ignores the mode: its record walk is the host's)."""
+as with "all" and as the host modes (a BAM file itself ignores the mode while its record walk is the host's).
+--walk device: the BAM's records are found on the device (FileChunks(bam_walk="device"): k_bam_*); every case must give the written
+list, and with --inflate device --host-copy needed the BAM reader itself keeps the inflated bytes on the device (copy_stats: active).
+The text detour of --host-copy needed is left out then: the mode is the BAM reader's own.  The last line reports how many records the device vouched for and how many the host walk took.
+    python tools/fuzz_bam.py --walk device [--inflate device --host-copy needed]"""
 import argparse
 import os
 import random
@@ -28,12 +32,14 @@ def main():
     ap.add_argument("--lib", default=os.environ.get("LQCOV_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liblqcov_emu.so"))
     ap.add_argument("--inflate", choices=("host", "device"), default="host")
     ap.add_argument("--host-copy", choices=("all", "needed"), default="all")
+    ap.add_argument("--walk", choices=("host", "device"), default="host")
     args = ap.parse_args()
     from longqc_amd import api, chunkpass
     from tests import bam_writer as BW
     lib = api.load_library(args.lib)
     rng = random.Random(args.seed)
-    bad = 0
+    bad, on_device, on_host = 0, 0, 0
+    bam_kw = dict(bam_walk="device", host_copy=args.host_copy) if args.walk == "device" else {}
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "f.bam")
         for it in range(args.n):
@@ -83,15 +89,20 @@ def main():
                     want.append((cur, ns, nb)); cur, acc = [], 0
             want.append((cur, ns, nb))
             try:
-                fc = chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads, is_sequel=sequel, inflate=args.inflate)
+                fc = chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads, is_sequel=sequel, inflate=args.inflate, **bam_kw)
                 got = [(ch.records(), a, b) for ch, a, b in fc]
                 ok = got == want and fc.format == 1
+                if args.walk == "device":
+                    ps = fc.parse_stats
+                    on_device += ps["records_device"]; on_host += ps["records_host"]
+                    ok = ok and ps["records_device"] + ps["records_host"] == n and ps["fallbacks"] == 0
+                    ok = ok and fc.copy_stats["active"] == int(args.inflate == "device" and args.host_copy == "needed")
                 if ok and args.inflate == "device":
                     ok = got == [(ch.records(), a, b) for ch, a, b in chunkpass.FileChunks(path, chunk_size=cs, str_overhead=ov, lib=lib, n_threads=threads,
                                                                                          is_sequel=sequel, inflate="host")]
             except api.LqcovError as e:
                 got, ok = repr(e), False
-            if ok and args.host_copy == "needed":
+            if ok and args.host_copy == "needed" and args.walk == "host":      # (--walk device: the BAM reader itself has just honoured the mode)
                 text = b"".join(b"@" + r[0] + b"\n" + r[1] + b"\n+\n" + (b"!" * len(r[1]) if q is None else bytes(x + 33 for x in q)) + b"\n" for r, q in zip(reads, quals))
                 tpath = os.path.join(d, "f.fq.gz")
                 open(tpath, "wb").write(BW.bgzf(text, block_payload=kw["block_payload"], level=min(kw["level"], 6), eof=kw["eof"], empty_block_every=kw["empty_block_every"]))
@@ -110,6 +121,8 @@ def main():
                 print("case %d: %d reads, %s, piece %s, %d threads, chunk_size %d, is_sequel %s: %s" % (
                     it, n, kw if len(kw["header_text"]) < 50 else "...", piece, threads, cs, sequel,
                     got if isinstance(got, str) else [(len(c), a, b) for c, a, b in got]))
+    if args.walk == "device":
+        print("records the device vouched for: %d; records the host walk took: %d" % (on_device, on_host))
     print("%d cases, %d failed" % (args.n, bad))
     return 1 if bad else 0
 
