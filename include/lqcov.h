@@ -127,7 +127,7 @@ const char *lqcov_last_error(const lqcov_handle *h);
 int  lqcov_abi_version(void);
 int  lqcov_set_profiling(lqcov_handle *h, int on);                         /* 0 off; 1 wait for every kernel (exclusive per-kernel times); 2 record events only, no waits */
 int  lqcov_set_profiling_only(lqcov_handle *h, const char *stage);         /* time only the named stage (NULL / "": all) */
-int  lqcov_set_debug(lqcov_handle *h, unsigned flags);                     /* bit0: record chains for lqcov_get_chains */
+int  lqcov_set_debug(lqcov_handle *h, unsigned flags);                     /* bit0: record chains for lqcov_get_chains; bit1: record every anchor sort for lqcov_get_sort_batches */
 int  lqcov_get_stage_times(lqcov_handle *h, lqcov_stage_time *out, int max_out);   /* returns count */
 
 /* Query reads (the subsample): n reads, bases seq[seq_off[i] .. seq_off[i+1]) as ASCII, optional
@@ -285,6 +285,28 @@ int lqcov_accum_set_replayed(lqcov_handle *h, uint32_t query, const uint32_t *co
  * keys), and out[i] = sum of in[0..i-1].  Host arrays in and out. */
 int lqcov_debug_sort_pairs(lqcov_handle *h, uint64_t *keys, uint64_t *vals, uint64_t n, unsigned bits, int key_bytes);
 int lqcov_debug_scan(lqcov_handle *h, const uint32_t *in, uint64_t *out, uint64_t n);
+
+/* Test access to the anchor sort between the seed stage and the chains (lqmap.c:238): sort_batch on anchors handed
+ * in from the host.  xy: n anchors (x, y) as the seed stage would emit them, query after query (q_off: n_q + 1 offsets from 0
+ * to n); on return the sorted anchors.  q_klib[q] = 1: query q goes through klib's passes (more than 64 anchors), 0: it holds no
+ * equal x, or at most 64 anchors.  n_targets, max_len: the geometry of the part the anchors are said to come from -- it decides
+ * which key bytes the passes step over; every anchor must lie inside it (rid < n_targets, position < max_len), n < 2^31,
+ * otherwise LQCOV_E_ARG.  want != NULL: the second pass's pruning, with the sorted keys query << 32 | x >> 32 of the runs that
+ * are wanted (queries numbered 0 .. n_q - 1): only those runs are promised to be there, in klib's order, and the keys x >> 32
+ * of every query still ascend.  With profiling on, lqcov_get_stage_times names the kernels that ran.  (LQCOV_DEBUG_SORT and
+ * lqcov_set_debug's bit 1 switch the pruning off here as they do in a mapping.) */
+int lqcov_debug_sort_anchors(lqcov_handle *h, uint64_t *xy, uint64_t n, const uint64_t *q_off, const uint32_t *q_klib, uint32_t n_q,
+                             uint32_t n_targets, uint32_t max_len, const uint64_t *want, uint32_t n_want);
+/* What the last lqcov_part_map handed to the anchor sort, call by call (lqcov_set_debug bit 1; nothing is kept without it, and
+ * while it is set the second pass sorts its queries whole, without pruning).  info[0] = the number of recorded sorts,
+ * and for sort `index`: info[1] = its kind (0: every seed hit in klib's order -- LQCOV_TIES=klib, or the replay of a saturated
+ * query; 1: first pass, the seed filter's survivors, equal x in any order; 2: second pass), info[2] = its queries n_q.
+ * q, klib (up to q_cap entries): the engine's query numbers (lqcov_query_order) and which of them went through klib's passes;
+ * off (up to q_cap entries of n_q + 1): where every query's anchors start; emitted, sorted (up to a_cap anchors of two words):
+ * the anchors as the seed stage wrote them and as the sort left them.  *n_anchors: the anchors of the sort; pass NULL buffers to
+ * get the sizes.  An index past the last sort sets info[0] alone. */
+int lqcov_get_sort_batches(lqcov_handle *h, uint32_t index, uint32_t info[4], uint32_t *q, uint32_t *klib, uint64_t *off, uint64_t q_cap,
+                           uint64_t *emitted, uint64_t *sorted, uint64_t a_cap, uint64_t *n_anchors);
 
 /* The table text (minimap2-coverage.c:567-605) of rows computed elsewhere: the ranks of a multi-GPU run gather their rows and
  * region pools as they are (lqcov_get_rows / lqcov_get_regions; reg_off / mreg_off rebased onto the concatenated pools) and

@@ -133,6 +133,8 @@ def load_library(path: Optional[str] = None):
         "lqcov_sat_replay": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
         "lqcov_accum_set_replayed": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_uint64]),
         "lqcov_debug_sort_pairs": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint, C.c_int]),
+        "lqcov_debug_sort_anchors": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+        "lqcov_get_sort_batches": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
         "lqcov_debug_scan": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_uint64]),
         "lqcov_part_minimizers_dev": (C.c_int, [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p]),
         "lqcov_part_minimizers_export_dev": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -573,6 +575,38 @@ class Engine:
         v = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint64).copy()
         self._ck(self.lib.lqcov_debug_sort_pairs(self.h, k.ctypes.data, None if v is None else v.ctypes.data, k.shape[0], bits, key_bytes))
         return k, v
+
+    def debug_sort_anchors(self, xy: np.ndarray, q_off: np.ndarray, q_klib: np.ndarray, n_targets: int, max_len: int,
+                           want: Optional[np.ndarray] = None) -> np.ndarray:
+        """tests: the anchor sort (sort_batch) on anchors (n, 2) uint64 emitted query after query -> the sorted anchors.
+        q_klib[q] = 1: the query goes through klib's passes; want: sorted keys query << 32 | x >> 32, the second pass's pruning"""
+        a = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2).copy()
+        off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        kl = np.ascontiguousarray(q_klib, dtype=np.uint32)
+        assert off.shape[0] == kl.shape[0] + 1
+        w = None if want is None else np.ascontiguousarray(want, dtype=np.uint64)
+        self._ck(self.lib.lqcov_debug_sort_anchors(self.h, a.ctypes.data, a.shape[0], off.ctypes.data, kl.ctypes.data, kl.shape[0], n_targets, max_len,
+                                                   None if w is None else w.ctypes.data, 0 if w is None else w.shape[0]))
+        return a
+
+    def sort_batches(self) -> List[dict]:
+        """tests: every anchor sort of the last part_map (needs set_debug(2)) -- dict(kind, q = engine query numbers, klib, off,
+        emitted = (n, 2) uint64, sorted = (n, 2) uint64)"""
+        out = []
+        info = np.zeros(4, dtype=np.uint32)
+        n = C.c_uint64()
+        i = 0
+        while True:
+            self._ck(self.lib.lqcov_get_sort_batches(self.h, i, info.ctypes.data, None, None, None, 0, None, None, 0, C.byref(n)))
+            if i >= int(info[0]):
+                return out
+            nq = int(info[2])
+            q = np.zeros(nq, dtype=np.uint32); kl = np.zeros(nq, dtype=np.uint32); off = np.zeros(nq + 1, dtype=np.uint64)
+            em = np.zeros((n.value, 2), dtype=np.uint64); so = np.zeros((n.value, 2), dtype=np.uint64)
+            self._ck(self.lib.lqcov_get_sort_batches(self.h, i, info.ctypes.data, q.ctypes.data, kl.ctypes.data, off.ctypes.data, nq + 1,
+                                                     em.ctypes.data, so.ctypes.data, n.value, C.byref(n)))
+            out.append(dict(kind=int(info[1]), q=q, klib=kl, off=off, emitted=em, sorted=so))
+            i += 1
 
     def debug_scan(self, counts: np.ndarray) -> np.ndarray:
         """tests: the engine's exclusive scan of u32 counts (u64 sums)"""

@@ -624,6 +624,33 @@ int lqcov_debug_scan(lqcov_handle *h, const uint32_t *in, uint64_t *out, uint64_
 {
 	return guard(h, [&] { h->debug_scan(in, out, n); });
 }
+int lqcov_debug_sort_anchors(lqcov_handle *h, uint64_t *xy, uint64_t n, const uint64_t *q_off, const uint32_t *q_klib, uint32_t n_q,
+                             uint32_t n_targets, uint32_t max_len, const uint64_t *want, uint32_t n_want)
+{
+	return guard(h, [&] { SortGeom g; g.n_targets = n_targets; g.max_len = max_len; h->debug_sort_anchors(xy, n, q_off, q_klib, n_q, g, want, want ? n_want : 0); });
+}
+
+int lqcov_get_sort_batches(lqcov_handle *h, uint32_t index, uint32_t info[4], uint32_t *q, uint32_t *klib, uint64_t *off, uint64_t q_cap,
+                           uint64_t *emitted, uint64_t *sorted, uint64_t a_cap, uint64_t *n_anchors)
+{
+	return guard(h, [&] {
+		if (!(h->debug_flags & 2)) throw std::logic_error("sort recording is off (lqcov_set_debug(h, 2))");
+		std::lock_guard<std::mutex> lk(h->sort_rec_mu);
+		if (info) { info[0] = (uint32_t)h->sort_recs.size(); info[1] = info[2] = info[3] = 0; }
+		if (n_anchors) *n_anchors = 0;
+		if (index >= h->sort_recs.size()) return;
+		const SortBatchRec &r = h->sort_recs[index];
+		const u64 nq = r.q.size(), na = r.sorted.size();
+		if (info) { info[1] = r.kind; info[2] = (uint32_t)nq; }
+		if (n_anchors) *n_anchors = na;
+		for (u64 i = 0; i < nq && i < q_cap; ++i) { if (q) q[i] = r.q[i]; if (klib) klib[i] = r.klib[i]; }
+		if (off) for (u64 i = 0; i <= nq && i < q_cap; ++i) off[i] = r.off[i];
+		static_assert(sizeof(mm128) == 16, "anchor layout");
+		const u64 m = std::min<u64>(na, a_cap);
+		if (emitted && m) memcpy(emitted, r.emitted.data(), m * 16);
+		if (sorted && m) memcpy(sorted, r.sorted.data(), m * 16);
+	});
+}
 
 int lqcov_part_minimizers_dev(lqcov_handle *h, int part, const uint64_t **x_dev, const uint64_t **y_dev, uint64_t *n)
 {

@@ -897,17 +897,27 @@ void lqcov_handle::build_part(Part &pt)
 static u64 dbg_anchor_sum(const mm128 &a) { u64 h = (a.x * 0x9E3779B97F4A7C15ULL) ^ (a.y * 0xD6E8FEB86659FD93ULL); return h ^ (h >> 29); }
 
 // sort_batch with the LQCOV_DEBUG_SORT checks around it; h_off: the batch's per-query anchor offsets (relative, nqb + 1), h_klib: which queries' anchors are in B
-void lqcov_handle::sort_checked(MapLane &L, Part &pt, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA, const std::vector<u64> &h_off, const std::vector<u32> &h_klib)
+// lqcov_set_debug bit 1: the call is kept for lqcov_get_sort_batches -- kind (SortBatchRec), h_q: the engine's numbers of the batch's queries
+void lqcov_handle::sort_checked(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA, const std::vector<u64> &h_off, const std::vector<u32> &h_klib, u32 kind, const u32 *h_q)
 {
 	mm128 *dA = L.A.as<mm128>(), *dB = L.B.as<mm128>();
 	u64 sum_before = 0;
-	if (K.debug_sort) {
+	const bool record = (debug_flags & 2) != 0;
+	SortBatchRec rec;
+	if (K.debug_sort || record) {
 		std::vector<mm128> ha(nA), hb(nA);
 		d2h(ha.data(), dA, nA, L.stream); d2h(hb.data(), dB, nA, L.stream);
 		for (u32 q = 0; q < nqb; ++q)
-			for (u64 i = h_off[q]; i < h_off[q + 1]; ++i) sum_before += dbg_anchor_sum(h_klib[q] ? hb[i] : ha[i]);
+			for (u64 i = h_off[q]; i < h_off[q + 1]; ++i) { if (h_klib[q]) ha[i] = hb[i]; sum_before += dbg_anchor_sum(ha[i]); }
+		if (record) { rec.kind = kind; rec.q.assign(h_q, h_q + nqb); rec.klib = h_klib; rec.off = h_off; rec.emitted.swap(ha); }
 	}
-	sort_batch(L, pt, aqb, qkb, nqb, a_base, nA);           // lqmap.c:238
+	sort_batch(L, g, aqb, qkb, nqb, a_base, nA);            // lqmap.c:238
+	if (record) {
+		rec.sorted.resize(nA);
+		d2h(rec.sorted.data(), dA, nA, L.stream);
+		std::lock_guard<std::mutex> lk(sort_rec_mu);
+		sort_recs.push_back(std::move(rec));
+	}
 	if (K.debug_sort) {
 		std::vector<mm128> ha(nA);
 		d2h(ha.data(), dA, nA, L.stream);
@@ -1155,7 +1165,7 @@ void lqcov_handle::map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, 
 		// (second pass: only the listed runs are chained -- klib's levels drop every bucket without one, k_rs_children)
 		L.prune = tie_mode == 2 && !sink; L.prune_n_want = n_want; L.prune_n_sub = ns;
 		struct PruneGuard { MapLane &L; ~PruneGuard() { L.prune = false; } } prune_guard{L};
-		sort_checked(L, pt, L.sub_off.as<u64>(), L.sub_klib.as<u32>(), ns, 0, nA2, so, sk);
+		sort_checked(L, sort_geom(pt), L.sub_off.as<u64>(), L.sub_klib.as<u32>(), ns, 0, nA2, so, sk, tie_mode == 2 ? 2u : 0u, sq.data());
 		if (lq_timeline) { LQ_HIP_CHECK(hipStreamSynchronize(L.stream)); int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_; lq_tl("lane", lane_id, "  second pass sorted"); }
 		chain_stage(L, pt, L.sub_off.as<u64>(), 0, ns, 0, L.sub_q.as<u32>(), nA2, tie_mode, n_want, ivl_cap, dbg, sink);
 	}
@@ -1212,13 +1222,14 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	if (nA) {
 		const u64 *aqb = (opt ? aqf_off : aq_off).as<u64>() + q0;          // batch view of the per-query anchor offsets
 		const u32 *qkb = opt ? qzero.as<u32>() : qklib.as<u32>() + q0;               // (first pass: nobody goes through klib's passes)
-		std::vector<u64> rel; std::vector<u32> hk;
-		if (K.debug_sort) {
-			rel.resize(nqb + 1); hk.assign(nqb, 0);
+		std::vector<u64> rel; std::vector<u32> hk, hq;
+		if (K.debug_sort || (debug_flags & 2)) {
+			rel.resize(nqb + 1); hk.assign(nqb, 0); hq.resize(nqb);
 			for (u32 i = 0; i <= nqb; ++i) rel[i] = h_off[q0 + i] - a_base;
+			for (u32 i = 0; i < nqb; ++i) hq[i] = q0 + i;
 			if (!opt) d2h(hk.data(), qklib.as<u32>() + q0, nqb, L.stream);
 		}
-		sort_checked(L, pt, aqb, qkb, nqb, a_base, nA, rel, hk);
+		sort_checked(L, sort_geom(pt), aqb, qkb, nqb, a_base, nA, rel, hk, opt ? 1u : 0u, hq.data());
 		if (opt && !L.gate_passed) { L.gate_passed = true; open_gate(); }          // (no walks in the first pass: the next lane may start under this batch's chains)
 		chain_stage(L, pt, aqb, a_base, nqb, q0, nullptr, nA, opt ? 1 : 0, 0, ivl_cap, dbg);
 	}
@@ -1399,21 +1410,27 @@ void lqcov_handle::psort_tail(MapLane &L, int set, hipStream_t s, u64 nA, const 
 //   * the others (their anchors are in B, the originals) go through klib's passes byte by byte as 8-byte records
 //     (kernels_sort.hpp, kernels_rsort.hpp); buckets of a pass that received fewer than two marked anchors leave for the
 //     parallel sort as well (set 1, after the last pass), the others are written to A when they are finished.
-void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA)
+SortGeom lqcov_handle::sort_geom(const Part &pt)
+{
+	SortGeom g; g.n_targets = pt.rs.n;
+	for (u32 v : pt.rs.h_len) g.max_len = std::max(g.max_len, v);
+	return g;
+}
+
+void lqcov_handle::sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA)
 {
 	mm128 *dA = L.A.as<mm128>(), *dB = L.B.as<mm128>();
 	hipStream_t sD = L.stream, sC = L.stream2;
 	if (nA >= 0x7ffffff0ULL) throw std::domain_error("more than 2^31 anchors in one query batch");
 	// varying key bits of this part: x = strand:1 | rid:31 | position:32 (lqmap.c:190-196)
-	u32 max_len = 0;
-	for (u32 v : pt.rs.h_len) max_len = std::max(max_len, v);
+	const u32 max_len = g.max_len, n_targets = g.n_targets;
 	KeyMap km; km.pbits = 1; km.rbits = 0;
 	while (km.pbits < 32 && ((u64)1 << km.pbits) < (u64)max_len) ++km.pbits;
-	while (km.rbits < 31 && ((u64)1 << km.rbits) < (u64)pt.rs.n) ++km.rbits;
+	while (km.rbits < 31 && ((u64)1 << km.rbits) < (u64)n_targets) ++km.rbits;
 	u32 const_levels = 0;                                    // key bytes that are zero in every anchor of this part
 	if (!K.no_level_skip) {
-		if (pt.rs.n <= (1u << 16)) const_levels |= 1u << 6;
-		if (pt.rs.n <= (1u << 8)) const_levels |= 1u << 5;
+		if (n_targets <= (1u << 16)) const_levels |= 1u << 6;
+		if (n_targets <= (1u << 8)) const_levels |= 1u << 5;
 		if (max_len <= (1u << 24)) const_levels |= 1u << 3;
 		if (max_len <= (1u << 16)) const_levels |= 1u << 2;
 		if (max_len <= (1u << 8)) const_levels |= 1u << 1;
@@ -1512,9 +1529,9 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 				hipStream_t sW = L.streamW, sW2 = L.streamW2;
 				// the largest digit of this level decides how many register groups the long walker needs
 				u32 max_digit = 255;
-				if (shift == 48) max_digit = (pt.rs.n ? pt.rs.n - 1 : 0) >> 16;
-				else if (shift == 40 && pt.rs.n <= (1u << 16)) max_digit = (pt.rs.n ? pt.rs.n - 1 : 0) >> 8;
-				else if (shift == 32 && pt.rs.n <= (1u << 8)) max_digit = pt.rs.n ? pt.rs.n - 1 : 0;
+				if (shift == 48) max_digit = (n_targets ? n_targets - 1 : 0) >> 16;
+				else if (shift == 40 && n_targets <= (1u << 16)) max_digit = (n_targets ? n_targets - 1 : 0) >> 8;
+				else if (shift == 32 && n_targets <= (1u << 8)) max_digit = n_targets ? n_targets - 1 : 0;
 				else if (shift == 24) max_digit = (max_len ? max_len - 1 : 0) >> 24;
 				else if (shift == 16 && max_len <= (1u << 24)) max_digit = (max_len ? max_len - 1 : 0) >> 16;
 				else if (shift == 8 && max_len <= (1u << 16)) max_digit = (max_len ? max_len - 1 : 0) >> 8;
@@ -1531,7 +1548,7 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 				// placed, LDS included, only to find its list empty, and a level has up to ten such launches on its critical path.
 				u32 lenc[LQ_WALK_CLASSES];
 				for (int c = 0; c < LQ_WALK_CLASSES; ++c) lenc[c] = hl[LQ_C_LEN0 + c];
-				const u32 max_buckets = shift == 56 ? 2 * (((pt.rs.n ? pt.rs.n - 1 : 0) >> 24) + 1) : max_digit + 1;
+				const u32 max_buckets = shift == 56 ? 2 * (((n_targets ? n_targets - 1 : 0) >> 24) + 1) : max_digit + 1;
 				const bool any_walk = max_buckets > 2 || K.no_level_skip;
 				const bool ck_small = K.reg_walker && max_digit < LQ_CK_B;
 				const bool ck3 = ck_small || K.ckpt3;                             // (round 6: on by default for passes with many buckets too -- their states are found by sub-chains side by side, a 65-160 k walk took 8-21 ms whole)
@@ -1615,7 +1632,7 @@ void lqcov_handle::sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *q
 				StageTimer t(this, sD, "k_rs_children");
 				LQ_LAUNCH(k_rs_children, (u32)std::min<u64>((u64)ns * 4, 1u << 20), LQ_CHILD_THREADS, sD, cur, cnt + cur_slot, R[rb ^ 1], rb ^ 1, dB, dA, L.hist.as<u32>(), L.mhist.as<u32>(), L.begs.as<u32>(),
 				          nxt, cnt + nxt_slot, const_levels, lists(1), km, (int)K.all_klib, cnt + LQ_C_TILES, cnt + LQ_C_LEN0, wcaps,
-			          L.prune && !K.debug_sort ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0});
+			          L.prune && !K.debug_sort && !(debug_flags & 2) ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0});
 				check_launch();
 			}
 			d2h(hl, cnt, LQ_C_N, sD);
@@ -1949,10 +1966,36 @@ void lqcov_handle::swap_plan(SeedPlan &S)
 	surv.swap(S.surv); aqf_off.swap(S.aqf_off);
 }
 
+// one more mapping lane: its streams and events
+void lqcov_handle::add_lane()
+{
+	lanes.emplace_back(new MapLane());
+	LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream));
+	LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream2));
+	{	// Token walks are latency-bound single-lane waves that live for milliseconds: left alone they fill the wave slots and
+		// the LDS of every CU and the bandwidth kernels of the other streams crawl (rocprofv3, configs[2]: k_ps_scatter 66 ms
+		// alone, 1100 ms beside the walkers).  Their stream may only use every fourth CU; 64 CUs x 32 waves are plenty for them.
+		// (Keeping the other streams off those CUs as well was measured in round 3: slower, 2.15 vs 1.85-2.1 s per step.)
+		// (Round 3: a different quarter of the CUs per lane, or 128 / 192 CUs instead of 64: no change, 1.69-1.71 s per step whatever
+		// the mask; no mask at all: 2.03 s.)
+		uint32_t mask[8];
+		for (int i = 0; i < 8; ++i) mask[i] = LQ_WALK_CU_MASK;
+		if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW)); }
+		if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW2, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW2)); }
+	}
+	LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w0, hipEventDisableTiming));
+	LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w1, hipEventDisableTiming));
+	LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w2, hipEventDisableTiming));
+	LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_fork, hipEventDisableTiming));
+	LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_join, hipEventDisableTiming));
+	lanes.back()->prim.stream = lanes.back()->stream;
+}
+
 void lqcov_handle::map_part(Part &pt)
 {
 	if (!pt.built) throw std::logic_error("part not built");
 	finished = false; sat_last_valid = false;
+	{ std::lock_guard<std::mutex> lk(sort_rec_mu); sort_recs.clear(); }
 	const u32 n_q = q.n;
 	const u64 n_qm = q.n_mini;
 	last_n_anchors = 0;
@@ -2000,26 +2043,7 @@ void lqcov_handle::map_part(Part &pt)
 	if (anchor_budget > (1ULL << 31) - 4096) anchor_budget = (1ULL << 31) - 4096;   // (a record names its anchor in 31 bits)
 	if (anchor_budget < 1024) anchor_budget = 1024;
 	while (lanes.size() < (size_t)n_lanes) {
-		lanes.emplace_back(new MapLane());
-		LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream));
-		LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream2));
-		{	// Token walks are latency-bound single-lane waves that live for milliseconds: left alone they fill the wave slots and
-			// the LDS of every CU and the bandwidth kernels of the other streams crawl (rocprofv3, configs[2]: k_ps_scatter 66 ms
-			// alone, 1100 ms beside the walkers).  Their stream may only use every fourth CU; 64 CUs x 32 waves are plenty for them.
-			// (Keeping the other streams off those CUs as well was measured in round 3: slower, 2.15 vs 1.85-2.1 s per step.)
-			// (Round 3: a different quarter of the CUs per lane, or 128 / 192 CUs instead of 64: no change, 1.69-1.71 s per step whatever
-			// the mask; no mask at all: 2.03 s.)
-			uint32_t mask[8];
-			for (int i = 0; i < 8; ++i) mask[i] = LQ_WALK_CU_MASK;
-			if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW)); }
-			if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW2, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW2)); }
-		}
-		LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w0, hipEventDisableTiming));
-		LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w1, hipEventDisableTiming));
-		LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_w2, hipEventDisableTiming));
-		LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_fork, hipEventDisableTiming));
-		LQ_HIP_CHECK(hipEventCreateWithFlags(&lanes.back()->ev_join, hipEventDisableTiming));
-		lanes.back()->prim.stream = lanes.back()->stream;
+		add_lane();
 	}
 	{	// every lane's work space (prim.hpp, LqArena): as much as its largest batch of this part can need, taken while the device is
 		// idle -- from the stream-ordered pool (one block, handed back only when the lanes go: plain hipMalloc of tens of gigabytes
@@ -2775,4 +2799,50 @@ void lqcov_handle::debug_scan(const u32 *in, u64 *out, u64 n)
 	prim.exclusive_scan_u32_u64(di.as<u32>(), dout.as<u64>(), n);
 	d2h(out, dout.as<u64>(), n, stream);
 	LQ_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// ---- tests: the anchor sort on anchors from the host (lqcov_debug_sort_anchors) -------------------------------------------------------
+// Lane 0 as map_subset leaves it in front of sort_batch: the anchors of the queries with q_klib in B, the others in A, the offsets
+// and flags on the device, and -- with `want` -- the second pass's pruning switched on with the queries numbered 0 .. n_q - 1.  No
+// kernel of its own: what runs is sort_batch.
+void lqcov_handle::debug_sort_anchors(u64 *xy, u64 n, const u64 *q_off, const u32 *q_klib, u32 n_q, SortGeom g, const u64 *want, u32 n_want)
+{
+	if (n >= (1ULL << 31)) throw std::invalid_argument("2^31 anchors or more in one batch");
+	if (!q_off || (n_q && !q_klib) || (n && !xy) || (n_want && !want)) throw std::invalid_argument("null buffers");
+	if (q_off[0] != 0 || q_off[n_q] != n) throw std::invalid_argument("the query offsets do not span the anchors");
+	for (u32 q = 0; q < n_q; ++q) {
+		if (q_off[q + 1] < q_off[q] || q_off[q + 1] > n) throw std::invalid_argument("the query offsets descend");
+		if (q_klib[q] > 1 || (q_klib[q] && q_off[q + 1] - q_off[q] <= LQ_RS_MIN)) throw std::invalid_argument("a query of 64 anchors or fewer does not go through klib's passes");
+	}
+	// (the parallel sort rebuilds x from the compact key: an anchor outside the geometry would come back changed)
+	for (u64 i = 0; i < n; ++i) {
+		const u64 x = xy[2 * i];
+		if (((x >> 32) & 0x7fffffffu) >= g.n_targets || (u32)x >= g.max_len) throw std::invalid_argument("an anchor outside the stated geometry (rid >= n_targets or position >= max_len)");
+	}
+	for (u32 i = 1; i < n_want; ++i) if (want[i] <= want[i - 1]) throw std::invalid_argument("the wanted keys are not sorted");
+	for (u32 i = 0; i < n_want; ++i) if ((want[i] >> 32) >= n_q) throw std::invalid_argument("a wanted key of no query");
+	if (!n) return;
+	if (lanes.empty()) add_lane();
+	MapLane &L = *lanes[0];
+	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+	L.drop_arena_buffers();
+	batch_buffers(L, n);
+	std::vector<mm128> ha(n), hb(n);
+	memset(ha.data(), 0, n * sizeof(mm128)); memset(hb.data(), 0, n * sizeof(mm128));
+	for (u32 q = 0; q < n_q; ++q)
+		for (u64 i = q_off[q]; i < q_off[q + 1]; ++i) { mm128 &e = q_klib[q] ? hb[i] : ha[i]; e.x = xy[2 * i]; e.y = xy[2 * i + 1]; }
+	std::vector<u32> ident(n_q);
+	for (u32 q = 0; q < n_q; ++q) ident[q] = q;
+	L.sub_q.ensure(n_q * 4 + 4); L.sub_off.ensure(((u64)n_q + 1) * 8); L.sub_klib.ensure(n_q * 4 + 4); L.want.ensure(((u64)n_want + 1) * 8);
+	h2d(L.A.as<mm128>(), ha.data(), n, L.stream); h2d(L.B.as<mm128>(), hb.data(), n, L.stream);
+	h2d(L.sub_q.as<u32>(), ident.data(), n_q, L.stream); h2d(L.sub_off.as<u64>(), q_off, (size_t)n_q + 1, L.stream); h2d(L.sub_klib.as<u32>(), q_klib, n_q, L.stream);
+	h2d(L.want.as<u64>(), want, n_want, L.stream);
+	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+	L.gate_passed = true;                                   // (no other lane waits for this one)
+	L.prune = want != nullptr; L.prune_n_want = n_want; L.prune_n_sub = n_q;
+	struct PruneGuard { MapLane &L; ~PruneGuard() { L.prune = false; } } prune_guard{L};
+	sort_batch(L, g, L.sub_off.as<u64>(), L.sub_klib.as<u32>(), n_q, 0, n);
+	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+	d2h(ha.data(), L.A.as<mm128>(), n, L.stream);
+	for (u64 i = 0; i < n; ++i) { xy[2 * i] = ha[i].x; xy[2 * i + 1] = ha[i].y; }
 }

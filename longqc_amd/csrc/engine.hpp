@@ -143,6 +143,19 @@ struct PsWork {                           // one set of psort lists + the scratc
 	DBuf big[2], fin_s, fin_b, plan, gcnt, gcur, gdiff, tmap;
 };
 
+// What the anchor sort needs to know of a part: how many targets it holds and how long the longest one is (the key bits that vary,
+// the levels that are identity passes: sort_batch).  From the part's reads (lqcov_handle::sort_geom) or stated by a test
+// (lqcov_debug_sort_anchors).
+struct SortGeom { u32 n_targets = 0, max_len = 0; };
+
+// One call of sort_checked as lqcov_set_debug's bit 1 records it (lqcov_get_sort_batches)
+struct SortBatchRec {
+	u32 kind = 0;                         // 0: every hit, klib's order (LQCOV_TIES=klib; the replay of a saturated query), 1: first pass, 2: second pass
+	std::vector<u32> q, klib;             // the engine's query numbers; which of them went through klib's passes
+	std::vector<u64> off;                 // per-query anchor offsets (q.size() + 1)
+	std::vector<mm128> emitted, sorted;
+};
+
 struct MapLane {
 	hipStream_t stream = nullptr;         // klib's passes (queries with repeated minimizers), then runs and chains
 	hipStream_t stream2 = nullptr;        // the parallel sort of every other query, meanwhile
@@ -196,7 +209,8 @@ struct lqcov_handle {
 	void add_stage_bytes(const char *name, u64 bytes);       // algorithmic bytes known only after the fact (device-side tallies)
 	std::map<std::string, u64> late_bytes;
 	void drain_stages();
-	u32 debug_flags = 0;
+	u32 debug_flags = 0;                  // lqcov_set_debug: bit 0 records chains, bit 1 what every sort was handed and what it made of it
+	std::vector<SortBatchRec> sort_recs; std::mutex sort_rec_mu;   // bit 1: the sorts of the last map_part
 	bool distributed = false;             // per-part accumulators, COVT replayed by the caller (multi-GPU)
 	std::map<std::string, StageAcc> stages;
 	std::vector<std::string> stage_order;
@@ -297,13 +311,16 @@ struct lqcov_handle {
 	void map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, const std::vector<u32> &sk, const std::vector<u64> &so, u64 max_mini, int tie_mode, u32 n_want, u32 ivl_cap, bool dbg, const SatSink *sink);
 	void debug_sort_pairs(u64 *keys, u64 *vals, u64 n, unsigned bits, int key_bytes);   // tests: the primitives of kernels_isort.hpp on host arrays
 	void debug_scan(const u32 *in, u64 *out, u64 n);
+	void debug_sort_anchors(u64 *xy, u64 n, const u64 *q_off, const u32 *q_klib, u32 n_q, SortGeom g, const u64 *want, u32 n_want);   // tests: sort_batch on anchors from the host
+	void add_lane();
+	static SortGeom sort_geom(const Part &pt);
 	bool sat_chains(Part &pt, u32 qi, const std::vector<u64> &h_aq, const std::vector<u64> &h_qmoff, std::vector<SatRec> &recs, std::vector<u32> &at);
 	void sat_check(const std::vector<SatRec> &recs, const std::vector<u32> &at, size_t nc);
 	void part_sat_records(Part &pt, u32 qi, std::vector<SatRec> &recs, std::vector<u32> &at);
 	void sat_replay_host(u32 qi, const SatRec *recs, u64 n_recs, const u32 *at, u64 n_at, u32 *counters, u64 n_counters);
 	void sat_replay_part(Part &pt, const std::vector<u64> &h_aq, const std::vector<u64> &h_qmoff);
-	void sort_checked(MapLane &L, Part &pt, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA, const std::vector<u64> &h_off, const std::vector<u32> &h_klib);
-	void sort_batch(MapLane &L, Part &pt, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA);
+	void sort_checked(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA, const std::vector<u64> &h_off, const std::vector<u32> &h_klib, u32 kind, const u32 *h_q);
+	void sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA);
 	void psort_run(MapLane &L, int set, hipStream_t s, u64 nA, const KeyMap &km, const struct PsData &pd);
 	void psort_tail(MapLane &L, int set, hipStream_t s, u64 nA, const KeyMap &km, const struct PsData &pd);
 	void reset();

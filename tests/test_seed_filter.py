@@ -61,7 +61,7 @@ import numpy as np
 import pytest
 
 from longqc_amd import api
-from tests.helpers import seed_filter_dataset, seed_filter_long_pair
+from tests.helpers import all_hits, seed_filter_dataset, seed_filter_long_pair
 
 K, W = 9, 4
 MAX_GAP = 10000
@@ -86,38 +86,6 @@ def dshift_of(bw):
     while (1 << s) <= max(bw, 0):
         s += 1
     return s
-
-
-def all_hits(qxy, qoff, txy, qlen, qnames, tnames, mid_occ):
-    """every occurrence in the part of every query minimizer whose list is shorter than mid_occ (lqmap.c:166-173), as columns:
-    q (caller's order), rid, rs, diag, jl, y (query coordinate, lqmap.c:190-197), r (target position), drop_self (the self
-    diagonal of -Y) and drop_ava (with -X: the targets named below the query), both lqmap.c:180-187"""
-    qxy = qxy.astype(np.uint64); txy = txy.astype(np.uint64)
-    qoff = qoff.astype(np.int64)
-    tkey, ty = txy[:, 0] >> np.uint64(8), txy[:, 1]
-    order = np.lexsort((ty, tkey))
-    tkey, ty = tkey[order], ty[order]
-    qkey = qxy[:, 0] >> np.uint64(8)
-    lo, hi = np.searchsorted(tkey, qkey, "left"), np.searchsorted(tkey, qkey, "right")
-    n = hi - lo
-    n = np.where(n < mid_occ, n, 0)
-    j = np.repeat(np.arange(qkey.shape[0], dtype=np.int64), n)                        # the hit's query minimizer
-    at = lo[j] + (np.arange(j.shape[0], dtype=np.int64) - np.repeat(np.cumsum(n) - n, n))
-    occ = ty[at]
-    q = np.searchsorted(qoff, j, "right") - 1
-    rid = (occ >> np.uint64(32)).astype(np.int64)
-    rpos = ((occ & np.uint64(0xffffffff)) >> np.uint64(1)).astype(np.int64)
-    qy = qxy[j, 1]
-    qpos = ((qy & np.uint64(0xffffffff)) >> np.uint64(1)).astype(np.int64)
-    span = (qxy[j, 0] & np.uint64(0xff)).astype(np.int64)
-    rs = ((occ ^ qy) & np.uint64(1)).astype(np.int64)
-    ql = np.asarray(qlen, dtype=np.int64)[q]
-    y = np.where(rs == 1, ql - (qpos + 1 - span) - 1, qpos)
-    diag = rpos - y + ql + 256
-    same = np.array([[qn == tn for tn in tnames] for qn in qnames])
-    below = np.array([[tn.encode() < qn.encode() for tn in tnames] for qn in qnames])
-    return dict(q=q, rid=rid, rs=rs, diag=diag, jl=j - qoff[q], y=y.astype(np.int32), r=rpos.astype(np.int32),
-                drop_self=same[q, rid] & (rpos == qpos), drop_ava=below[q, rid])
 
 
 def _group(*cols):
