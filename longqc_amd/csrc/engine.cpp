@@ -1978,6 +1978,12 @@ void lqcov_handle::add_lane()
 		// (Keeping the other streams off those CUs as well was measured in round 3: slower, 2.15 vs 1.85-2.1 s per step.)
 		// (Round 3: a different quarter of the CUs per lane, or 128 / 192 CUs instead of 64: no change, 1.69-1.71 s per step whatever
 		// the mask; no mask at all: 2.03 s.)
+		// (The checkpoint solvers, k_ck_*, are whole-wave kernels and sit on these streams only because their walkers do.  Measured
+		// with the walks checkpointed, configs[2]: launched on the lane's own, unmasked stream behind an event of their own, their
+		// kernel times per step hardly move -- k_ck_chain256 51.5 -> 46.8 ms, k_ck_solve 27.2 -> 25.6, k_ck_phases 11.0 -> 10.2,
+		// k_ck_tilehist 4.7 -> 2.0: what a launch takes is its longest sub-chain, not the CUs it may use -- and the step gains 4-7 ms
+		// where three runs of one library differ by 5-7: not told from the spread, not kept.  On the lane's second stream: 362-374
+		// against 342-347 ms per step.)
 		uint32_t mask[8];
 		for (int i = 0; i < 8; ++i) mask[i] = LQ_WALK_CU_MASK;
 		if (hipExtStreamCreateWithCUMask(&lanes.back()->streamW, 8, mask) != hipSuccess) { (void)hipGetLastError(); LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->streamW)); }
@@ -2211,7 +2217,7 @@ void lqcov_handle::finish()
 	}
 	{
 		StageTimer t(this, "k_cnt_stats", q.n_mini * 8);
-		LQ_LAUNCH(k_cnt_stats, nblk(n_q, 64), 64, stream, cnts.as<u32>(), cnt_off_dev(), own_cnt_layout ? d_nsize.as<u32>() : (const u32*)nullptr, n_q, rowdev.as<RowDev>(), qflags.as<u32>(), cnt_max);
+		LQ_LAUNCH(k_cnt_stats, nblk(n_q, LQ_CNT_STATS_THREADS / 64), LQ_CNT_STATS_THREADS, stream, cnts.as<u32>(), cnt_off_dev(), own_cnt_layout ? d_nsize.as<u32>() : (const u32*)nullptr, n_q, rowdev.as<RowDev>(), qflags.as<u32>(), cnt_max);
 		check_launch();
 	}
 	std::vector<RowDev> hr(n_q);

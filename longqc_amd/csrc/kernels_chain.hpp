@@ -1252,24 +1252,31 @@ __global__ void k_reliable(const u64 *se, const u32 *pvq_off, u32 n_q, u32 min_c
 	rows[q].reg_off = ro; rows[q].n_reg = nr; rows[q].mreg_off = mo; rows[q].n_mreg = nm;
 }
 
-// minimap2-coverage.c:552-561: integer mean of the uint16 counters, count of those above it
-__global__ void k_cnt_stats(const u32 *cnts, const u64 *cnt_off, const u32 *nsize, u32 n_q, RowDev *rows, u32 *qflags, u32 cnt_max)
+// minimap2-coverage.c:552-561: integer mean of the uint16 counters, count of those above it.  One wave per query, its lanes
+// striding over the query's counters (a thread per query read ~3 400 counters twice, one by one: 22 GB/s); the partial sums are
+// added by shuffles -- u32 addition wraps, so their order does not matter and `sum` is the reference's to the bit.  The second
+// sweep finds the counters in the caches.  Lane 0 writes the row and the flags.
+#define LQ_CNT_STATS_THREADS 256
+__global__ void __launch_bounds__(LQ_CNT_STATS_THREADS)
+k_cnt_stats(const u32 *cnts, const u64 *cnt_off, const u32 *nsize, u32 n_q, RowDev *rows, u32 *qflags, u32 cnt_max)
 {
-	u32 q = blockIdx.x * blockDim.x + threadIdx.x;
-	if (q >= n_q) return;
-	const u64 lo = cnt_off[q], hi = nsize ? lo + nsize[q] : cnt_off[q + 1];   // mv.n counters (minimap2-coverage.c:552-561)
-	u32 sum = 0, n = (u32)(hi - lo), nm = 0;
-	bool sat = false;
-	for (u64 j = lo; j < hi; ++j) { sum += cnts[j] & cnt_max; if (cnts[j] >= cnt_max) sat = true; }   // uint16 storage wraps (esterr.c:136); a flagged query's counters are the replayed ones by now
-	if (sat) atomicOr(&qflags[q], 1u);
-	if (nsize) {                                            // counters the reference never allocated (see adopt_index_params)
-		bool over = false;
-		for (u64 j = hi; j < cnt_off[q + 1]; ++j) if (cnts[j]) over = true;
-		if (over) atomicOr(&qflags[q], 2u);
-	}
+	const u32 lane = threadIdx.x & 63;
+	const u32 q = blockIdx.x * (LQ_CNT_STATS_THREADS / 64) + (threadIdx.x >> 6);
+	if (q >= n_q) return;                                   // (the whole wave)
+	const u64 lo = cnt_off[q], end = cnt_off[q + 1], hi = nsize ? lo + nsize[q] : end;   // mv.n counters (minimap2-coverage.c:552-561)
+	u32 sum = 0, n = (u32)(hi - lo), nm = 0, fl = 0;
+	for (u64 j = lo + lane; j < hi; j += 64) { const u32 v = cnts[j]; sum += v & cnt_max; if (v >= cnt_max) fl |= 1u; }   // uint16 storage wraps (esterr.c:136); a flagged query's counters are the replayed ones by now
+	if (nsize)                                              // counters the reference never allocated (see adopt_index_params)
+		for (u64 j = hi + lane; j < end; j += 64) if (cnts[j]) fl |= 2u;
+	for (int d = 32; d; d >>= 1) { sum += __shfl_xor(sum, d); fl |= __shfl_xor(fl, d); }
 	if (n) sum /= n;
-	for (u64 j = lo; j < hi; ++j) if ((cnts[j] & cnt_max) > sum) ++nm;
-	rows[q].n_match = nm;
+	for (u64 j = lo + lane; j < hi; j += 64) if ((cnts[j] & cnt_max) > sum) ++nm;
+	for (int d = 32; d; d >>= 1) nm += __shfl_xor(nm, d);
+	if (lane == 0) {
+		if (fl & 1u) atomicOr(&qflags[q], 1u);
+		if (fl & 2u) atomicOr(&qflags[q], 2u);
+		rows[q].n_match = nm;
+	}
 }
 
 // meanQ's accumulation (lqutils.c:51-56): a sequential double sum per read, in read order

@@ -34,7 +34,8 @@
 #define LQ_CK_B 16                 // buckets a checkpointed pass may have (digits 0..15)
 #define LQ_CK_TILE 1024            // elements per prefix-count tile
 // elements per checkpoint, passes of up to LQ_CK_B / up to 256 buckets (configs[2], ms per step: 16384 / 4096: 502, 65536 / 4096: 502,
-// 65536 / 8192: 491, 65536 / 16384: 491, 131072 / 8192: 494)
+// 65536 / 8192: 491, 65536 / 16384: 491, 131072 / 8192: 494; with the solvers on an unmasked stream, three alternating runs each: 65536 / 8192:
+// 335-345, 32768 / 8192: 336-339, 65536 / 4096: 342-353)
 #define LQ_CK_UNIT 65536
 #define LQ_CK_UNIT_MANY 8192
 
