@@ -415,6 +415,39 @@ int lqchunk_sdust(lqchunk *c, int W, int T, uint32_t *masked, double *qual_psum,
  * second call; every lqchunk_sdust_split call classifies and scans anew. */
 int lqchunk_sdust_split(lqchunk *c, int W, int T, uint32_t piece, uint32_t *masked, double *qual_psum, uint32_t *n_above_q7, uint32_t *n_serial);
 int lqchunk_sdust_intervals(lqchunk *c, int W, int T, uint32_t piece, uint64_t *n_off, uint8_t *flagged, uint64_t *iv, size_t iv_cap, size_t *iv_need);
+/* The table as text, made on the device (opt-in; k_sdust_rows, k_sdust_patch, k_sdust_text): per read the row `sdust` prints,
+ * name \t masked \t len \t %.3f of masked/len \t %.3f of meanQ \t q7 \n (sdust.c:211-217), byte for byte, one behind the other.
+ * lqchunk_sdust and lqchunk_sdust_split take NULL for all three host arrays: the results then stay on the device.
+ * lqchunk_sdust_table formats the results the chunk's last lqchunk_sdust / lqchunk_sdust_split left there: names / name_off as
+ * lqstore_append takes them (NULL: empty names); out gets the text, out_cap is its room -- the sum of the names' lengths + 48 bytes per
+ * read always suffices -- *out_len the text's length; stats (may be NULL) the table's summary; excl (may be NULL, else room for excl_cap
+ * indices): the reads on LongQC's two exclusion lists (longQC.py:370-371, by the printed fraction: len > 500000 and more than 0.200, then
+ * len > 10000 and more than 0.400), the first list's stats->excluded_first indices ascending, then the second's.
+ * LQCOV_E_STATE: no chunk loaded, or no scan since the chunk was loaded; LQCOV_E_ARG: out_cap or excl_cap too small -- nothing is written
+ * but *out_len and stats, and the next call works.
+ * lqsdust_format is the same from arrays on the host: row i has masked[i], len[i], qual_psum[i], n_above_q7[i] and qualities if len[i] > 0
+ * and has_q[i] != 0 (has_q NULL: no row has).  window: a row's meanQ is the device's unless |frac(|z| * 1000) - 0.5| < window * max(|z| *
+ * 1000, 1), where the host takes it with libm; 0: the default, 2^-30; 1: every row with qualities.  stats->unvouched counts them.
+ * lqsdust_format_lists is lqsdust_format with lqchunk_sdust_table's excl / excl_cap: the rows on the two exclusion lists. */
+#define LQSDUST_STATS_WORDS 8
+typedef struct lqsdust_stats {
+	uint64_t rows, bytes;                /* rows and bytes of the text */
+	uint64_t masked, q7;                 /* the sums of the two integer columns */
+	uint64_t unvouched;                  /* rows whose meanQ the host took */
+	uint64_t excluded, excluded_first;   /* entries of both exclusion lists, and of the first */
+	uint64_t reserved;
+} lqsdust_stats;
+int lqchunk_sdust_table(lqchunk *c, const char *names, const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                        lqsdust_stats *stats, uint32_t *excl, uint64_t excl_cap);
+int lqsdust_format(int device, uint32_t n, const char *names, const uint64_t *name_off, const uint32_t *masked, const uint32_t *len,
+                   const double *qual_psum, const uint8_t *has_q, const uint32_t *n_above_q7, double window, uint8_t *out, uint64_t out_cap,
+                   uint64_t *out_len, lqsdust_stats *stats, char *errbuf, size_t errbuf_len);
+int lqsdust_format_lists(int device, uint32_t n, const char *names, const uint64_t *name_off, const uint32_t *masked, const uint32_t *len,
+                         const double *qual_psum, const uint8_t *has_q, const uint32_t *n_above_q7, double window, uint8_t *out, uint64_t out_cap,
+                         uint64_t *out_len, lqsdust_stats *stats, uint32_t *excl, uint64_t excl_cap, char *errbuf, size_t errbuf_len);
+/* printf's "%.3f" as the table's kernels and the host take it (lq_fmt3.hpp): -> the class (0 finite, 1 nan, 2 inf, 3 2^50 or more; + 4:
+ * the sign bit), *thousandths: |x| rounded to 1/1000 exactly, ties to even.  No device needed. */
+uint32_t lqsdust_fmt3(double x, uint64_t *thousandths);
 int lqchunk_adapt(lqchunk *c, const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
                   uint32_t length, int32_t *out5, int32_t *out3);
 int lqchunk_gc(lqchunk *c, uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,

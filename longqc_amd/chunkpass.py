@@ -32,6 +32,7 @@ def _lib(lib=None):
             "lqchunk_load": (C.c_int, [H, C.c_uint32, P, P, P]),
             "lqchunk_sdust": (C.c_int, [H, C.c_int, C.c_int, P, P, P]),
             "lqchunk_sdust_split": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, P]),
+            "lqchunk_sdust_table": (C.c_int, [H, C.c_char_p, P, P, C.c_uint64, P, P, P, C.c_uint64]),
             "lqchunk_sdust_intervals": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, C.c_size_t, P]),
             "lqchunk_adapt": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32, P, P]),
             "lqchunk_gc": (C.c_int, [H, C.c_uint32, P, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
@@ -314,6 +315,21 @@ class ReadChunk:
                 raise ValueError("a quality string differs in length from its read")
         self._ck(self.lib.lqchunk_load(self.h, n, self.flat if len(self.flat) else None, self.off.ctypes.data, self.qflat))
 
+    def load_arrays(self, names, seq, off, qual=None):
+        """load() for reads that are arrays already: seq (uint8) holds read i's bases at [off[i], off[i + 1]) (off: n + 1 offsets from 0),
+        qual (uint8, as long as seq; None: no qualities) its qualities, a zero byte first for a read without.  No record becomes a string"""
+        n = len(names)
+        seq, off = np.ascontiguousarray(seq, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint64)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8) if qual is not None else None
+        if off.shape != (n + 1,) or int(off[0]) != 0 or (n and (np.diff(off.astype(np.int64)) < 0).any()) or seq.shape != (int(off[n]),):
+            raise ValueError("off holds n + 1 ascending offsets from 0 to the bases' number")
+        if qual is not None and qual.shape != seq.shape:
+            raise ValueError("a quality string differs in length from its read")
+        self.n, self.names, self.off, self.lens = n, list(names), off, np.diff(off.astype(np.int64))
+        self.packed, self.from_file, self._name_blob = False, False, None
+        self.flat, self.qflat = seq, qual
+        self._ck(self.lib.lqchunk_load(self.h, n, seq.ctypes.data if seq.size else None, off.ctypes.data, qual.ctypes.data if qual is not None and qual.size else None))
+
     def __len__(self):
         return self.n
 
@@ -417,6 +433,30 @@ class ReadChunk:
         else:
             self._ck(self.lib.lqchunk_sdust(self.h, w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data))
         return masked, psum, qv
+
+    def sdust_table(self, w: int = 64, t: int = 20, split: Optional[str] = None, piece: Optional[int] = None):
+        """The chunk's low-complexity table as text, made on the device: the scan (lqchunk_sdust, or lqchunk_sdust_split with split
+        "pieces") leaves its arrays there, lqchunk_sdust_table formats them (k_sdust_rows, k_sdust_text).  -> (bytes: the rows sdust._rows
+        gives, each with its newline; stats: a dict of sdust.TABLE_STATS and exclude_first / exclude_second, the ascending indices of the
+        reads on LongQC's two exclusion lists)"""
+        if split_mode(split) == "pieces":
+            ns = C.c_uint32()
+            self._ck(self.lib.lqchunk_sdust_split(self.h, w, t, _piece(piece), None, None, None, C.byref(ns)))
+            self.n_serial = ns.value
+        else:
+            self._ck(self.lib.lqchunk_sdust(self.h, w, t, None, None, None))
+        return self.sdust_table_bytes()
+
+    def sdust_table_bytes(self, out_cap: Optional[int] = None):
+        """sdust_table's second half: the table of the last scan (lqchunk_sdust_table).  out_cap: room for the text, default what always
+        suffices"""
+        n = self.n
+        nb, noff = self.names_c()
+        cap = int((np.diff(noff).astype(np.int64) - 1).sum()) + sdust.ROW_FIELDS_MAX * n if out_cap is None else int(out_cap)
+        out, n_out, st = np.empty(max(cap, 1), np.uint8), C.c_uint64(), (C.c_uint64 * len(sdust.TABLE_STATS))()
+        excl = np.zeros(max(2 * n, 1), np.uint32)
+        self._ck(self.lib.lqchunk_sdust_table(self.h, nb, noff.ctypes.data, out.ctypes.data, cap, C.byref(n_out), st, excl.ctypes.data, 2 * n))
+        return out[:n_out.value].tobytes(), sdust.with_lists(sdust.stats_dict(st), excl)
 
     def sdust_intervals(self, w: int = 64, t: int = 20, piece: Optional[int] = None):
         """The masked intervals of the reads the pieces serve, what the reference's sdust() returns for them: lqchunk_sdust_intervals.
@@ -647,12 +687,12 @@ class SampleQCPass:
 
     def __init__(self, work_dir: str, preset: str, adp5=None, adp3=None, nsample=5000, gc_draw: str = "device", device: int = 0,
                  fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None,
-                 sdust_split: Optional[str] = None):
+                 sdust_split: Optional[str] = None, sdust_table: Optional[str] = None):
         if preset not in sampleqc.PRESET_MED_SCORE:
             raise ValueError("unknown preset %r" % preset)
         self.preset, self.fast, self.inds, self.device, self.lib = preset, fast, inds, device, lib
         self.adp5, self.adp3, self.nsample = adp5, adp3, nsample
-        self.mask = sdust.LqMaskMI355X(work_dir, suffix, device=device, lib=lib, split=sdust_split)     # sdust_split: split_mode's
+        self.mask = sdust.LqMaskMI355X(work_dir, suffix, device=device, lib=lib, split=sdust_split, table=sdust_table)     # split_mode's, table_mode's
         self.adapters = adapter.AdapterStats(adp5, adp3)
         self.gc = gcfrac.LqGCMI355X(chunk_size=150, draw=gc_draw, seed=gc_seed, device=device, lib=lib)
         self.store = PackedStore(device, lib)
@@ -697,17 +737,21 @@ class SampleQCPass:
 
     def run_file(self, path: str, chunk_size=0.5 * 1024 ** 3, trim=False, is_upper: bool = True, str_overhead: Optional[int] = None,
                  is_sequel: bool = True, inflate: Optional[str] = None, fastx_out=None, parse: Optional[str] = None,
-                 host_copy: Optional[str] = None, sdust_split: Optional[str] = None, bam_walk: Optional[str] = None):
+                 host_copy: Optional[str] = None, sdust_split: Optional[str] = None, bam_walk: Optional[str] = None,
+                 sdust_table: Optional[str] = None):
         """the whole loop of longQC.py:299-360 over a plain or gzip FASTA/FASTQ file or an unaligned BAM (is_sequel, inflate, parse,
         host_copy, bam_walk: FileChunks'): FileChunks + add_resident.  -> the per-chunk adapter results; with trim=True `trimmed_chunks` holds every chunk's
         trimmed records (longQC.py:330-338 writes them out).  trim=<path> (str or os.PathLike): every chunk's trimmed reads are
         appended to that file from the device (a FastqWriter; the file write_fastq(path, trimmed, is_chunk=True) per chunk makes),
         `trimmed` stays None and `trimmed_chunks` empty.  fastx_out=<path>: every chunk is appended to that file untrimmed -- the
         FASTQ that longQC.py:302-303 converts a BAM file to, for any input.  Both files are complete, and their errors raised, when
-        the call returns.  sdust_split: split_mode's, for this file (None: what the constructor was given); the table is the same."""
-        mask_split = self.mask.split
+        the call returns.  sdust_split: split_mode's, for this file (None: what the constructor was given); the table is the same.
+        sdust_table: sdust.table_mode's, for this file in the same way ("device": the rows are formatted on the device)."""
+        mask_split, mask_table = self.mask.split, self.mask.table
         if sdust_split is not None:
             self.mask.split = split_mode(sdust_split)
+        if sdust_table is not None:
+            self.mask.table = sdust.table_mode(sdust_table)
         results, self.trimmed_chunks = [], []
         to_file = isinstance(trim, (str, os.PathLike))
         if to_file and not (self.adp5 or self.adp3):
@@ -731,7 +775,7 @@ class SampleQCPass:
             _close_writers(writers, quiet=True)                    # (the loop's error is the one to report)
             raise
         finally:
-            self.mask.split = mask_split                           # (sdust_split held for this file)
+            self.mask.split, self.mask.table = mask_split, mask_table      # (sdust_split and sdust_table held for this file)
         _close_writers(writers)
         return results
 
@@ -771,6 +815,10 @@ class SampleQCPass:
             return [eng.table_text()] if len(sets) == 1 else [eng.table_text(set=k) for k in range(len(sets))]
         finally:
             eng.close()
+
+    def summary(self):
+        """the mask's summary (LqMaskMI355X.summary): what longQC.py:369-371, 452-471 read back from the table"""
+        return self.mask.summary()
 
     def close(self):
         self.store.close()

@@ -23,7 +23,7 @@ void lq_chunk_set(lqchunk &c, u32 n, const u8 *seq, const u64 *seq_off, const u8
 	c.h_seq = seq ? seq + seq_off[0] : nullptr;
 	c.h_qual = qual ? qual + seq_off[0] : nullptr;
 	c.has_qual = qual != nullptr;
-	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false;
 }
 
 void lq_chunk_ready(lqchunk &c)
@@ -101,7 +101,7 @@ static void gather_begin(lqchunk &c, const std::vector<u64> &off)
 	lq_cabi::select_device(c.device);
 	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
 	const u32 n = (u32)(off.size() - 1);
-	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false;
 	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
 	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
 	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
@@ -142,6 +142,9 @@ template <class F> int chunk_guard(lqchunk *c, F &&f)
 }
 
 void need_loaded(const lqchunk &c) { if (!c.resident) throw std::logic_error("no chunk loaded (lqchunk_load)"); }
+
+// the scan's three host arrays come together or not at all (all null: the results stay on the device)
+bool some_null(const void *a, const void *b, const void *d) { return (!a || !b || !d) && (a || b || d); }
 
 // ASCII -> the engine's packed layout, on the device
 void chunk_pack(lqchunk &c)
@@ -226,7 +229,7 @@ int lqchunk_sdust(lqchunk *c, int W, int T, uint32_t *masked, double *qual_psum,
 {
 	return chunk_guard(c, [&] {
 		need_loaded(*c);
-		if (c->n && (!masked || !qual_psum || !n_above_q7)) throw std::invalid_argument("null buffers");
+		if (c->n && some_null(masked, qual_psum, n_above_q7)) throw std::invalid_argument("null buffers");
 		lq_chunk_sdust(*c, W, T, masked, qual_psum, n_above_q7);
 	});
 }
@@ -235,8 +238,21 @@ int lqchunk_sdust_split(lqchunk *c, int W, int T, uint32_t piece, uint32_t *mask
 {
 	return chunk_guard(c, [&] {
 		need_loaded(*c);
-		if (c->n && (!masked || !qual_psum || !n_above_q7)) throw std::invalid_argument("null buffers");
+		if (c->n && some_null(masked, qual_psum, n_above_q7)) throw std::invalid_argument("null buffers");
 		lq_chunk_sdust_split(*c, W, T, piece, masked, qual_psum, n_above_q7, n_serial);
+	});
+}
+
+int lqchunk_sdust_table(lqchunk *c, const char *names, const uint64_t *name_off, uint8_t *out, uint64_t out_cap, uint64_t *out_len, lqsdust_stats *stats,
+                        uint32_t *excl, uint64_t excl_cap)
+{
+	return chunk_guard(c, [&] {
+		need_loaded(*c);
+		if (!out_len) throw std::invalid_argument("null buffers");
+		u64 st[LQSDUST_STATS_WORDS] = {0};
+		try { lq_chunk_sdust_table(*c, names, name_off, out, out_cap, out_len, st, excl, excl_cap); }
+		catch (...) { if (stats) memcpy(stats, st, sizeof(st)); throw; }      // (a table that does not fit: its size and summary are known)
+		if (stats) memcpy(stats, st, sizeof(st));
 	});
 }
 

@@ -15,6 +15,12 @@ struct alignas(16) GatherSeg { u64 src, dst; };        // source byte, destinati
 #define LQ_GATHER_FILL LQ_U64MAX     // src of a segment without source bytes: '!' (a record without a quality string)
 #define LQ_GATHER_SRC_PAD 32u        // bytes the raw buffer extends past its last byte
 
+// the low-complexity table as text (kernels_dust_table.hpp, dust.cpp): the names, the per-row tables, the lists and the text on the device
+struct LqDustTab {
+	DBuf names, noff, nlen, fthou, qthou, meta, rbytes, rec, unv, patch, ex1, ex2, st, text;
+	Prim prim;                                                // the scan of the rows' byte counts
+};
+
 struct lqchunk {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -39,6 +45,8 @@ struct lqchunk {
 	DBuf coff, tile_read, codes, amb, flags;                  // packed form
 	DBuf gseg, gtile;                                         // k_chunk_gather's segments and work list
 	DBuf fq_names, fq_noff, fq_be, fq_rec, fq_tile, fq_text;  // k_fastq_format's names and tables (writer.cpp), lqchunk_fastq's text
+	LqDustTab tb;                                             // lqchunk_sdust_table
+	bool dust_done = false;                                   // masked, psum and qv are a scan's of the reads loaded now
 	std::vector<u64> h_coff;                                  // packed chunks before read i
 	u64 n_chunks = 0; bool packed = false;
 	~lqchunk()
@@ -62,12 +70,15 @@ void lq_chunk_gather(lqchunk &c, const std::vector<u64> &off, const u8 *raw, std
 // in destination order, room for one more behind each; the per-tile work list is made on the device (k_fx_tileseg).  bam: as
 // lq_chunk_gather's (the reader's device walk of a BAM file, kernels_bamscan.hpp)
 void lq_chunk_gather_dev(lqchunk &c, const std::vector<u64> &off, const u8 *raw, GatherSeg *sseg, u64 n_sseg, GatherSeg *qseg, u64 n_qseg, bool upper, int bam = 0);
+// masked, psum, qv: the host's arrays, or all three null -- the results stay on the device (c.masked, c.psum, c.qv) for lq_chunk_sdust_table
 void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv);
 // the same table with the reads of A/C/G/T alone cut into pieces of `piece` bases (0: LQ_DUST_SPLIT_PIECE), the others walked by k_sdust;
 // n_serial (may be null): how many those were
 void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, double *psum, u32 *qv, u32 *n_serial);
 // the maximal runs of the pieces' mask per read (start << 32 | finish; none for a flagged read), kept in c.h_iv / c.h_ivoff / c.h_dflag
 void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece);
+// the table of the last scan as text (dust.cpp); stats: LQSDUST_STATS_WORDS words; excl (may be null): the reads on LongQC's exclusion lists
+void lq_chunk_sdust_table(lqchunk &c, const char *names, const u64 *name_off, u8 *out, u64 out_cap, u64 *out_len, u64 *stats, u32 *excl, u64 excl_cap);
 void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
 void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,
                  u32 *gc, u32 *pos_out, u16 *win_gc, u32 *kept);

@@ -1,9 +1,11 @@
 // longqc_amd/csrc/dust.cpp -- host side of the low-complexity table: the reference's `sdust` binary
 // (sdust.c:181-222) behind the C ABI of include/lqcov.h (lqsdust_*).  Reads go to the device as ASCII (a resident chunk, chunk.hpp), one
-// thread walks one read (kernels_dust.hpp); rows are formatted on the host with libc/libm like the reference.
+// thread walks one read (kernels_dust.hpp); rows are formatted on the host with libc/libm like the reference, or -- opt-in, lqsdust_format and
+// lqchunk_sdust_table -- on the device (kernels_dust_table.hpp), where the host takes only the mean qualities the device does not vouch for.
 #include "engine.hpp"
 #include "kernels_dust.hpp"
 #include "kernels_dust_split.hpp"
+#include "kernels_dust_table.hpp"
 #include "fastx.hpp"
 #include "chunk.hpp"
 using lq_cabi::guarded;
@@ -17,6 +19,7 @@ using lq_cabi::select_device;
 #include <mutex>
 #include <condition_variable>
 #include <exception>
+#include <algorithm>
 
 static inline dim3 nblk_d(u64 n, u32 b) { return dim3((unsigned)((n + b - 1) / b)); }
 
@@ -25,7 +28,8 @@ void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv
 {
 	if (W < 3 || W > 66) throw std::domain_error("sdust window outside [3, 66] (the window ring holds 64 words; the reference's default is 64)");
 	const u32 n = c.n;
-	if (n == 0) return;
+	c.dust_done = false;
+	if (n == 0) { c.dust_done = true; return; }
 	for (u32 i = 0; i < n; ++i) if (c.off[i + 1] - c.off[i] > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases");
 	lq_chunk_ready(c);
 	const u32 n_thr = (u32)std::min<u64>(((u64)n + LQ_DUST_THREADS - 1) / LQ_DUST_THREADS * LQ_DUST_THREADS, LQ_DUST_MAX_THREADS);
@@ -41,10 +45,13 @@ void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv
 	LQ_LAUNCH(k_sdust, nblk_d(n_thr, LQ_DUST_THREADS), LQ_DUST_THREADS, c.stream, c.seq.as<u8>(), c.has_qual ? c.qual.as<u8>() : (const u8*)nullptr,
 	          c.d_off.as<u64>(), n, (i32)W, (i32)T, c.q2p.as<double>(), c.pi.as<DustPI>(), c.masked.as<u32>(), c.psum.as<double>(), c.qv.as<u32>());
 	LQ_HIP_CHECK(hipGetLastError());
-	LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream));
-	LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+	if (masked) {                                              // (null: the results stay on the device, for lq_chunk_sdust_table)
+		LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+	}
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+	c.dust_done = true;
 }
 
 // ---- the scan in pieces (kernels_dust_split.hpp) -----------------------------------------------------------------------------
@@ -115,7 +122,8 @@ void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, doub
 	piece = dust_piece(c, W, piece);
 	const u32 n = c.n;
 	if (n_serial) *n_serial = 0;
-	if (n == 0) return;
+	c.dust_done = false;
+	if (n == 0) { c.dust_done = true; return; }
 	lq_chunk_ready(c);
 	if (!c.stream2) LQ_HIP_CHECK(hipStreamCreate(&c.stream2));
 	dust_q2p(c);
@@ -153,15 +161,18 @@ void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, doub
 			          c.dflag.as<u8>(), n, c.masked.as<u32>());
 			LQ_HIP_CHECK(hipGetLastError());
 		}
-		LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-		LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream2));
-		LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream2));
+		if (masked) {
+			LQ_HIP_CHECK(hipMemcpyAsync(masked, c.masked.p, n * 4, hipMemcpyDeviceToHost, c.stream));
+			LQ_HIP_CHECK(hipMemcpyAsync(psum, c.psum.p, n * 8, hipMemcpyDeviceToHost, c.stream2));
+			LQ_HIP_CHECK(hipMemcpyAsync(qv, c.qv.p, n * 4, hipMemcpyDeviceToHost, c.stream2));
+		}
 	} catch (...) {                                              // (nothing of this call stays queued behind the caller's buffers)
 		(void)hipStreamSynchronize(c.stream); (void)hipStreamSynchronize(c.stream2);
 		throw;
 	}
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream));                 // (`serial` and `soff` die here)
 	LQ_HIP_CHECK(hipStreamSynchronize(c.stream2));
+	c.dust_done = true;
 }
 
 void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece)
@@ -202,6 +213,178 @@ void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece)
 	}
 	c.iv_valid = true; c.iv_W = W; c.iv_T = T; c.iv_piece = piece;
 }
+
+// ---- the table as text (kernels_dust_table.hpp) ------------------------------------------------------------------------------
+// meanQ(qual.s, qual.l) of the reference (lqutils.c:51-58) with libm, 0.0 / 0 without qualities: lqsdust_main's rows and the rows the
+// device does not vouch for
+static double dust_meanq(bool has_q, double psum, int len)
+{
+	volatile double num = has_q ? psum : 0.0; volatile int ql = has_q ? len : 0;
+	return -10 * log10(num / ql);
+}
+
+// the rows of one mini-batch as the reference prints them (sdust.c:211-217)
+static void dust_print_rows(FILE *o, const ReadBatch &rb, const u32 *masked, const double *psum, const u32 *qv)
+{
+	const u32 n = rb.size();
+	for (u32 i = 0; i < n; ++i) {
+		const int len = (int)(rb.seq_off[i + 1] - rb.seq_off[i]);
+		const bool has_q = rb.any_qual && len > 0 && rb.qual[rb.seq_off[i]] != 0;
+		const double mq = dust_meanq(has_q, psum[i], len);
+		volatile double m = (double)masked[i]; volatile int sl = len;
+		fprintf(o, "%s\t%d\t%d\t%.3f\t%.3f\t%d\n", rb.name(i), (int)masked[i], len, m / sl, mq, (int)qv[i]);
+	}
+}
+
+namespace {
+static_assert(sizeof(lqsdust_stats) == LQSDUST_STATS_WORDS * 8, "lqsdust_stats is LQSDUST_STATS_WORDS words");
+struct DustTabIn {                                            // device arrays of n rows: len or off, has_q or qual (kernels_dust_table.hpp)
+	u32 n; const u32 *masked, *len; const u64 *off; const double *psum; const u8 *has_q, *qual; const u32 *q7;
+};
+
+// arrays on the device -> the text on the host.  Nothing is written to out or excl unless both have room
+void dust_table_queued(LqDustTab &tb, hipStream_t stream, const DustTabIn &in, const char *names, const u64 *name_off, double window, u8 *out, u64 out_cap,
+                u64 *out_len, u64 *stats, u32 *excl, u64 excl_cap)
+{
+	const u32 n = in.n;
+	*out_len = 0;
+	for (u32 w = 0; w < LQSDUST_STATS_WORDS; ++w) stats[w] = 0;
+	if (!n) return;
+	if (names && !name_off) throw std::invalid_argument("null buffers");
+	if (!(window >= 0)) throw std::invalid_argument("window must not be negative");
+	if (window == 0) window = LQ_DTAB_WINDOW;
+	// the names: the bytes names[blob0 .. blob1), where each starts in them, and its length
+	std::vector<u64> noff(n, 0);
+	std::vector<u32> nlen(n, 0);
+	u64 blob0 = LQ_U64MAX, blob1 = 0;
+	for (u32 i = 0; names && i < n; ++i) blob0 = std::min(blob0, name_off[i]);
+	for (u32 i = 0; names && i < n; ++i) {
+		const size_t l = strlen(names + name_off[i]);
+		if (l > 0xffffffULL) throw std::domain_error("a name of 2^24 bytes or more");
+		noff[i] = name_off[i] - blob0; nlen[i] = (u32)l;
+		blob1 = std::max(blob1, name_off[i] + l);
+	}
+	const u64 blob = names ? blob1 - blob0 : 0;
+	tb.names.ensure((size_t)blob + 16); tb.noff.ensure((size_t)n * 8); tb.nlen.ensure((size_t)n * 4);
+	tb.fthou.ensure((size_t)n * 8); tb.qthou.ensure((size_t)n * 8); tb.meta.ensure((size_t)n * 4); tb.rbytes.ensure(((size_t)n + 1) * 4);
+	tb.rec.ensure(((size_t)n + 1) * 8); tb.unv.ensure((size_t)n * sizeof(DustUnv)); tb.ex1.ensure((size_t)n * 4); tb.ex2.ensure((size_t)n * 4);
+	tb.st.ensure(LQ_DTAB_ST_WORDS * 8);
+	if (blob) LQ_HIP_CHECK(hipMemcpyAsync(tb.names.p, names + blob0, (size_t)blob, hipMemcpyHostToDevice, stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(tb.noff.p, noff.data(), (size_t)n * 8, hipMemcpyHostToDevice, stream));
+	LQ_HIP_CHECK(hipMemcpyAsync(tb.nlen.p, nlen.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream));
+	LQ_HIP_CHECK(hipMemsetAsync(tb.st.p, 0, LQ_DTAB_ST_WORDS * 8, stream));
+	LQ_HIP_CHECK(hipMemsetAsync(tb.rbytes.as<u32>() + n, 0, 4, stream));
+	const u32 grid = (u32)std::min<u64>(((u64)n + LQ_DTAB_THREADS - 1) / LQ_DTAB_THREADS, LQ_DTAB_MAX_BLOCKS);
+	LQ_LAUNCH(k_sdust_rows, grid, LQ_DTAB_THREADS, stream, n, tb.nlen.as<u32>(), in.masked, in.len, in.off, in.psum, in.has_q, in.qual, in.q7, window,
+	          tb.fthou.as<u64>(), tb.qthou.as<u64>(), tb.meta.as<u32>(), tb.rbytes.as<u32>(), tb.unv.as<DustUnv>(), tb.ex1.as<u32>(), tb.ex2.as<u32>(),
+	          tb.st.as<unsigned long long>());
+	LQ_HIP_CHECK(hipGetLastError());
+	u64 st[LQ_DTAB_ST_WORDS];
+	LQ_HIP_CHECK(hipMemcpyAsync(st, tb.st.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));                 // (noff and nlen die here)
+	const u64 k = st[LQ_DTAB_ST_UNV], e1 = st[LQ_DTAB_ST_EX1], e2 = st[LQ_DTAB_ST_EX2];
+	if (k > n || e1 > n || e2 > n) throw std::logic_error("the table's lists are longer than the chunk");
+	std::vector<DustPatch> patch;
+	if (k) {                                                      // the rows the device does not vouch for: meanQ with libm, the same rounding
+		std::vector<DustUnv> unv((size_t)k);
+		LQ_HIP_CHECK(hipMemcpyAsync(unv.data(), tb.unv.p, (size_t)k * sizeof(DustUnv), hipMemcpyDeviceToHost, stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(stream));
+		patch.resize((size_t)k);
+		for (u64 j = 0; j < k; ++j) {
+			patch[j].idx = unv[j].idx;
+			patch[j].qcls = lq_fmt3_round(dust_meanq(true, unv[j].psum, (int)unv[j].len), &patch[j].qthou);
+			if (LQ_F3_CLASS(patch[j].qcls) == LQ_F3_BIG) throw std::domain_error("a mean quality of 2^50 or more");
+		}
+		tb.patch.ensure((size_t)k * sizeof(DustPatch));
+		LQ_HIP_CHECK(hipMemcpyAsync(tb.patch.p, patch.data(), (size_t)k * sizeof(DustPatch), hipMemcpyHostToDevice, stream));
+		const u32 pgrid = (u32)std::min<u64>((k + LQ_DTAB_THREADS - 1) / LQ_DTAB_THREADS, LQ_DTAB_MAX_BLOCKS);
+		LQ_LAUNCH(k_sdust_patch, pgrid, LQ_DTAB_THREADS, stream, (u32)k, tb.patch.as<DustPatch>(), tb.qthou.as<u64>(), tb.meta.as<u32>(), tb.rbytes.as<u32>());
+		LQ_HIP_CHECK(hipGetLastError());
+	}
+	tb.prim.stream = stream;
+	tb.prim.exclusive_scan_u32_u64(tb.rbytes.as<u32>(), tb.rec.as<u64>(), (size_t)n + 1);
+	u64 total = 0;
+	LQ_HIP_CHECK(hipMemcpyAsync(&total, tb.rec.as<u64>() + n, 8, hipMemcpyDeviceToHost, stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));                 // (`patch` dies here)
+	*out_len = total;
+	stats[0] = n; stats[1] = total; stats[2] = st[LQ_DTAB_ST_MASKED]; stats[3] = st[LQ_DTAB_ST_Q7]; stats[4] = k; stats[5] = e1 + e2; stats[6] = e1;
+	if (total > out_cap) throw std::invalid_argument("out_cap is smaller than the table");
+	if (excl && e1 + e2 > excl_cap) throw std::invalid_argument("excl_cap is smaller than the exclusion lists");
+	if (!out) throw std::invalid_argument("null buffers");
+	tb.text.ensure((size_t)total + 16);
+	LQ_LAUNCH(k_sdust_text, grid, LQ_DTAB_THREADS, stream, n, tb.names.as<u8>(), tb.noff.as<u64>(), tb.nlen.as<u32>(), in.masked, in.len, in.off, in.q7,
+	          tb.fthou.as<u64>(), tb.qthou.as<u64>(), tb.meta.as<u32>(), tb.rec.as<u64>(), tb.text.as<u8>());
+	LQ_HIP_CHECK(hipGetLastError());
+	LQ_HIP_CHECK(hipMemcpyAsync(out, tb.text.p, (size_t)total, hipMemcpyDeviceToHost, stream));
+	if (excl && e1) LQ_HIP_CHECK(hipMemcpyAsync(excl, tb.ex1.p, (size_t)e1 * 4, hipMemcpyDeviceToHost, stream));
+	if (excl && e2) LQ_HIP_CHECK(hipMemcpyAsync(excl + e1, tb.ex2.p, (size_t)e2 * 4, hipMemcpyDeviceToHost, stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));
+	if (excl) { std::sort(excl, excl + e1); std::sort(excl + e1, excl + e1 + e2); }    // (the atomics' order -> file order)
+}
+
+// (its copies come from and go to memory of this call and of the caller: nothing of a call that throws stays queued behind them)
+void dust_table(LqDustTab &tb, hipStream_t stream, const DustTabIn &in, const char *names, const u64 *name_off, double window, u8 *out, u64 out_cap,
+                u64 *out_len, u64 *stats, u32 *excl, u64 excl_cap)
+{
+	try { dust_table_queued(tb, stream, in, names, name_off, window, out, out_cap, out_len, stats, excl, excl_cap); }
+	catch (...) { (void)hipStreamSynchronize(stream); throw; }
+}
+} // namespace
+
+void lq_chunk_sdust_table(lqchunk &c, const char *names, const u64 *name_off, u8 *out, u64 out_cap, u64 *out_len, u64 *stats, u32 *excl, u64 excl_cap)
+{
+	if (!c.dust_done) throw std::logic_error("no scan of the chunk loaded now (lqchunk_sdust, lqchunk_sdust_split)");
+	lq_cabi::select_device(c.device);
+	const DustTabIn in = {c.n, c.masked.as<u32>(), nullptr, c.d_off.as<u64>(), c.psum.as<double>(), nullptr, c.has_qual ? c.qual.as<u8>() : (const u8*)nullptr, c.qv.as<u32>()};
+	dust_table(c.tb, c.stream, in, names, name_off, 0, out, out_cap, out_len, stats, excl, excl_cap);
+}
+
+extern "C" {
+
+uint32_t lqsdust_fmt3(double x, uint64_t *thousandths)
+{
+	u64 t = 0;
+	const u32 c = lq_fmt3_round(x, &t);
+	if (thousandths) *thousandths = t;
+	return c;
+}
+
+int lqsdust_format_lists(int device, uint32_t n, const char *names, const uint64_t *name_off, const uint32_t *masked, const uint32_t *len,
+                         const double *qual_psum, const uint8_t *has_q, const uint32_t *n_above_q7, double window, uint8_t *out, uint64_t out_cap,
+                         uint64_t *out_len, lqsdust_stats *stats, uint32_t *excl, uint64_t excl_cap, char *errbuf, size_t errbuf_len)
+{
+	return guarded(errbuf, errbuf_len, [&] {
+		if (!out_len || (n && (!masked || !len || !qual_psum || !n_above_q7))) throw std::invalid_argument("null buffers");
+		lq_cabi::ScopedStream stream(device);
+		LqDustTab tb;
+		DBuf d_masked, d_len, d_psum, d_hq, d_q7;
+		u64 st[LQSDUST_STATS_WORDS] = {0};
+		try {                                                       // (the uploads read the caller's arrays: none stays queued if one throws)
+			if (n) {
+				d_masked.ensure((size_t)n * 4); d_len.ensure((size_t)n * 4); d_psum.ensure((size_t)n * 8); d_q7.ensure((size_t)n * 4); d_hq.ensure(n);
+				LQ_HIP_CHECK(hipMemcpyAsync(d_masked.p, masked, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+				LQ_HIP_CHECK(hipMemcpyAsync(d_len.p, len, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+				LQ_HIP_CHECK(hipMemcpyAsync(d_psum.p, qual_psum, (size_t)n * 8, hipMemcpyHostToDevice, stream));
+				LQ_HIP_CHECK(hipMemcpyAsync(d_q7.p, n_above_q7, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+				if (has_q) LQ_HIP_CHECK(hipMemcpyAsync(d_hq.p, has_q, n, hipMemcpyHostToDevice, stream));
+				else LQ_HIP_CHECK(hipMemsetAsync(d_hq.p, 0, n, stream));
+			}
+			const DustTabIn in = {n, d_masked.as<u32>(), d_len.as<u32>(), nullptr, d_psum.as<double>(), d_hq.as<u8>(), nullptr, d_q7.as<u32>()};
+			dust_table(tb, stream, in, names, name_off, window, out, out_cap, out_len, st, excl, excl_cap);
+		} catch (...) { (void)hipStreamSynchronize(stream); if (stats) memcpy(stats, st, sizeof(st)); throw; }
+		if (stats) memcpy(stats, st, sizeof(st));
+	});
+}
+
+int lqsdust_format(int device, uint32_t n, const char *names, const uint64_t *name_off, const uint32_t *masked, const uint32_t *len,
+                   const double *qual_psum, const uint8_t *has_q, const uint32_t *n_above_q7, double window, uint8_t *out, uint64_t out_cap,
+                   uint64_t *out_len, lqsdust_stats *stats, char *errbuf, size_t errbuf_len)
+{
+	return lqsdust_format_lists(device, n, names, name_off, masked, len, qual_psum, has_q, n_above_q7, window, out, out_cap, out_len, stats, nullptr, 0,
+	                            errbuf, errbuf_len);
+}
+
+} // extern "C"
 
 extern "C" {
 
@@ -290,14 +473,7 @@ int lqsdust_main(int argc, const char *const *argv, const char *out_path, const 
 			if (split) lq_chunk_sdust_split(D, W, T, 0, masked.data(), psum.data(), qv.data(), nullptr);
 			else lq_chunk_sdust(D, W, T, masked.data(), psum.data(), qv.data());
 			t0 = lq_now_s(); t_dev += t0 - t1;
-			for (u32 i = 0; i < n; ++i) {
-				const int len = (int)(rb.seq_off[i + 1] - rb.seq_off[i]);
-				const bool has_q = rb.any_qual && len > 0 && rb.qual[rb.seq_off[i]] != 0;
-				volatile double num = has_q ? psum[i] : 0.0; volatile int ql = has_q ? len : 0;     // meanQ(qual.s, qual.l): 0/0 without qualities
-				const double mq = -10 * log10(num / ql);
-				volatile double m = (double)masked[i]; volatile int sl = len;
-				fprintf(o, "%s\t%d\t%d\t%.3f\t%.3f\t%d\n", rb.name(i), (int)masked[i], len, m / sl, mq, (int)qv[i]);
-			}
+			dust_print_rows(o, rb, masked.data(), psum.data(), qv.data());
 			t1 = lq_now_s(); t_rows += t1 - t0; t0 = t1;
 			{ std::lock_guard<std::mutex> lk(mu); filled[k] = 0; }
 			cv.notify_all();

@@ -4,6 +4,7 @@ include/lqcov.h (lqsdust_main, lqsdust_reads).  No CPU fallback: without liblqco
 import ctypes as C
 import math
 import os
+from fractions import Fraction
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -19,6 +20,13 @@ def _lib(lib=None):
         lib.lqsdust_reads.restype = C.c_int
         lib.lqsdust_reads.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.lqsdust_format.restype = C.c_int
+        lib.lqsdust_format.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.lqsdust_format_lists.restype = C.c_int
+        lib.lqsdust_format_lists.argtypes = lib.lqsdust_format.argtypes[:-2] + [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        lib.lqsdust_fmt3.restype = C.c_uint32
+        lib.lqsdust_fmt3.argtypes = [C.c_double, C.c_void_p]
         lib._lqsdust_bound = True
     return lib
 
@@ -35,6 +43,64 @@ def split_mode(split):
     if mode not in SPLIT_MODES:
         raise ValueError("split must be 'serial' or 'pieces', not %r" % (mode,))
     return mode
+
+
+TABLE_MODES = ("host", "device")
+TABLE_STATS = ("rows", "bytes", "masked", "q7", "unvouched", "excluded", "excluded_first", "reserved")      # lqsdust_stats' words
+ROW_FIELDS_MAX = 48                                        # a row's bytes beside its name at most: lqchunk_sdust_table's capacity rule
+
+
+def table_mode(table):
+    """"host" | "device" | None (the environment variable LQSDUST_TABLE, "host" without it) -> the mode's name.  "device": the rows of a
+    resident chunk are formatted on the device (k_sdust_rows, k_sdust_text) and leave it as bytes; the table is the same"""
+    mode = os.environ.get("LQSDUST_TABLE", "host") if table is None else table
+    if mode not in TABLE_MODES:
+        raise ValueError("table must be 'host' or 'device', not %r" % (mode,))
+    return mode
+
+
+def stats_dict(words):
+    d = dict(zip(TABLE_STATS, (int(w) for w in words)))
+    del d["reserved"]
+    return d
+
+
+def with_lists(stats, excl):
+    """stats and the index array lqchunk_sdust_table / lqsdust_format_lists filled -> stats with exclude_first and exclude_second"""
+    k1, k = stats["excluded_first"], stats["excluded"]
+    stats["exclude_first"], stats["exclude_second"] = excl[:k1].tolist(), excl[k1:k].tolist()
+    return stats
+
+
+def fmt3(x: float, lib=None):
+    """"%.3f" of x as the table's kernels take it (lqsdust_fmt3): -> (class: 0 finite, 1 nan, 2 inf, 3 2^50 or more, + 4 with the sign
+    bit; thousandths of |x|)"""
+    t = C.c_uint64()
+    return int(_lib(lib).lqsdust_fmt3(float(x), C.byref(t))), t.value
+
+
+def format_rows(names: Sequence[str], masked, lens, psum, has_q, qv, window: float = 0.0, device: int = 0, lib=None, out_cap: Optional[int] = None):
+    """Arrays -> the table's text, made on the device (lqsdust_format): row i is what _rows prints for masked[i], lens[i], psum[i], qv[i]
+    and -- has_q[i] != 0 and lens[i] > 0 -- qualities.  window: 0 the default (2^-30), 1 every row with qualities takes the host's
+    meanQ.  -> (bytes, stats: a dict of TABLE_STATS and, as ReadChunk.sdust_table's, exclude_first / exclude_second, the ascending indices
+    of the rows on LongQC's two exclusion lists: lqsdust_format_lists)"""
+    lib = _lib(lib)
+    n = len(names)
+    nb, noff = api.encode_names(list(names))
+    masked, lens, qv = (np.ascontiguousarray(a, dtype=np.uint32) for a in (masked, lens, qv))
+    psum = np.ascontiguousarray(psum, dtype=np.float64)
+    has_q = np.ascontiguousarray(has_q, dtype=np.uint8) if has_q is not None else None
+    if any(a.shape != (n,) for a in (masked, lens, qv, psum)) or (has_q is not None and has_q.shape != (n,)):
+        raise ValueError("one entry per name in every array")
+    cap = len(nb) - n + ROW_FIELDS_MAX * n if out_cap is None else int(out_cap)
+    out, n_out, st, err = np.empty(max(cap, 1), np.uint8), C.c_uint64(), (C.c_uint64 * len(TABLE_STATS))(), C.create_string_buffer(512)
+    excl = np.zeros(max(2 * n, 1), np.uint32)
+    rc = lib.lqsdust_format_lists(device, n, nb, noff.ctypes.data, masked.ctypes.data, lens.ctypes.data, psum.ctypes.data,
+                                  has_q.ctypes.data if has_q is not None else None, qv.ctypes.data, float(window), out.ctypes.data, cap, C.byref(n_out), st,
+                                  excl.ctypes.data, 2 * n, err, 512)
+    if rc != 0:
+        raise api.LqcovError(rc, err.value.decode())
+    return out[:n_out.value].tobytes(), with_lists(stats_dict(st), excl)
 
 
 def run_sdust(fin: str, fout: str, device: int = 0, w: Optional[int] = None, t: Optional[int] = None, lib=None) -> None:
@@ -66,16 +132,18 @@ def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional
     chunk: a chunkpass.ReadChunk that holds these reads on the device already -- seqs and quals are not looked at, nothing is
     gathered or uploaded.  split, piece: split_mode's; "pieces" scans long reads in pieces of `piece` bases (lqchunk_sdust_split) --
     the rows are the same."""
+    return _rows(names, *_scan(names, seqs, quals, device, w, t, lib, chunk, split, piece))
+
+
+def _scan(names, seqs, quals, device, w, t, lib, chunk, split, piece):
+    """sdust_rows' scan -> (n, off, qflat, masked, psum, qv), what _rows takes behind the names"""
     split = split_mode(split)
     if chunk is not None:
-        return _rows(names, chunk.n, chunk.off, chunk.qual_first(), *chunk.sdust(w, t, split=split, piece=piece))
+        return (chunk.n, chunk.off, chunk.qual_first()) + tuple(chunk.sdust(w, t, split=split, piece=piece))
     if split == "pieces":                                  # (the pieces live on a resident chunk: one for this call)
-        from . import chunkpass
-        qs = quals if quals is not None else [None] * len(seqs)
-        reads = [[nm, bytes(s), bytes(q) if q is not None and q.shape[0] else None] for nm, s, q in zip(names, seqs, qs)]
-        ch = chunkpass.ReadChunk(reads, device=device, lib=lib)
+        ch = _chunk_of(names, seqs, quals, device, lib)
         try:
-            return _rows(names, ch.n, ch.off, ch.qual_first(), *ch.sdust(w, t, split=split, piece=piece))
+            return (ch.n, ch.off, ch.qual_first()) + tuple(ch.sdust(w, t, split=split, piece=piece))
         finally:
             ch.close()
     lib = _lib(lib)
@@ -98,7 +166,15 @@ def sdust_rows(names: Sequence[str], seqs: Sequence[np.ndarray], quals: Optional
                            w, t, masked.ctypes.data, psum.ctypes.data, qv.ctypes.data, err, 512)
     if rc != 0:
         raise api.LqcovError(rc, err.value.decode())
-    return _rows(names, n, off, qflat, masked, psum, qv)
+    return n, off, qflat, masked, psum, qv
+
+
+def _chunk_of(names, seqs, quals, device, lib):
+    """a resident chunk of reads in memory, for one call"""
+    from . import chunkpass
+    qs = quals if quals is not None else [None] * len(seqs)
+    reads = [[nm, bytes(s), bytes(q) if q is not None and q.shape[0] else None] for nm, s, q in zip(names, seqs, qs)]
+    return chunkpass.ReadChunk(reads, device=device, lib=lib)
 
 
 def _rows(names, n, off, qflat, masked, psum, qv) -> List[str]:
@@ -117,15 +193,22 @@ class LqMaskMI355X:
     """Counterpart of lq_mask.LqMask for the chunk loop of longQC.py (lq_mask.py:25-41, 99-121): submit_sdust(reads,
     chunk_n) per chunk, close_pool() at the end, get_outfile_path() -> analysis table `longqc_sdust<suffix>.txt` with one
     row per read in submission order.  Reads are LongQC's [name, seq, qual, ...] records (str or bytes); no temporary
-    FASTQ files, no process pool: every chunk is one call into the device.  The plots of LqMask are out of scope."""
+    FASTQ files, no process pool: every chunk is one call into the device.  The plots of LqMask are out of scope.
+    table (table_mode's) "device": a chunk's rows are formatted on the device and kept as bytes (ReadChunk.sdust_table); the file is the
+    same.  summary() and json_block() give what longQC.py:369-371, 452-471, 495-502 read back from the file, from arrays kept at submit
+    time in either mode."""
 
-    def __init__(self, work_dir: str, suffix: Optional[str] = None, device: int = 0, lib=None, split: Optional[str] = None):
+    def __init__(self, work_dir: str, suffix: Optional[str] = None, device: int = 0, lib=None, split: Optional[str] = None,
+                 table: Optional[str] = None):
         self.split = split_mode(split)                         # "pieces": long reads are scanned in pieces, the rows are the same
+        self.table = table_mode(table)                         # "device": the rows are formatted there, the file is the same
         self.suffix = "_" + suffix if suffix else ""
         os.makedirs(work_dir, exist_ok=True)
         self.wdir, self.device, self.lib = work_dir, device, lib
         self.outf = os.path.join(work_dir, "longqc_sdust" + self.suffix + ".txt")
         self._chunks = {}
+        self._lens, self._excl = {}, {}                        # per chunk: the lengths; the names on the two exclusion lists
+        self._masked = self._q7 = 0
 
     @staticmethod
     def _arr(v):
@@ -137,23 +220,97 @@ class LqMaskMI355X:
 
     def submit_sdust(self, reads, chunk_n, chunk=None):
         """chunk: the chunkpass.ReadChunk made of `reads` (its device copy is scanned; `reads` is not gathered again)"""
-        if chunk is not None:
-            self._chunks[chunk_n] = sdust_rows(chunk.names, None, None, chunk=chunk, split=self.split)
+        if self.table == "device":
+            own = chunk is None
+            if own:                                            # (the table is made from a resident chunk: one for this call)
+                names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
+                chunk = _chunk_of(names, [self._arr(r[1]) for r in reads], [self._arr(r[2]) if len(r) > 2 and r[2] else None for r in reads],
+                                  self.device, self.lib)
+            try:
+                text, st = chunk.sdust_table(split=self.split)
+                self._chunks[chunk_n] = text
+                self._note(chunk_n, chunk.lens, st["masked"], st["q7"], [chunk.names[i] for i in st["exclude_first"]],
+                           [chunk.names[i] for i in st["exclude_second"]])
+            finally:
+                if own:
+                    chunk.close()
             return
-        names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
-        seqs = [self._arr(r[1]) for r in reads]
-        quals = [self._arr(r[2]) if len(r) > 2 and r[2] else None for r in reads]
-        self._chunks[chunk_n] = sdust_rows(names, seqs, quals, device=self.device, lib=self.lib, split=self.split)
+        if chunk is not None:
+            names, seqs, quals = chunk.names, None, None
+        else:
+            names = [r[0].decode() if isinstance(r[0], (bytes, bytearray)) else str(r[0]) for r in reads]
+            seqs = [self._arr(r[1]) for r in reads]
+            quals = [self._arr(r[2]) if len(r) > 2 and r[2] else None for r in reads]
+        n, off, qflat, masked, psum, qv = _scan(names, seqs, quals, self.device, 64, 20, self.lib, chunk, self.split, None)
+        self._chunks[chunk_n] = _rows(names, n, off, qflat, masked, psum, qv)
+        lens = np.diff(np.asarray(off).astype(np.int64))
+        first, second = exclusion_lists(masked[:n], lens)
+        self._note(chunk_n, lens, int(masked[:n].sum(dtype=np.uint64)), int(qv[:n].sum(dtype=np.uint64)), [names[i] for i in first], [names[i] for i in second])
+
+    def _note(self, chunk_n, lens, masked, q7, first, second):
+        self._lens[chunk_n] = np.array(lens, dtype=np.int64)
+        self._excl[chunk_n] = (first, second)
+        self._masked += int(masked)
+        self._q7 += int(q7)
 
     def close_pool(self):
         with open(self.outf, "w") as out:                      # lq_mask.py:83-88 concatenates the chunk tables in submission order
             for k in self._chunks:
+                if isinstance(self._chunks[k], bytes):             # (a chunk's table from the device)
+                    out.flush()
+                    out.buffer.write(self._chunks[k])
+                    continue
                 for row in self._chunks[k]:
                     out.write(row + "\n")
         self._chunks = {}
 
     def get_outfile_path(self):
         return self.outf
+
+    def summary(self):
+        """What longQC.py reads back from the table (:369-371, 452-471), from the arrays kept at submit time, every chunk submitted so far:
+        n_reads, yield, longest, mean_length, n50 (lq_utils.get_N50: the first of the descending lengths at which the running sum reaches
+        half the yield), q7_bases, masked_bases, and exclude_seqs: the names of the reads with len > 500000 and a printed fraction above
+        0.2, then of those with len > 10000 and above 0.4, each list in file order (a read on both is named twice).  No reads: 0 everywhere"""
+        lens = np.concatenate([self._lens[k] for k in self._lens]) if self._lens else np.zeros(0, np.int64)
+        n, total = int(lens.shape[0]), int(lens.sum())
+        n50 = 0
+        if n:
+            d = np.sort(lens)[::-1]
+            n50 = int(d[int(np.searchsorted(np.cumsum(d), total / 2, side="left"))])
+        excl = [nm for which in (0, 1) for k in self._excl for nm in self._excl[k][which]]
+        return {"n_reads": n, "yield": total, "longest": int(lens.max()) if n else 0, "mean_length": float(lens.mean()) if n else 0.0, "n50": n50,
+                "q7_bases": self._q7, "masked_bases": self._masked, "exclude_seqs": excl}
+
+    def json_block(self):
+        """the entries of longQC.py:495-502 that come from the table (gamma_params is scipy's fit and stays with the caller)"""
+        s = self.summary()
+        if not s["n_reads"] or not s["yield"]:
+            raise ValueError("no bases submitted")
+        return {"Yield": s["yield"], "Q7 bases": "%.2f%%" % float(100 * s["q7_bases"] / s["yield"]), "Longest_read": s["longest"],
+                "Num_of_reads": s["n_reads"], "Length_stats": {"Mean_read_length": s["mean_length"], "N50_read_length": float(s["n50"])}}
+
+
+def _printed_above(thou: int) -> float:
+    """the smallest double that "%.3f" prints above thou / 1000: printf rounds the binary value exactly, so x prints above it exactly when
+    x > (thou + 0.5) / 1000 -- no double is that border (2000 has the factor 125), so no tie exists -- and one comparison decides"""
+    border = Fraction(2 * thou + 1, 2000)
+    c = float(border)                                      # (the nearest double, on either side)
+    return c if Fraction(c) > border else math.nextafter(c, math.inf)
+
+
+_ABOVE_200, _ABOVE_400 = _printed_above(200), _printed_above(400)
+
+
+def exclusion_lists(masked, lens):
+    """longQC.py:370-371 on arrays: the reads with len > 500000 and masked/len printed above 0.200, and those with len > 10000 and
+    printed above 0.400 -- pandas compares what it parsed, the "%.3f" text -> two ascending index lists.  Array work alone: the double
+    masked / len (the division _rows prints) against the smallest double that prints above the threshold"""
+    masked, lens = np.asarray(masked).astype(np.float64), np.asarray(lens).astype(np.int64)
+    frac = masked / np.maximum(lens, 1)
+    first = np.flatnonzero((lens > 500000) & (frac >= _ABOVE_200))
+    second = np.flatnonzero((lens > 10000) & (frac >= _ABOVE_400))
+    return first.tolist(), second.tolist()
 
 
 def _c_div(a: float, b: int) -> float:
