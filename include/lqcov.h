@@ -386,6 +386,30 @@ int lqgc_reads(int device, uint32_t n, const uint8_t *seq, const uint64_t *seq_o
                uint64_t seed, uint64_t first_read, uint32_t *gc, uint32_t *pos_out, uint16_t *win_gc, uint32_t *kept,
                char *errbuf, size_t errbuf_len);
 
+/* ---- the numbers behind the GC figure and the length figure (lq_gcfrac.py:49-85, lq_gamma.py:47-59, longQC.py:487-488) ------------ */
+/* Array-level calls over every read of a run; each uploads its array (fewer than 2^32 values, LQCOV_E_DOMAIN otherwise) and keeps
+ * nothing resident.  dtype: the element type of x, float32 or uint32; every value is converted to double exactly.  LQCOV_E_ARG: null
+ * pointers with non-zero sizes, another dtype, and what each call names.  Nothing is drawn.                                          */
+#define LQFIG_F32 0
+#define LQFIG_U32 1
+/* *min_out / *max_out (4 bytes each, of x's type) = the smallest and largest value, NaN left out.  LQCOV_E_ARG: n == 0, or NaN alone. */
+int lqfig_range(int device, int dtype, const void *x, uint64_t n, void *min_out, void *max_out, char *errbuf, size_t errbuf_len);
+/* np.histogram(x, bins=edges)'s counts for an explicit edge array: counts[k], k < n_edges - 1, = the values with edges[k] <= v <
+ * edges[k+1], the last bin closed on the right; a value below edges[0], above edges[n_edges-1] or NaN is counted nowhere.  n_edges < 2:
+ * no bins, nothing written.  n == 0: zero counts.  LQCOV_E_ARG: edges not ascending (equal neighbours pass, as in numpy) or NaN.     */
+int lqfig_hist(int device, int dtype, const void *x, uint64_t n, const double *edges, uint32_t n_edges, uint64_t *counts,
+               char *errbuf, size_t errbuf_len);
+/* sums[j], j < m, = sum over i < n of exp(-0.5 u u), u = (points[j] - data[i]) / h, in double, the difference taken first: the sum of
+ * a Gaussian KDE before its normalisation (density = sums[j] / n / (h sqrt(2 pi))).  The terms are added in an order fixed by n alone
+ * (tiles of 256 values in index order, a pairwise tree over the tiles): the same bytes from every call.  n == 0: zeros.
+ * LQCOV_E_ARG: m == 0, h not finite or <= 0.                                                                                          */
+int lqfig_kde(int device, const float *data, uint64_t n, const double *points, uint32_t m, double h, double *sums,
+              char *errbuf, size_t errbuf_len);
+/* *sum = sum of x (exact), *n_zero = the number of zeros, *sum_log = sum of log(x) over the non-zero values, in double, in the same fixed
+ * order: what the gamma fit of the read lengths needs (mean and mean log).  n == 0: zeros.                                            */
+int lqfig_logsum(int device, const uint32_t *x, uint64_t n, uint64_t *sum, double *sum_log, uint64_t *n_zero,
+                 char *errbuf, size_t errbuf_len);
+
 /* ---- one upload per chunk: the chunk loop of sampleqc (longQC.py:299-360) and the coverage call on the same device bytes ---------- */
 /* A resident chunk: lqchunk_load uploads the reads (ASCII, seq_off with n+1 ascending entries, qual NULL or parallel to seq as in
  * lqsdust_reads) once into device buffers the handle owns and reuses, growing, from chunk to chunk.  lqchunk_sdust, lqchunk_adapt and

@@ -683,7 +683,7 @@ class SampleQCPass:
     writes longqc_sdust<suffix>.txt), the adapter search trims a copy of the records (kept in `trimmed`, for --trim; `adapters` is the
     AdapterStats) as the reference's pool does, the subsample (`s_reads`, seed-7 reservoir of `nsample`) and the GC fractions (`gc`, an
     LqGCMI355X) see the untrimmed reads; then the chunk is packed on the device and appended to `store`.
-    coverage() maps the subsample against the stored chunks."""
+    coverage() maps the subsample against the stored chunks; figures() gives the numbers behind the GC and the length figure."""
 
     def __init__(self, work_dir: str, preset: str, adp5=None, adp3=None, nsample=5000, gc_draw: str = "device", device: int = 0,
                  fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None,
@@ -819,6 +819,11 @@ class SampleQCPass:
     def summary(self):
         """the mask's summary (LqMaskMI355X.summary): what longQC.py:369-371, 452-471 read back from the table"""
         return self.mask.summary()
+
+    def figures(self):
+        """the numbers behind the GC figure and the length figure of every chunk added (LqGCMI355X.figure_data,
+        LqMaskMI355X.length_figure_data): what longQC.py:449,487-488 compute before they draw"""
+        return {"gc": self.gc.figure_data(), "length": self.mask.length_figure_data()}
 
     def close(self):
         self.store.close()

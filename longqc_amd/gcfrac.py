@@ -8,7 +8,8 @@ The sampled positions (`np.random.choice(l, k, replace=False)` in the reference,
 draws: draw="numpy" calls np.random.choice per read on the host, in read order, as the reference does -- after
 np.random.seed(x) the object equals the reference's after the same seed; draw="device" evaluates a bijection of [0, l) keyed by
 (seed, the read's ordinal in the whole input) on the device: fast, reproducible, and independent of how the
-input was cut into chunks.  The plot and the KDE of plot_unmasked_gc_frac are not built."""
+input was cut into chunks.  plot_unmasked_gc_frac's figure is not drawn; figure_data() returns the numbers behind it -- the two
+histograms and the two KDE curves, made on the device over every read and window (longqc_amd/figdata.py) -- for the caller to plot."""
 import array
 import ctypes as C
 from typing import Optional, Sequence, Tuple
@@ -172,6 +173,29 @@ class LqGCMI355X:
     def gc_stats(self):
         """[mean, standard deviation] of the reads' GC fractions, as plot_unmasked_gc_frac returns them (lq_gcfrac.py:55)"""
         return [np.mean(self.r_frac), np.std(self.r_frac)]
+
+    def figure_data(self, b_width=0.02, n_points=50) -> dict:
+        """What plot_unmasked_gc_frac computes before it draws (lq_gcfrac.py:49-72), on the device (figdata.py): xs = np.linspace(0, 1.0,
+        n_points); read_hist / chunk_hist = (edges, counts, density) of plt.hist(frac, bins=np.arange(min, max + b_width, b_width),
+        density=True); read_kde / chunk_kde = gaussian_kde(frac)(xs), read_kde None for fewer than two reads as the reference skips it;
+        read_bandwidth / chunk_bandwidth the standard deviations of the two Gaussians (what lq_gcfrac.py:81-84 wanted to return;
+        None with read_kde); mean, sd = gc_stats().  ValueError when there is no read or no window (the reference's min() raises it),
+        and when a KDE is refused (one window, or values without variance)"""
+        from . import figdata
+        if len(self.r_frac) == 0 or len(self.c_frac) == 0:
+            raise ValueError("min() arg is an empty sequence")
+        xs = np.linspace(0, 1.0, n_points)
+        out = {"xs": xs}
+        for key, frac in (("read", self.r_frac), ("chunk", self.c_frac)):
+            a = np.array(frac, dtype=np.float32)                    # (a copy: a view would pin the array('f') against further appends)
+            lo, hi = figdata.value_range(a, self.device, self.lib)
+            out[key + "_hist"] = figdata.density_hist(a, float(lo), float(hi) + b_width, b_width, self.device, self.lib)
+            if key == "read" and len(frac) <= 1:
+                out["read_kde"] = out["read_bandwidth"] = None
+                continue
+            out[key + "_kde"], out[key + "_bandwidth"] = figdata.gaussian_kde_curve(a, xs, self.device, self.lib, return_bandwidth=True)
+        out["mean"], out["sd"] = self.gc_stats()
+        return out
 
     def json_block(self) -> dict:
         gc_read_mean, gc_read_sd = self.gc_stats()

@@ -193,7 +193,8 @@ class LqMaskMI355X:
     """Counterpart of lq_mask.LqMask for the chunk loop of longQC.py (lq_mask.py:25-41, 99-121): submit_sdust(reads,
     chunk_n) per chunk, close_pool() at the end, get_outfile_path() -> analysis table `longqc_sdust<suffix>.txt` with one
     row per read in submission order.  Reads are LongQC's [name, seq, qual, ...] records (str or bytes); no temporary
-    FASTQ files, no process pool: every chunk is one call into the device.  The plots of LqMask are out of scope.
+    FASTQ files, no process pool: every chunk is one call into the device.  Nothing is plotted: length_figure_data() gives the numbers of
+    the length figure (histogram, gamma fit); the masked-fraction histogram and the QV box plot of lq_mask.py:43-79 are not built.
     table (table_mode's) "device": a chunk's rows are formatted on the device and kept as bytes (ReadChunk.sdust_table); the file is the
     same.  summary() and json_block() give what longQC.py:369-371, 452-471, 495-502 read back from the file, from arrays kept at submit
     time in either mode."""
@@ -282,13 +283,45 @@ class LqMaskMI355X:
         return {"n_reads": n, "yield": total, "longest": int(lens.max()) if n else 0, "mean_length": float(lens.mean()) if n else 0.0, "n50": n50,
                 "q7_bases": self._q7, "masked_bases": self._masked, "exclude_seqs": excl}
 
-    def json_block(self):
-        """the entries of longQC.py:495-502 that come from the table (gamma_params is scipy's fit and stays with the caller)"""
+    def length_figure_data(self, b_width=1000) -> dict:
+        """What longQC.py:487-488 computes for the length figure, on the device (figdata.py), every chunk submitted so far: hist = (edges,
+        counts, density) of plt.hist(lengths, bins=np.arange(min(lengths), longest + b_width, b_width), density=True) (lq_gamma.py:54),
+        gamma_params = (a, scale) of gamma.fit(lengths, floc=0.0) (lq_gamma.py:47-49), and mean_length, n50, longest of summary().
+        ValueError for no reads, for a read of length 0 (scipy's FitDataError is one), and for lengths without spread (one read, or all
+        equal: log(mean) - mean(log) is not above the rounding of its two sums, and no shape maximises the likelihood)"""
+        from . import figdata
+        lens = np.concatenate([self._lens[k] for k in self._lens]) if self._lens else np.zeros(0, np.int64)
+        n = int(lens.shape[0])
+        if n == 0:
+            raise ValueError("no reads submitted")
+        if int(lens.max()) >= 1 << 32:
+            raise ValueError("a read of 2^32 bases or more")
+        u = lens.astype(np.uint32)
+        total, sum_log, zeros = figdata.log_sums(u, self.device, self.lib)
+        if zeros:
+            raise ValueError("Invalid values in `data`.  Maximum likelihood estimation with 'gamma' requires that 0 < x < inf for each x in `data`.")
+        # the rounding of s = log(mean) - sum_log / n: a unit each for the logarithm and the two divisions, and the device sum's bound
+        # (DESIGN 8(17): a logarithm, 256 sequential additions and a tree of log2 n levels, on non-negative terms)
+        s_err = (3 * abs(math.log(total / n)) + (2 + 256 + math.log2(n)) * abs(sum_log / n)) * 2.0 ** -53
+        if not math.log(total / n) - sum_log / n > s_err:
+            raise ValueError("the lengths have no spread that their sums can show: no gamma shape maximises the likelihood")
+        s = self.summary()
+        lo, _ = figdata.value_range(u, self.device, self.lib)
+        return {"hist": figdata.density_hist(u, int(lo), s["longest"] + b_width, b_width, self.device, self.lib),
+                "gamma_params": figdata.gamma_fit(n, total, sum_log), "mean_length": s["mean_length"], "n50": s["n50"], "longest": s["longest"]}
+
+    def json_block(self, with_gamma=False):
+        """the entries of longQC.py:495-502 that come from the table; with_gamma: Length_stats also holds "gamma_params": [a, scale], the
+        fit of longQC.py:487,500 (length_figure_data, figdata.gamma_fit), in the reference's place"""
         s = self.summary()
         if not s["n_reads"] or not s["yield"]:
             raise ValueError("no bases submitted")
+        stats = {"Mean_read_length": s["mean_length"], "N50_read_length": float(s["n50"])}
+        if with_gamma:
+            a, scale = self.length_figure_data()["gamma_params"]
+            stats = {"gamma_params": [float(a), float(scale)], **stats}
         return {"Yield": s["yield"], "Q7 bases": "%.2f%%" % float(100 * s["q7_bases"] / s["yield"]), "Longest_read": s["longest"],
-                "Num_of_reads": s["n_reads"], "Length_stats": {"Mean_read_length": s["mean_length"], "N50_read_length": float(s["n50"])}}
+                "Num_of_reads": s["n_reads"], "Length_stats": stats}
 
 
 def _printed_above(thou: int) -> float:
