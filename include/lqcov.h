@@ -297,6 +297,14 @@ int lqcov_debug_scan(lqcov_handle *h, const uint32_t *in, uint64_t *out, uint64_
  * lqcov_set_debug's bit 1 switch the pruning off here as they do in a mapping.) */
 int lqcov_debug_sort_anchors(lqcov_handle *h, uint64_t *xy, uint64_t n, const uint64_t *q_off, const uint32_t *q_klib, uint32_t n_q,
                              uint32_t n_targets, uint32_t max_len, const uint64_t *want, uint32_t n_want);
+/* Test access to the stage between the chains and the persisted intervals (filter_redundant_coords, lqmap.c:25-100, as a part's
+ * batch runs it: split, sort by query, offsets, room in the pool, the filter).  intervals: n triples (query in the engine's order,
+ * start, end), host array, laid out as lqcov_accum_export_dev hands intervals out and encoded as the chains emit them
+ * (position << 3 | flags, esterr.c:122-125), in any order: one part's intervals of these queries.  What the filter keeps, and the
+ * markers it makes, are appended to the handle's persisted intervals (lqcov_accum_export_dev shows them, lqcov_finish sweeps
+ * them).  The pool is not grown ahead as lqcov_part_map does.  info[0] = the persisted intervals afterwards, info[1] = 1 if this
+ * call had to move the earlier ones to a larger pool.  A query >= lqcov_n_queries is LQCOV_E_ARG. */
+int lqcov_debug_filter_intervals(lqcov_handle *h, const uint32_t *intervals, uint32_t n, uint32_t info[2]);
 /* What the last lqcov_part_map handed to the anchor sort, call by call (lqcov_set_debug bit 1; nothing is kept without it, and
  * while it is set the second pass sorts its queries whole, without pruning).  info[0] = the number of recorded sorts,
  * and for sort `index`: info[1] = its kind (0: every seed hit in klib's order -- LQCOV_TIES=klib, or the replay of a saturated

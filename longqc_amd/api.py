@@ -134,6 +134,7 @@ def load_library(path: Optional[str] = None):
         "lqcov_accum_set_replayed": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_uint64]),
         "lqcov_debug_sort_pairs": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint, C.c_int]),
         "lqcov_debug_sort_anchors": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+        "lqcov_debug_filter_intervals": (C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p]),
         "lqcov_get_sort_batches": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
         "lqcov_debug_scan": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_uint64]),
         "lqcov_part_minimizers_dev": (C.c_int, [H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), u64p]),
@@ -588,6 +589,14 @@ class Engine:
         self._ck(self.lib.lqcov_debug_sort_anchors(self.h, a.ctypes.data, a.shape[0], off.ctypes.data, kl.ctypes.data, kl.shape[0], n_targets, max_len,
                                                    None if w is None else w.ctypes.data, 0 if w is None else w.shape[0]))
         return a
+
+    def debug_filter_intervals(self, intervals: np.ndarray) -> Tuple[int, bool]:
+        """tests: one part's intervals (n, 3) uint32 = (query in the engine's order, start, end) through the per-part filter
+        (k_filter_redundant and what feeds it) -> (persisted intervals afterwards, whether their pool had to grow)"""
+        iv = np.ascontiguousarray(intervals, dtype=np.uint32).reshape(-1, 3)
+        info = np.zeros(2, dtype=np.uint32)
+        self._ck(self.lib.lqcov_debug_filter_intervals(self.h, iv.ctypes.data, iv.shape[0], info.ctypes.data))
+        return int(info[0]), bool(info[1])
 
     def sort_batches(self) -> List[dict]:
         """tests: every anchor sort of the last part_map (needs set_debug(2)) -- dict(kind, q = engine query numbers, klib, off,

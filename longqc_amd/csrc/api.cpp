@@ -629,6 +629,10 @@ int lqcov_debug_sort_anchors(lqcov_handle *h, uint64_t *xy, uint64_t n, const ui
 {
 	return guard(h, [&] { SortGeom g; g.n_targets = n_targets; g.max_len = max_len; h->debug_sort_anchors(xy, n, q_off, q_klib, n_q, g, want, want ? n_want : 0); });
 }
+int lqcov_debug_filter_intervals(lqcov_handle *h, const uint32_t *intervals, uint32_t n, uint32_t info[2])
+{
+	return guard(h, [&] { h->debug_filter_intervals(intervals, n, info); });
+}
 
 int lqcov_get_sort_batches(lqcov_handle *h, uint32_t index, uint32_t info[4], uint32_t *q, uint32_t *klib, uint64_t *off, uint64_t q_cap,
                            uint64_t *emitted, uint64_t *sorted, uint64_t a_cap, uint64_t *n_anchors)

@@ -1178,7 +1178,6 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	L.drop_arena_buffers();
 	lq_arena = L.arena.base ? &L.arena : nullptr;
 	struct ArenaGuard { ~ArenaGuard() { lq_arena = nullptr; } } arena_guard;
-	const u32 n_q = q.n;
 	int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_;
 	lq_tl("lane", lane_id, "batch begins, queries", (double)(q1 - q0));
 	L.gate_passed = false;
@@ -1275,31 +1274,40 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 		u32 ni = 0;
 		d2h(&ni, L.n_ivl.as<u32>(), 1, L.stream);
 		if (ni > ivl_cap) throw std::runtime_error("interval pool overflow");
-		if (ni) {
-			L.iv_q.ensure((u64)ni * 4); L.iv_q2.ensure((u64)ni * 4); L.iv_se.ensure((u64)ni * 8); L.iv_se2.ensure((u64)ni * 8);
-			L.ivq_off.ensure((n_q + 1) * 4); L.iv_scratch.ensure((u64)ni * 16);
-			LQ_LAUNCH(k_split_ivl, nblk(ni, 256), 256, L.stream, L.ivl.as<Ivl>(), ni, L.iv_q.as<u32>(), L.iv_se.as<u64>()); check_launch();
-			L.prim.sort_pairs_u32_u64(L.iv_q.as<u32>(), L.iv_q2.as<u32>(), L.iv_se.as<u64>(), L.iv_se2.as<u64>(), ni, 32);
-			LQ_LAUNCH(k_ivl_offsets, nblk(n_q + 1, 256), 256, L.stream, L.iv_q2.as<u32>(), ni, n_q, L.ivq_off.as<u32>()); check_launch();
-			// pv (the persisted intervals of all parts) is shared by the lanes: reserve the worst case under the lock, and grow
-			// it only with every lane's kernels drained
-			std::lock_guard<std::mutex> guard(pv_mu);
-			const u64 need = pv_reserved + 2 * (u64)ni;
-			if (need > 0xfffffff0ULL) throw std::domain_error("too many persisted intervals");
-			if (need > pv_cap) {
-				LQ_HIP_CHECK(hipDeviceSynchronize());
-				u32 npv = 0;
-				d2h(&npv, n_pv.as<u32>(), 1, L.stream);
-				grow_keep(pv, (u64)npv * sizeof(Ivl), need * sizeof(Ivl) * 2, L.stream);
-				pv_cap = (u32)std::min<u64>(pv.cap / sizeof(Ivl), 0xfffffff0ULL);
-			}
-			pv_reserved = need;
-			StageTimer t(this, L.stream, "k_filter_redundant");
-			LQ_LAUNCH(k_filter_redundant, nblk(n_q, 64), 64, L.stream, L.iv_se2.as<u64>(), L.ivq_off.as<u32>(), n_q, (u32)P.min_coverage,
-			          L.iv_scratch.as<u32>(), pv.as<Ivl>(), n_pv.as<u32>(), pv_cap);
-			check_launch();
-		}
+		if (ni) filter_intervals(L, ni);
 	}
+}
+
+// filter_redundant_coords per query (lqmap.c:25-100) on the ni intervals in L.ivl, whatever their order: they are split and sorted by
+// query, and what the filter keeps -- with the markers it makes -- is appended to pv.  true: pv had to grow.
+bool lqcov_handle::filter_intervals(MapLane &L, u32 ni)
+{
+	const u32 n_q = q.n;
+	bool grew = false;
+	L.iv_q.ensure((u64)ni * 4); L.iv_q2.ensure((u64)ni * 4); L.iv_se.ensure((u64)ni * 8); L.iv_se2.ensure((u64)ni * 8);
+	L.ivq_off.ensure((n_q + 1) * 4); L.iv_scratch.ensure((u64)ni * 16);
+	LQ_LAUNCH(k_split_ivl, nblk(ni, 256), 256, L.stream, L.ivl.as<Ivl>(), ni, L.iv_q.as<u32>(), L.iv_se.as<u64>()); check_launch();
+	L.prim.sort_pairs_u32_u64(L.iv_q.as<u32>(), L.iv_q2.as<u32>(), L.iv_se.as<u64>(), L.iv_se2.as<u64>(), ni, 32);
+	LQ_LAUNCH(k_ivl_offsets, nblk(n_q + 1, 256), 256, L.stream, L.iv_q2.as<u32>(), ni, n_q, L.ivq_off.as<u32>()); check_launch();
+	// pv (the persisted intervals of all parts) is shared by the lanes: reserve the worst case under the lock, and grow
+	// it only with every lane's kernels drained
+	std::lock_guard<std::mutex> guard(pv_mu);
+	const u64 need = pv_reserved + 2 * (u64)ni;
+	if (need > 0xfffffff0ULL) throw std::domain_error("too many persisted intervals");
+	if (need > pv_cap) {
+		LQ_HIP_CHECK(hipDeviceSynchronize());
+		u32 npv = 0;
+		d2h(&npv, n_pv.as<u32>(), 1, L.stream);
+		grow_keep(pv, (u64)npv * sizeof(Ivl), need * sizeof(Ivl) * 2, L.stream);
+		pv_cap = (u32)std::min<u64>(pv.cap / sizeof(Ivl), 0xfffffff0ULL);
+		grew = true;
+	}
+	pv_reserved = need;
+	StageTimer t(this, L.stream, "k_filter_redundant");
+	LQ_LAUNCH(k_filter_redundant, nblk(n_q, 64), 64, L.stream, L.iv_se2.as<u64>(), L.ivq_off.as<u32>(), n_q, (u32)P.min_coverage,
+	          L.iv_scratch.as<u32>(), pv.as<Ivl>(), n_pv.as<u32>(), pv_cap);
+	check_launch();
+	return grew;
 }
 
 static PsLists ps_lists(MapLane &L, int set, u32 sh)
@@ -2851,4 +2859,34 @@ void lqcov_handle::debug_sort_anchors(u64 *xy, u64 n, const u64 *q_off, const u3
 	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
 	d2h(ha.data(), L.A.as<mm128>(), n, L.stream);
 	for (u64 i = 0; i < n; ++i) { xy[2 * i] = ha[i].x; xy[2 * i + 1] = ha[i].y; }
+}
+
+// ---- tests: the per-part interval filter on intervals from the host (lqcov_debug_filter_intervals) ------------------------------------
+// Lane 0 as the chains of a part's batch leave it: n intervals (query in the engine's order, start, end) in L.ivl, in any order.
+// pv_reserved is taken from n_pv as map_part does, pv is not grown ahead.  No kernel of its own: what runs is filter_intervals.
+void lqcov_handle::debug_filter_intervals(const u32 *iv, u32 n, u32 info[2])
+{
+	if (!have_queries) throw std::logic_error("no queries");
+	if ((n && !iv) || !info) throw std::invalid_argument("null buffers");
+	if (n > 0x7ffffff0u) throw std::invalid_argument("too many intervals in one call");
+	for (u32 i = 0; i < n; ++i) if (iv[3 * (u64)i] >= q.n) throw std::invalid_argument("an interval of no query");
+	if (lanes.empty()) add_lane();
+	MapLane &L = *lanes[0];
+	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));
+	L.drop_arena_buffers();
+	u32 npv = 0;
+	d2h(&npv, n_pv.as<u32>(), 1, L.stream);
+	pv_reserved = npv;
+	bool grew = false;
+	if (n) {
+		static_assert(sizeof(Ivl) == 12, "interval layout");
+		L.ivl.ensure((u64)n * sizeof(Ivl));
+		h2d(L.ivl.as<Ivl>(), (const Ivl*)iv, n, L.stream);
+		grew = filter_intervals(L, n);
+		LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+		d2h(&npv, n_pv.as<u32>(), 1, L.stream);
+	}
+	info[0] = npv; info[1] = grew ? 1u : 0u;
+	finished = false;
 }

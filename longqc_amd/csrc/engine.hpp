@@ -312,6 +312,8 @@ struct lqcov_handle {
 	void debug_sort_pairs(u64 *keys, u64 *vals, u64 n, unsigned bits, int key_bytes);   // tests: the primitives of kernels_isort.hpp on host arrays
 	void debug_scan(const u32 *in, u64 *out, u64 n);
 	void debug_sort_anchors(u64 *xy, u64 n, const u64 *q_off, const u32 *q_klib, u32 n_q, SortGeom g, const u64 *want, u32 n_want);   // tests: sort_batch on anchors from the host
+	bool filter_intervals(MapLane &L, u32 ni);                  // the per-part filter on the ni intervals of L.ivl (map_batch); true: pv grew
+	void debug_filter_intervals(const u32 *iv, u32 n, u32 info[2]);   // tests: filter_intervals on intervals from the host
 	void add_lane();
 	static SortGeom sort_geom(const Part &pt);
 	bool sat_chains(Part &pt, u32 qi, const std::vector<u64> &h_aq, const std::vector<u64> &h_qmoff, std::vector<SatRec> &recs, std::vector<u32> &at);

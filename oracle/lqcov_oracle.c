@@ -1176,6 +1176,63 @@ int lqo_dump_chains(const lqo_params *p, const char *target_fn, const char *quer
 	return 0;
 }
 
+/* filter_redundant / reliable_region on intervals from a text file: "H n_queries n_parts", then "I part query start end" in part
+ * order (start, end: the encoded u32 of esterr.c:122-125).  Per part and query with lines in it, the filter on those lines in
+ * file order; after every part "V part query start end" of every query's list sorted by (start, end); after the last part the
+ * regions per query, "R query start end" then "M query start end", in the order they are pushed (as `ref_harness intervals`). */
+static int cmp_subc(const void *a_, const void *b_)
+{
+	const subc_t *a = (const subc_t*)a_, *b = (const subc_t*)b_;
+	if (a->start != b->start) return a->start < b->start ? -1 : 1;
+	return a->end < b->end ? -1 : a->end > b->end;
+}
+
+static void intervals_close_part(uint32_t part, uint32_t n_q, subc_v *v, subc_v *cv, uint32_t min_cov, FILE *out)
+{
+	uint32_t q;
+	size_t z;
+	for (q = 0; q < n_q; ++q) {
+		subc_v s = {0,0,0};
+		if (cv[q].n) filter_redundant(&v[q], &cv[q], min_cov);
+		free(cv[q].a); memset(&cv[q], 0, sizeof(cv[q]));
+		for (z = 0; z < v[q].n; ++z) vpush(s, v[q].a[z]);
+		if (s.n) qsort(s.a, s.n, sizeof(subc_t), cmp_subc);
+		for (z = 0; z < s.n; ++z) fprintf(out, "V\t%u\t%u\t%u\t%u\n", part, q, s.a[z].start, s.a[z].end);
+		free(s.a);
+	}
+}
+
+int lqo_dump_intervals(uint32_t min_cov, const char *fn, FILE *out)
+{
+	FILE *f = fopen(fn, "r");
+	uint32_t n_q = 0, n_p = 0, part = 0, q;
+	unsigned long a, b, c, d;
+	subc_v *v, *cv;
+	char tag[4];
+	size_t z;
+	if (!f) return -1;
+	if (fscanf(f, "%3s %lu %lu", tag, &a, &b) != 3 || strcmp(tag, "H") != 0) { fclose(f); return -1; }
+	n_q = (uint32_t)a; n_p = (uint32_t)b;
+	v = (subc_v*)calloc(n_q ? n_q : 1, sizeof(subc_v)); cv = (subc_v*)calloc(n_q ? n_q : 1, sizeof(subc_v));
+	while (fscanf(f, "%3s %lu %lu %lu %lu", tag, &a, &b, &c, &d) == 5) {
+		subc_t s;
+		if (strcmp(tag, "I") != 0 || a < part || a >= n_p || b >= n_q) { fclose(f); return -1; }
+		for (; part < a; ++part) intervals_close_part(part, n_q, v, cv, min_cov, out);
+		s.start = (uint32_t)c; s.end = (uint32_t)d;
+		vpush(cv[b], s);
+	}
+	for (; part < n_p; ++part) intervals_close_part(part, n_q, v, cv, min_cov, out);
+	for (q = 0; q < n_q; ++q) {
+		subc_v regs = {0,0,0}, mregs = {0,0,0};
+		reliable_region(&v[q], min_cov, &regs, &mregs);
+		for (z = 0; z < regs.n; ++z) fprintf(out, "R\t%u\t%u\t%u\n", q, regs.a[z].start, regs.a[z].end);
+		for (z = 0; z < mregs.n; ++z) fprintf(out, "M\t%u\t%u\t%u\n", q, mregs.a[z].start, mregs.a[z].end);
+		free(regs.a); free(mregs.a); free(v[q].a);
+	}
+	free(v); free(cv); fclose(f);
+	return 0;
+}
+
 /* pass-2 formatter (minimap2-coverage.c:545-617) */
 static void format_row(const lqo_params *p, const fx_rec *q, qstate_t *s, FILE *out)
 {

@@ -58,6 +58,8 @@ int lqo_dump_sketch(const lqo_params *p, const char *fn, FILE *out);
 int lqo_dump_index(const lqo_params *p, const char *fn, FILE *out);
 /* First index part only: per query Q/C/V/N records (as `ref_harness chains`). */
 int lqo_dump_chains(const lqo_params *p, const char *target_fn, const char *query_fn, FILE *out);
+/* The per-part interval filter and the region sweep on intervals from a text file: V/R/M records (as `ref_harness intervals`). */
+int lqo_dump_intervals(uint32_t min_cov, const char *fn, FILE *out);
 /* The whole path: the 9-column table (minimap2-coverage.c:545-617). */
 int lqo_run_files(const lqo_params *p, const char *target_fn, const char *query_fn, FILE *out, FILE *log);
 

@@ -7,6 +7,7 @@
  *   lqcov_oracle sketch [opts] <reads>
  *   lqcov_oracle index  [opts] <targets>
  *   lqcov_oracle chains [opts] <targets> <queries>
+ *   lqcov_oracle intervals <min_cov> <file>
  *   opts: -k -w -H -I -g -n -m -p -q -s -a -l -c -r -Y -X -f  --stable-sort --grouped --ties-reversed --ties-hashed  --bw N
  */
 #include <stdio.h>
@@ -42,6 +43,10 @@ int main(int argc, char **argv)
 		}
 		if (!fn) return 2;
 		return lqo_sdust_file(fn, W, T, stdout) ? 1 : 0;
+	}
+	if (!strcmp(argv[1], "intervals")) {                    /* == `ref_harness intervals <min_cov> <file>` */
+		if (argc != 4) { fprintf(stderr, "usage: lqcov_oracle intervals <min_cov> <file>\n"); return 2; }
+		return lqo_dump_intervals((uint32_t)strtoul(argv[2], 0, 10), argv[3], stdout) ? 1 : 0;
 	}
 	lqo_params_default(&p);
 	p.min_ovlp = 1000;

@@ -9,6 +9,13 @@
  *   ref_harness index  <k> <w> <hpc> <I> <targets.fx>        mm_idx_gen (index.c:311) + mm_idx_cal_max_occ (index.c:123)
  *   ref_harness chains <k> <w> <hpc> <I> <m> <p> <q> <targets.fx> <queries.fx>
  *                                                             lq_map_frag_mod (lqmap.c:207) on the first index part only
+ *   ref_harness intervals <min_cov> <file>                    filter_redundant_coords (lqmap.c:25) per part and query, then
+ *                                                             compute_reliable_region (lqutils.c:83) per query
+ *
+ * `intervals` reads text: "H <n_queries> <n_parts>", then "I <part> <query> <start> <end>" in part order, start and end being the
+ * encoded u32 of esterr.c:122-125.  Per part, every query with lines in it gets a malloc'd cv in file order and one call of the
+ * filter; after each part "V part query start end" of every query's v sorted by (start, end); after the last part per query
+ * "R query start end" and then "M query start end" in the order the function pushes them.
  *
  * Output is plain text on stdout, one record per line, in a canonical order.
  */
@@ -165,11 +172,74 @@ static int cmd_chains(int argc, char **argv)
 	return 0;
 }
 
+void filter_redundant_coords(lq_subcoords_v *v, lq_subcoords_v *cv, void *km, uint32_t min_cov);
+void compute_reliable_region(lq_subcoords_v *v, uint32_t min_cov, lq_subcoords_v *coords, lq_subcoords_v *mcoords);
+
+static uint32_t intervals_min_cov;
+
+static int subc_cmp(const void *a_, const void *b_)
+{
+	const lq_subcoords_t *a = (const lq_subcoords_t*)a_, *b = (const lq_subcoords_t*)b_;
+	if (a->start != b->start) return a->start < b->start ? -1 : 1;
+	return a->end < b->end ? -1 : a->end > b->end;
+}
+
+/* the intervals of one part are all read: the filter per query that has some (it frees cv->a), then every query's list */
+static void intervals_close_part(uint32_t part, uint32_t n_q, lq_subcoords_v *v, lq_subcoords_v *cv)
+{
+	uint32_t q;
+	size_t z;
+	for (q = 0; q < n_q; ++q) {
+		lq_subcoords_t *s;
+		if (cv[q].n) filter_redundant_coords(&v[q], &cv[q], 0, intervals_min_cov);
+		memset(&cv[q], 0, sizeof(cv[q]));
+		if (v[q].n == 0) continue;
+		s = (lq_subcoords_t*)malloc(v[q].n * sizeof(lq_subcoords_t));
+		memcpy(s, v[q].a, v[q].n * sizeof(lq_subcoords_t));
+		qsort(s, v[q].n, sizeof(lq_subcoords_t), subc_cmp);
+		for (z = 0; z < v[q].n; ++z) printf("V\t%u\t%u\t%u\t%u\n", part, q, s[z].start, s[z].end);
+		free(s);
+	}
+}
+
+static int cmd_intervals(int argc, char **argv)
+{
+	FILE *f = fopen(argv[3], "r");
+	uint32_t n_q, n_p, part = 0, q;
+	unsigned long a, b, c, d;
+	lq_subcoords_v *v, *cv;
+	char tag[4];
+	size_t z;
+	intervals_min_cov = (uint32_t)strtoul(argv[2], 0, 10);
+	if (!f) { fprintf(stderr, "cannot open %s\n", argv[3]); return 1; }
+	if (fscanf(f, "%3s %lu %lu", tag, &a, &b) != 3 || strcmp(tag, "H") != 0) { fprintf(stderr, "no header line\n"); return 1; }
+	n_q = (uint32_t)a; n_p = (uint32_t)b;
+	v = (lq_subcoords_v*)calloc(n_q ? n_q : 1, sizeof(lq_subcoords_v)); cv = (lq_subcoords_v*)calloc(n_q ? n_q : 1, sizeof(lq_subcoords_v));
+	while (fscanf(f, "%3s %lu %lu %lu %lu", tag, &a, &b, &c, &d) == 5) {
+		lq_subcoords_t s;
+		if (strcmp(tag, "I") != 0 || a < part || a >= n_p || b >= n_q) { fprintf(stderr, "bad line: %s %lu %lu\n", tag, a, b); return 1; }
+		for (; part < a; ++part) intervals_close_part(part, n_q, v, cv);
+		s.start = (uint32_t)c; s.end = (uint32_t)d;
+		kv_push(lq_subcoords_t, 0, cv[b], s);
+	}
+	for (; part < n_p; ++part) intervals_close_part(part, n_q, v, cv);
+	for (q = 0; q < n_q; ++q) {
+		lq_subcoords_v regs = {0,0,0}, mregs = {0,0,0};
+		compute_reliable_region(&v[q], intervals_min_cov, &regs, &mregs);
+		for (z = 0; z < regs.n; ++z) printf("R\t%u\t%u\t%u\n", q, regs.a[z].start, regs.a[z].end);
+		for (z = 0; z < mregs.n; ++z) printf("M\t%u\t%u\t%u\n", q, mregs.a[z].start, mregs.a[z].end);
+		free(regs.a); free(mregs.a); free(v[q].a);
+	}
+	free(v); free(cv); fclose(f);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc == 4 && strcmp(argv[1], "intervals") == 0) return cmd_intervals(argc, argv);
 	if (argc >= 6 && strcmp(argv[1], "sketch") == 0) return cmd_sketch(argc, argv);
 	if (argc >= 7 && strcmp(argv[1], "index") == 0) return cmd_index(argc, argv);
 	if (argc >= 11 && strcmp(argv[1], "chains") == 0) return cmd_chains(argc, argv);
-	fprintf(stderr, "usage: ref_harness sketch|index|chains ... (see header)\n");
+	fprintf(stderr, "usage: ref_harness sketch|index|chains|intervals ... (see header)\n");
 	return 2;
 }

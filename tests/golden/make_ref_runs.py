@@ -17,7 +17,8 @@ from tests import oracle_bind  # noqa: E402
 
 TESTS = ["tests/test_oracle_vs_ref.py",
          "tests/test_sdust.py::test_oracle_sdust_vs_reference_binary_on_synthetic_reads",
-         "tests/test_emu_pipeline.py::test_fuzz_tool_runs_a_case"]
+         "tests/test_emu_pipeline.py::test_fuzz_tool_runs_a_case",
+         "tests/test_intervals.py::test_interval_inputs_have_teeth"]
 
 
 def main():

@@ -189,3 +189,148 @@ def all_hits(qxy, qoff, txy, qlen, qnames, tnames, mid_occ):
     below = np.array([[tn.encode() < qn.encode() for tn in tnames] for qn in qnames])
     return dict(q=q, rid=rid, rs=rs, diag=diag, jl=j - qoff[q], y=y.astype(np.int32), r=rpos.astype(np.int32),
                 drop_self=same[q, rid] & (rpos == qpos), drop_ava=below[q, rid])
+
+
+# ---- tests/test_intervals.py: overlap intervals of the test's choosing, as text for `ref_harness intervals` ----
+IVL_N_QUERIES = 130                                             # 64 + 64 + 2 threads of k_filter_redundant / k_reliable
+# queries (caller's order) without any interval.  The engine holds the queries longest first, the test runs every case with the
+# lengths ascending and descending: the set is its own mirror image at the ends and in the middle, so that the engine's
+# positions 0, 63, 64 and 129 (the edges of the 64-thread blocks) are empty both times; 17 and 100 lie inside a block
+IVL_EMPTY = (0, 17, 63, 64, 65, 66, 100, 129)
+
+
+def ivl_enc(s, e, med):
+    """a chain's query interval [s, e) as esterr.c:122-125 encodes it: position << 3 | 2 if the score is medium | 1 at the end"""
+    f = 2 if med else 0
+    return (s << 3) | f, (e << 3) | f | 1
+
+
+def _ivl_random(rng, n, span, lengths, p_med=0.6):
+    out = []
+    for _ in range(n):
+        L = int(lengths[int(rng.integers(0, len(lengths)))]) if isinstance(lengths, (list, tuple)) else int(rng.integers(lengths.start, lengths.stop))
+        s = int(rng.integers(0, span - L + 1))
+        out.append(ivl_enc(s, s + L, bool(rng.random() < p_med)))
+    return out
+
+
+def _ivl_quirk_block(form):
+    """lqmap.c:63 takes the decoded end minus the *encoded* start: a merged region that closes where end == 8 * start + 2 (the
+    start event of a medium interval carries flag 2) has length 0 there and makes no marker.  form 1 (for -c 1): a lone medium
+    interval [s, 8s + 2); form 2 (for -c 2): [max(s - 1, 0), 8s + 2) under [s, 8s + 5), the coverage reaches 2 at s and leaves it
+    at 8s + 2.  With each, the neighbours that close one base earlier and later.  -> [(s, offset of the end, [intervals])] * 12"""
+    out = []
+    for s in range(4):
+        for d in (-1, 0, 1):
+            x = 8 * s + 2 + d
+            out.append((s, d, [ivl_enc(s, x, True)] if form == 1 else [ivl_enc(max(s - 1, 0), x, True), ivl_enc(s, 8 * s + 5, True)]))
+    return out
+
+
+def _ivl_marker_block(min_cov):
+    """part 0: min_cov medium intervals [100, 200), which the filter merges into one marker; part 1: an interval strictly inside
+    the merged region, equal to it, sharing one end with it, overhanging it by one base on either side or both -- each as one
+    medium interval, as one that is not medium, and as min_cov medium ones (a second merged region); part 2: one medium interval
+    over everything.  -> [[part 0, part 1, part 2]] * 21, one entry per query"""
+    out = []
+    for s, e in ((120, 150), (100, 200), (100, 150), (150, 200), (99, 200), (100, 201), (99, 201)):
+        for med, copies in ((True, 1), (False, 1), (True, min_cov)):
+            out.append([[ivl_enc(100, 200, True)] * min_cov, [ivl_enc(s, e, med)] * copies, [ivl_enc(50, 250, True)]])
+    return out
+
+
+def make_interval_cases(seed=83):
+    """The generator of the inputs of tests/test_intervals.py (its docstring describes them): a list of dict(name, min_cov, parts =
+    three lists of (query in the caller's order, start, end) in the order the reference is given them, quirk = {query: (form, s,
+    offset)} for the hand-made inputs of lqmap.c:63, whose intervals are all in part 0, random = the queries whose intervals are
+    the same in every `mixed` case, grows = the part whose call has to move the persisted intervals to a larger pool, or None).
+    What it made is kept under tests/golden/intervals/ (tests/golden/make_interval_inputs.py): the recorded runs of the reference
+    are keyed by the bytes of their input, which must not hang on a random generator's stream staying what it was."""
+    rng = np.random.default_rng(seed)
+    usable = [q for q in range(IVL_N_QUERIES) if q not in IVL_EMPTY]
+    slots = [usable[i] for i in rng.permutation(len(usable))]
+    fam = {}
+    for name, n in (("crowded12", 8), ("crowded40", 8), ("ord3000", 2), ("ord200000", 2), ("marker", 21), ("quirk1", 12), ("quirk2", 12)):
+        fam[name], slots = slots[:n], slots[n:]
+    fam["sparse"] = slots
+    rnd = [[], [], []]                                          # the same in every mixed case
+    for p in range(3):
+        for q in fam["crowded12"] + fam["crowded40"]:
+            span = 12 if q in fam["crowded12"] else 40
+            rnd[p] += [(q,) + iv for iv in _ivl_random(rng, int(rng.integers(6, 41)), span, [0, 1, 2, span // 8, span // 2])]
+        for q in fam["ord3000"] + fam["ord200000"]:
+            span = 3000 if q in fam["ord3000"] else 200000
+            rnd[p] += [(q,) + iv for iv in _ivl_random(rng, int(rng.integers(30, 65)), span, range(span // 50, span // 3))]
+        for q in fam["sparse"]:
+            rnd[p] += [(q,) + iv for iv in _ivl_random(rng, int(rng.integers(0, 3)), 3000, range(50, 1500))]
+    random_queries = sorted(fam["crowded12"] + fam["crowded40"] + fam["ord3000"] + fam["ord200000"] + fam["sparse"])
+    cases = []
+    for c in (1, 2, 3, 5):
+        parts = [list(x) for x in rnd]
+        quirk = {}
+        for form in (1, 2):
+            for q, (s, d, ivs) in zip(fam["quirk%d" % form], _ivl_quirk_block(form)):
+                parts[0] += [(q,) + iv for iv in ivs]
+                quirk[q] = (form, s, d)
+        for q, per_part in zip(fam["marker"], _ivl_marker_block(c)):
+            for p in range(3):
+                parts[p] += [(q,) + iv for iv in per_part[p]]
+        parts = [[ivs[i] for i in rng.permutation(len(ivs))] for ivs in parts]   # (the queries' lines interleaved)
+        cases.append(dict(name="mixed_c%d" % c, min_cov=c, parts=parts, quirk=quirk, random=random_queries, grows=None))
+    # the long list: a query of 1800 intervals a part (the per-thread heapsort over 3600 and, in pass 2, over all that is persisted)
+    # between neighbours of one and of two intervals, and a query whose intervals are all the same
+    parts = []
+    for p in range(3):
+        one = [(70,) + iv for iv in _ivl_random(rng, 1800, 3000000, range(200, 10000))]
+        one += [(69,) + iv for iv in _ivl_random(rng, 1, 3000000, range(200, 10000))] + [(71,) + iv for iv in _ivl_random(rng, 2, 3000000, range(200, 10000))]
+        one += [(40,) + ivl_enc(1000, 2000, True)] * 30
+        parts.append([one[i] for i in rng.permutation(len(one))])
+    cases.append(dict(name="long_c3", min_cov=3, parts=parts, quirk={}, random=[], grows=None))
+    # growth: a small first part leaves a small pool with intervals in it, the second part does not fit
+    qs = [q for q in usable if q % 3 == 0]
+    parts = [[(qs[int(rng.integers(0, 5))],) + iv for iv in _ivl_random(rng, 12, 300, range(20, 200), 1.0)],
+             [(qs[int(rng.integers(0, len(qs)))],) + iv for iv in _ivl_random(rng, 300, 3000, range(50, 1500))],
+             [(qs[int(rng.integers(0, len(qs)))],) + iv for iv in _ivl_random(rng, 20, 3000, range(50, 1500))]]
+    cases.append(dict(name="growth_c3", min_cov=3, parts=parts, quirk={}, random=[], grows=1))
+    return cases
+
+
+def interval_cases():
+    """the inputs of tests/test_intervals.py as committed: tests/golden/intervals/cases.json (name, min_cov, quirk, random, grows
+    of every case) and <name>.txt.gz (its intervals, as the text the harness reads) -> the list make_interval_cases describes"""
+    import gzip
+    import json
+    d = os.path.join(GOLDEN, "intervals")
+    cases = json.load(open(os.path.join(d, "cases.json")))
+    for c in cases:
+        c["quirk"] = {int(q): tuple(v) for q, v in c["quirk"].items()}
+        with gzip.open(os.path.join(d, c["name"] + ".txt.gz"), "rt") as f:
+            head = f.readline().split()
+            assert head[0] == "H" and int(head[1]) == IVL_N_QUERIES
+            c["parts"] = [[] for _ in range(int(head[2]))]
+            for line in f:
+                t = line.split()
+                c["parts"][int(t[1])].append((int(t[2]), int(t[3]), int(t[4])))
+    return cases
+
+
+def write_interval_case(case, path):
+    """a case as the text `ref_harness intervals` and `lqcov_oracle intervals` read"""
+    with open(path, "w") as f:
+        f.write("H %d %d\n" % (IVL_N_QUERIES, len(case["parts"])))
+        for p, ivs in enumerate(case["parts"]):
+            for q, s, e in ivs:
+                f.write("I %d %d %d %d\n" % (p, q, s, e))
+
+
+def parse_interval_dump(text, n_parts=3):
+    """`intervals` dump -> (V[part][query] = sorted [(start, end)], R[query] = [(start, end)] as pushed, M[query] likewise)"""
+    V = [dict() for _ in range(n_parts)]
+    R, M = {}, {}
+    for line in text.splitlines():
+        f = line.split("\t")
+        if f[0] == "V":
+            V[int(f[1])].setdefault(int(f[2]), []).append((int(f[3]), int(f[4])))
+        elif f[0] in ("R", "M"):
+            (R if f[0] == "R" else M).setdefault(int(f[1]), []).append((int(f[2]), int(f[3])))
+    return V, R, M

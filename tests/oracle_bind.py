@@ -70,8 +70,11 @@ def _ref_run(tool: str, exe: str, args: Sequence, outputs: Sequence[str] = ()) -
     """stdout of the reference's `tool` (its files in `outputs` written); RuntimeError if it fails"""
     args = [str(a) for a in args]
     key = _run_key(tool, args, outputs)
-    if os.path.exists(exe):
-        r = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    fn = os.path.join(RECORDED, key + ".gz")
+    r = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE) if os.path.exists(exe) else None
+    if r is not None and r.returncode == 2 and r.stderr.startswith(b"usage:") and os.path.exists(fn):
+        r = None                                                # a harness built before this command existed: the recorded run stands in
+    if r is not None:
         if r.returncode != 0:
             raise RuntimeError("%s failed (%d): %s" % (tool, r.returncode, r.stderr.decode(errors="replace")[-2000:]))
         if os.environ.get("LQCOV_RECORD_REF") == "1":
@@ -81,7 +84,6 @@ def _ref_run(tool: str, exe: str, args: Sequence, outputs: Sequence[str] = ()) -
                 with open(o, "rb") as f:
                     _save_gz(os.path.join(RECORDED, "%s.out%d.gz" % (key, i)), f.read())
         return r.stdout.decode()
-    fn = os.path.join(RECORDED, key + ".gz")
     if not os.path.exists(fn):
         raise RuntimeError("%s: oracle/_ref is not built and no run of the reference with these inputs is recorded "
                            "(tests/golden/make_ref_runs.py records them where it is)" % tool)

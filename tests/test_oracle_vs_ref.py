@@ -8,7 +8,7 @@ import os
 import pytest
 
 from tests import oracle_bind
-from tests.helpers import GOLDEN, ONT, limits_dataset
+from tests.helpers import GOLDEN, ONT, interval_cases, limits_dataset, write_interval_case
 
 VARIANTS = {
     "ont": ONT,
@@ -47,6 +47,17 @@ def test_chains_intervals_counters(datasets):
     want = oracle_bind.ref_dump(["chains", "12", "5", "0", "4G", "40", "160", "160", tf, qf])
     got = oracle_bind.dump("chains", ["-k", "12", "-w", "5", "-m", "40", "-p", "160", "-q", "160", "-l", "0"], [tf, qf])
     assert got == want
+
+
+@pytest.mark.parametrize("case", interval_cases(), ids=lambda c: c["name"])
+def test_interval_filter_and_regions_identical_to_reference(tmp_path, case):
+    """filter_redundant_coords per part and compute_reliable_region at the end, on the intervals of tests/test_intervals.py (its
+    docstring describes them): the oracle's restatement against the reference's own two functions"""
+    fn = str(tmp_path / (case["name"] + ".txt"))
+    write_interval_case(case, fn)
+    want = oracle_bind.ref_dump(["intervals", str(case["min_cov"]), fn])
+    assert want.count("\nR\t") and want.count("\nV\t")
+    assert oracle_bind.dump("intervals", [str(case["min_cov"])], [fn]) == want
 
 
 @pytest.mark.parametrize("name,flags", [("adv", ["-g", "300"]), ("adv", ["-s", "0"]), ("rr", ["-g", "300"]), ("rr", ["-s", "1"])], ids=lambda v: v if isinstance(v, str) else "".join(v))
