@@ -417,6 +417,30 @@ int lqfig_kde(int device, const float *data, uint64_t n, const double *points, u
  * order: what the gamma fit of the read lengths needs (mean and mean log).  n == 0: zeros.                                            */
 int lqfig_logsum(int device, const uint32_t *x, uint64_t n, uint64_t *sum, double *sum_log, uint64_t *n_zero,
                  char *errbuf, size_t errbuf_len);
+/* Box-plot statistics by group: what LongQC's grouped box plots compute before they draw (lq_mask.py:43-79, lq_coverage.py:438-529).
+ * A value is a printed "%.3f" number as an integer count of thousandths, thou[i]; its double is thou / 1000 (one IEEE division, which is
+ * float(text)); LQFIG_MISSING is "-nan".  The group of element i is key[i] when interval == 0, else floor((double)key[i] / interval), the
+ * IEEE division (np.floor(len / interval)).  sorted (n entries) gets the values group by group, the groups ascending, inside a group the
+ * non-missing values ascending and then the missing ones; boxes one entry per group that occurs, ascending in `group`: the group's
+ * place in sorted[], and matplotlib.cbook.boxplot_stats(x, whis) of its non-missing values x -- q1, med, q3 by np.percentile's linear
+ * rule, every operation rounded on its own; whishi the largest value <= q3 + whis (q3 - q1), or q3 if there is none or it lies below q3;
+ * whislo its mirror; the fliers the n_low values below whislo and the n_high values above whishi, at the two ends of the group's stretch.
+ * mid_lo / mid_hi: the two middle order statistics, for the median (a + b) / 2 of np.median and pandas.  A group without non-missing
+ * values has NaN statistics, LQFIG_MISSING as both middles and no fliers.  The sort is on integers: the same bytes from every call.
+ * n == 0: no boxes.  LQCOV_E_ARG: null buffers, interval or whis negative or not finite, box_cap smaller than the number of groups
+ * -- *n_boxes is written all the same, and the next call works; LQCOV_E_DOMAIN: n >= 2^32, a group of 2^32 or more, a value of
+ * INT32_MAX (its sort key is the missing value's).                                                                                      */
+typedef struct lqfig_box {
+	uint32_t group, reserved;
+	uint64_t first, n_all, n;      /* place of the group in sorted[], its members, its non-missing members */
+	int32_t  mid_lo, mid_hi;       /* the two middle order statistics, thousandths (equal for odd n) */
+	double   q1, med, q3, whislo, whishi;
+	uint64_t n_low, n_high;        /* fliers: sorted[first .. first+n_low) and sorted[first+n-n_high .. first+n) */
+} lqfig_box;
+#define LQFIG_MISSING INT32_MIN
+int lqfig_boxstats(int device, const uint32_t *key, const int32_t *thou, uint64_t n, double interval, double whis,
+                   int32_t *sorted, lqfig_box *boxes, uint32_t box_cap, uint32_t *n_boxes,
+                   char *errbuf, size_t errbuf_len);
 
 /* ---- one upload per chunk: the chunk loop of sampleqc (longQC.py:299-360) and the coverage call on the same device bytes ---------- */
 /* A resident chunk: lqchunk_load uploads the reads (ASCII, seq_off with n+1 ascending entries, qual NULL or parallel to seq as in
@@ -480,6 +504,11 @@ int lqsdust_format_lists(int device, uint32_t n, const char *names, const uint64
 /* printf's "%.3f" as the table's kernels and the host take it (lq_fmt3.hpp): -> the class (0 finite, 1 nan, 2 inf, 3 2^50 or more; + 4:
  * the sign bit), *thousandths: |x| rounded to 1/1000 exactly, ties to even.  No device needed. */
 uint32_t lqsdust_fmt3(double x, uint64_t *thousandths);
+/* The two "%.3f" columns of the table lqchunk_sdust_table made last, as the thousandths its text shows (n entries each; the rows whose
+ * meanQ the host took included: a row's numbers and its text never disagree): frac_thou[i] of masked/len, qv_thou[i] of meanQ, negative
+ * where the text has a sign ("-0.000" is 0).  "-nan" is UINT32_MAX / LQFIG_MISSING.  LQCOV_E_STATE: no table of the chunk loaded now and of
+ * its last scan (a lqchunk_sdust_table call that failed made none); LQCOV_E_DOMAIN: an infinite meanQ, or one of 2^31 - 1 thousandths or more. */
+int lqchunk_sdust_columns(lqchunk *c, uint32_t *frac_thou, int32_t *qv_thou);
 int lqchunk_adapt(lqchunk *c, const uint8_t *adp5, uint32_t len5, const uint8_t *adp3, uint32_t len3,
                   uint32_t length, int32_t *out5, int32_t *out3);
 int lqchunk_gc(lqchunk *c, uint32_t chunk_size, const uint32_t *k, const uint64_t *draw_off, const uint32_t *pos_in,

@@ -33,6 +33,7 @@ def _lib(lib=None):
             "lqchunk_sdust": (C.c_int, [H, C.c_int, C.c_int, P, P, P]),
             "lqchunk_sdust_split": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, P]),
             "lqchunk_sdust_table": (C.c_int, [H, C.c_char_p, P, P, C.c_uint64, P, P, P, C.c_uint64]),
+            "lqchunk_sdust_columns": (C.c_int, [H, P, P]),
             "lqchunk_sdust_intervals": (C.c_int, [H, C.c_int, C.c_int, C.c_uint32, P, P, P, C.c_size_t, P]),
             "lqchunk_adapt": (C.c_int, [H, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint32, P, P]),
             "lqchunk_gc": (C.c_int, [H, C.c_uint32, P, P, P, C.c_uint64, C.c_uint64, P, P, P, P]),
@@ -458,6 +459,13 @@ class ReadChunk:
         self._ck(self.lib.lqchunk_sdust_table(self.h, nb, noff.ctypes.data, out.ctypes.data, cap, C.byref(n_out), st, excl.ctypes.data, 2 * n))
         return out[:n_out.value].tobytes(), sdust.with_lists(sdust.stats_dict(st), excl)
 
+    def sdust_columns(self):
+        """The two "%.3f" columns of the table sdust_table / sdust_table_bytes made last, as the thousandths its text shows
+        (lqchunk_sdust_columns) -> (fraction: uint32, 0xffffffff for "-nan"; meanQ: int32, figdata.MISSING for "-nan")"""
+        frac, qv = np.zeros(max(self.n, 1), np.uint32), np.zeros(max(self.n, 1), np.int32)
+        self._ck(self.lib.lqchunk_sdust_columns(self.h, frac.ctypes.data, qv.ctypes.data))
+        return frac[:self.n], qv[:self.n]
+
     def sdust_intervals(self, w: int = 64, t: int = 20, piece: Optional[int] = None):
         """The masked intervals of the reads the pieces serve, what the reference's sdust() returns for them: lqchunk_sdust_intervals.
         -> (iv_off uint64[n + 1], iv uint64[k, 2]: (start, finish) of read i's intervals at iv[iv_off[i] : iv_off[i + 1]], ascending,
@@ -820,10 +828,14 @@ class SampleQCPass:
         """the mask's summary (LqMaskMI355X.summary): what longQC.py:369-371, 452-471 read back from the table"""
         return self.mask.summary()
 
-    def figures(self):
+    def figures(self, per_read=False):
         """the numbers behind the GC figure and the length figure of every chunk added (LqGCMI355X.figure_data,
-        LqMaskMI355X.length_figure_data): what longQC.py:449,487-488 compute before they draw"""
-        return {"gc": self.gc.figure_data(), "length": self.mask.length_figure_data()}
+        LqMaskMI355X.length_figure_data): what longQC.py:449,487-488 compute before they draw.  per_read: also "qscore" and "masked", the
+        QV box plot by length bin and the masked-fraction histogram of lq_mask.py:43-79 (qscore_figure_data, masked_fraction_data)"""
+        out = {"gc": self.gc.figure_data(), "length": self.mask.length_figure_data()}
+        if per_read:
+            out["qscore"], out["masked"] = self.mask.qscore_figure_data(), self.mask.masked_fraction_data()
+        return out
 
     def close(self):
         self.store.close()

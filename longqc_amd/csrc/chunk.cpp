@@ -23,7 +23,7 @@ void lq_chunk_set(lqchunk &c, u32 n, const u8 *seq, const u64 *seq_off, const u8
 	c.h_seq = seq ? seq + seq_off[0] : nullptr;
 	c.h_qual = qual ? qual + seq_off[0] : nullptr;
 	c.has_qual = qual != nullptr;
-	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false; c.cols_done = false;
 }
 
 void lq_chunk_ready(lqchunk &c)
@@ -101,7 +101,7 @@ static void gather_begin(lqchunk &c, const std::vector<u64> &off)
 	lq_cabi::select_device(c.device);
 	if (!c.stream) LQ_HIP_CHECK(hipStreamCreate(&c.stream));
 	const u32 n = (u32)(off.size() - 1);
-	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false;
+	c.resident = false; c.packed = false; c.n_chunks = 0; c.iv_valid = false; c.dust_done = false; c.cols_done = false;
 	c.n = n; c.first_desc = n; c.off = off; c.total = off[n]; c.h_seq = c.h_qual = nullptr; c.has_qual = true;
 	// the buffers of lq_chunk_ready; k_chunk_gather writes whole 16-byte words, zeros behind the last base
 	const u64 total = c.total, alloc = (total + LQ_CHUNK_SEQ_TILE - 1) / LQ_CHUNK_SEQ_TILE * LQ_CHUNK_SEQ_TILE + LQ_PACK_PAD;
@@ -254,6 +254,11 @@ int lqchunk_sdust_table(lqchunk *c, const char *names, const uint64_t *name_off,
 		catch (...) { if (stats) memcpy(stats, st, sizeof(st)); throw; }      // (a table that does not fit: its size and summary are known)
 		if (stats) memcpy(stats, st, sizeof(st));
 	});
+}
+
+int lqchunk_sdust_columns(lqchunk *c, uint32_t *frac_thou, int32_t *qv_thou)
+{
+	return chunk_guard(c, [&] { need_loaded(*c); lq_chunk_sdust_columns(*c, frac_thou, (i32*)qv_thou); });
 }
 
 int lqchunk_sdust_intervals(lqchunk *c, int W, int T, uint32_t piece, uint64_t *n_off, uint8_t *flagged, uint64_t *iv, size_t iv_cap, size_t *iv_need)

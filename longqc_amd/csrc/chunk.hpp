@@ -17,7 +17,7 @@ struct alignas(16) GatherSeg { u64 src, dst; };        // source byte, destinati
 
 // the low-complexity table as text (kernels_dust_table.hpp, dust.cpp): the names, the per-row tables, the lists and the text on the device
 struct LqDustTab {
-	DBuf names, noff, nlen, fthou, qthou, meta, rbytes, rec, unv, patch, ex1, ex2, st, text;
+	DBuf names, noff, nlen, fthou, qthou, meta, rbytes, rec, unv, patch, ex1, ex2, st, text, cfrac, cqv;
 	Prim prim;                                                // the scan of the rows' byte counts
 };
 
@@ -47,6 +47,7 @@ struct lqchunk {
 	DBuf fq_names, fq_noff, fq_be, fq_rec, fq_tile, fq_text;  // k_fastq_format's names and tables (writer.cpp), lqchunk_fastq's text
 	LqDustTab tb;                                             // lqchunk_sdust_table
 	bool dust_done = false;                                   // masked, psum and qv are a scan's of the reads loaded now
+	bool cols_done = false;                                   // tb.fthou, tb.qthou and tb.meta are the table's of that scan (lqchunk_sdust_columns)
 	std::vector<u64> h_coff;                                  // packed chunks before read i
 	u64 n_chunks = 0; bool packed = false;
 	~lqchunk()
@@ -79,6 +80,8 @@ void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, doub
 void lq_chunk_sdust_intervals(lqchunk &c, int W, int T, u32 piece);
 // the table of the last scan as text (dust.cpp); stats: LQSDUST_STATS_WORDS words; excl (may be null): the reads on LongQC's exclusion lists
 void lq_chunk_sdust_table(lqchunk &c, const char *names, const u64 *name_off, u8 *out, u64 out_cap, u64 *out_len, u64 *stats, u32 *excl, u64 excl_cap);
+// the two "%.3f" columns of that table as thousandths (n entries each; "-nan": 0xffffffff / INT32_MIN)
+void lq_chunk_sdust_columns(lqchunk &c, u32 *frac_thou, i32 *qv_thou);
 void lq_chunk_adapt(lqchunk &c, const u8 *adp5, u32 len5, const u8 *adp3, u32 len3, u32 length, i32 *out5, i32 *out3);
 void lq_chunk_gc(lqchunk &c, u32 chunk_size, const u32 *k, const u64 *draw_off, const u32 *pos_in, u64 seed, u64 first_read,
                  u32 *gc, u32 *pos_out, u16 *win_gc, u32 *kept);

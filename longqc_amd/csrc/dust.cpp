@@ -28,7 +28,7 @@ void lq_chunk_sdust(lqchunk &c, int W, int T, u32 *masked, double *psum, u32 *qv
 {
 	if (W < 3 || W > 66) throw std::domain_error("sdust window outside [3, 66] (the window ring holds 64 words; the reference's default is 64)");
 	const u32 n = c.n;
-	c.dust_done = false;
+	c.dust_done = false; c.cols_done = false;
 	if (n == 0) { c.dust_done = true; return; }
 	for (u32 i = 0; i < n; ++i) if (c.off[i + 1] - c.off[i] > 0x7fffffffULL) throw std::domain_error("read longer than 2^31-1 bases");
 	lq_chunk_ready(c);
@@ -122,7 +122,7 @@ void lq_chunk_sdust_split(lqchunk &c, int W, int T, u32 piece, u32 *masked, doub
 	piece = dust_piece(c, W, piece);
 	const u32 n = c.n;
 	if (n_serial) *n_serial = 0;
-	c.dust_done = false;
+	c.dust_done = false; c.cols_done = false;
 	if (n == 0) { c.dust_done = true; return; }
 	lq_chunk_ready(c);
 	if (!c.stream2) LQ_HIP_CHECK(hipStreamCreate(&c.stream2));
@@ -336,7 +336,33 @@ void lq_chunk_sdust_table(lqchunk &c, const char *names, const u64 *name_off, u8
 	if (!c.dust_done) throw std::logic_error("no scan of the chunk loaded now (lqchunk_sdust, lqchunk_sdust_split)");
 	lq_cabi::select_device(c.device);
 	const DustTabIn in = {c.n, c.masked.as<u32>(), nullptr, c.d_off.as<u64>(), c.psum.as<double>(), nullptr, c.has_qual ? c.qual.as<u8>() : (const u8*)nullptr, c.qv.as<u32>()};
+	c.cols_done = false;
 	dust_table(c.tb, c.stream, in, names, name_off, 0, out, out_cap, out_len, stats, excl, excl_cap);
+	c.cols_done = true;
+}
+
+void lq_chunk_sdust_columns(lqchunk &c, u32 *frac_thou, i32 *qv_thou)
+{
+	if (!c.dust_done || !c.cols_done) throw std::logic_error("no table of the chunk loaded now (lqchunk_sdust_table)");
+	const u32 n = c.n;
+	if (!n) return;
+	if (!frac_thou || !qv_thou) throw std::invalid_argument("null buffers");
+	lq_cabi::select_device(c.device);
+	LqDustTab &tb = c.tb;
+	tb.cfrac.ensure((size_t)n * 4); tb.cqv.ensure((size_t)n * 4);
+	try {
+		LQ_HIP_CHECK(hipMemsetAsync(tb.st.p, 0, 4, c.stream));
+		const u32 grid = (u32)std::min<u64>(((u64)n + LQ_DTAB_THREADS - 1) / LQ_DTAB_THREADS, LQ_DTAB_MAX_BLOCKS);
+		LQ_LAUNCH(k_sdust_columns, grid, LQ_DTAB_THREADS, c.stream, n, tb.fthou.as<u64>(), tb.qthou.as<u64>(), tb.meta.as<u32>(), tb.cfrac.as<u32>(), tb.cqv.as<i32>(),
+		          tb.st.as<u32>());
+		LQ_HIP_CHECK(hipGetLastError());
+		u32 bad = 0;
+		LQ_HIP_CHECK(hipMemcpyAsync(&bad, tb.st.p, 4, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(frac_thou, tb.cfrac.p, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipMemcpyAsync(qv_thou, tb.cqv.p, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
+		LQ_HIP_CHECK(hipStreamSynchronize(c.stream));
+		if (bad) throw std::domain_error("a column value that is infinite or does not fit 31 bits of thousandths");
+	} catch (...) { (void)hipStreamSynchronize(c.stream); throw; }
 }
 
 extern "C" {

@@ -100,6 +100,23 @@ k_sdust_patch(u32 k, const DustPatch *pt, u64 *qthou, u32 *meta, u32 *rbytes)
 	}
 }
 
+// the two fraction columns as the thousandths the text shows (lqchunk_sdust_columns), after k_sdust_patch: "-nan" as 0xffffffff /
+// INT32_MIN, the sign of the text on meanQ ("-0.000" is 0).  *bad |= 1 for a meanQ that is infinite or does not fit 31 bits
+__global__ void __launch_bounds__(LQ_DTAB_THREADS)
+k_sdust_columns(u32 n, const u64 *fthou, const u64 *qthou, const u32 *meta, u32 *frac, i32 *qv, u32 *bad)
+{
+	for (u64 i = (u64)blockIdx.x * LQ_DTAB_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * LQ_DTAB_THREADS) {
+		const u32 m = meta[i], fc = m & 0xfu, qc = m >> 4 & 0xfu;
+		const u64 ft = fthou[i], qt = qthou[i];
+		u32 f = 0xffffffffu; i32 q = (i32)0x80000000;
+		bool err = false;
+		if (LQ_F3_CLASS(fc) != LQ_F3_NAN) { err = LQ_F3_CLASS(fc) != LQ_F3_FINITE || ft >= 0xffffffffULL; f = (u32)ft; }
+		if (LQ_F3_CLASS(qc) != LQ_F3_NAN) { err = err || LQ_F3_CLASS(qc) != LQ_F3_FINITE || qt >= 0x7fffffffULL; q = qc & LQ_F3_NEG ? -(i32)qt : (i32)qt; }
+		if (err) atomicOr(bad, 1u);
+		frac[i] = f; qv[i] = q;
+	}
+}
+
 // rec[i]: the text byte at which row i starts.  names: row i's name at names[noff[i] .. noff[i] + nlen[i])
 __global__ void __launch_bounds__(LQ_DTAB_THREADS)
 k_sdust_text(u32 n, const u8 *names, const u64 *noff, const u32 *nlen, const u32 *masked, const u32 *len, const u64 *off, const u32 *q7,

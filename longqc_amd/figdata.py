@@ -33,6 +33,25 @@ def _lib(lib=None):
     return lib
 
 
+def _box_lib(lib=None):
+    """lqfig_boxstats bound on its own: a library that holds this call alone, or the four above alone, serves its callers"""
+    lib = lib or api.load_library()
+    if not getattr(lib, "_lqbox_bound", False):
+        lib.lqfig_boxstats.restype = C.c_int
+        lib.lqfig_boxstats.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_char_p, C.c_size_t]
+        lib._lqbox_bound = True
+    return lib
+
+
+MISSING = -2 ** 31                                                 # LQFIG_MISSING: a "-nan" among the thousandths
+# lqfig_box of include/lqcov.h
+BOX = np.dtype([("group", np.uint32), ("reserved", np.uint32), ("first", np.uint64), ("n_all", np.uint64), ("n", np.uint64),
+                ("mid_lo", np.int32), ("mid_hi", np.int32), ("q1", np.float64), ("med", np.float64), ("q3", np.float64),
+                ("whislo", np.float64), ("whishi", np.float64), ("n_low", np.uint64), ("n_high", np.uint64)])
+assert BOX.itemsize == 96
+
+
 def _values(x, want=None):
     """x as a contiguous 1-D float32 or uint32 array (an array('f') is read in place) -> (array, LQFIG_* code)"""
     a = np.frombuffer(x, dtype=np.float32) if not isinstance(x, np.ndarray) and getattr(x, "typecode", None) == "f" and len(x) else np.asarray(x)
@@ -128,6 +147,89 @@ def density_hist(x, start, stop, step, device: int = 0, lib=None):
     counts = hist(x, edges, device, lib)
     db = np.array(np.diff(edges), float)
     return edges, counts, counts / db / counts.sum()
+
+
+# ---- box-plot statistics by group ---------------------------------------------------------------------------------------
+BOX_CAP_FIRST = 65536                                              # boxes the first call has room for; more groups: one more call
+
+
+def _ints(x, dtype, what):
+    a = np.asarray(x)
+    if a.size == 0:
+        a = a.astype(dtype)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise TypeError("%s: a 1-D integer array is needed, not %s%s" % (what, a.dtype, list(a.shape)))
+    if a.dtype != dtype:
+        info = np.iinfo(dtype)
+        if a.size and (int(a.min()) < info.min or int(a.max()) > info.max):
+            raise ValueError("%s does not fit %s" % (what, np.dtype(dtype).name))
+        a = a.astype(dtype)
+    return np.ascontiguousarray(a)
+
+
+def box_stats_raw(key, thou, interval: float = 0.0, whis: float = 1.5, device: int = 0, lib=None, box_cap=None):
+    """lqfig_boxstats as it is: -> (sorted: the int32 thousandths group by group, inside a group ascending and the MISSING ones last;
+    boxes: a BOX record per group that occurs, ascending in group).  box_cap: room for the boxes, default as many as needed"""
+    k, t = _ints(key, np.uint32, "key"), _ints(thou, np.int32, "thou")
+    if k.shape != t.shape:
+        raise ValueError("one value per key")
+    lib, n = _box_lib(lib), k.size
+    out = np.empty(n, dtype=np.int32)
+    cap = min(n, BOX_CAP_FIRST) if box_cap is None else int(box_cap)
+    while True:
+        boxes, nb, err = np.zeros(cap, dtype=BOX), C.c_uint32(0), C.create_string_buffer(512)
+        rc = lib.lqfig_boxstats(device, _ptr(k), _ptr(t), n, float(interval), float(whis), _ptr(out), _ptr(boxes), cap, C.byref(nb), err, 512)
+        if rc == -1 and box_cap is None and nb.value > cap:            # (LQCOV_E_ARG with the number of groups: once more with room for them)
+            cap = nb.value
+            continue
+        _check(rc, err)
+        return out, boxes[:nb.value]
+
+
+def box_stats(key, thou, interval: float = 0.0, whis: float = 1.5, device: int = 0, lib=None) -> dict:
+    """matplotlib.cbook.boxplot_stats(x, whis) of every group's non-missing values, on the device (kernels_boxstats.hpp).  thou: the values as
+    printed "%.3f" numbers, integer thousandths (MISSING: "-nan"), their doubles thou / 1000; the group of element i is key[i], or with an
+    interval np.floor(key[i] / interval).  -> a dict of arrays with one entry per group that occurs, ascending in group: group, n_all
+    (members), n (non-missing members), q1, med, q3, whislo, whishi (np.percentile's linear rule; NaN for a group without values), median
+    (np.median's and pandas': the mean of the two middle values, which can differ from med in the last bit), and fliers, a list of arrays:
+    the values below whislo, then those above whishi, ascending"""
+    s, b = box_stats_raw(key, thou, interval, whis, device, lib)
+    out = {f: b[f].copy() for f in ("group", "n_all", "n", "q1", "med", "q3", "whislo", "whishi")}
+    some = b["n"] > 0
+    with np.errstate(invalid="ignore"):
+        out["median"] = np.where(some, (b["mid_lo"] / 1000.0 + b["mid_hi"] / 1000.0) / 2, np.nan)
+    out["fliers"] = [np.concatenate([s[f:f + lo], s[f + n - hi:f + n]]) / 1000.0
+                     for f, n, lo, hi in zip(b["first"].astype(np.int64).tolist(), b["n"].astype(np.int64).tolist(), b["n_low"].astype(np.int64).tolist(), b["n_high"].astype(np.int64).tolist())]
+    return out
+
+
+_MASKED_EDGES = np.arange(0, 1.0, 0.01)                            # lq_mask.py:70
+
+
+
+def masked_bin_table() -> np.ndarray:
+    """the bin of each printed fraction k / 1000, k = 0 .. 1000, among np.arange(0, 1.0, 0.01), by numpy's own comparisons (np.histogram
+    places a value with searchsorted on the edge array; the last bin is closed); 99: counted nowhere (above the last edge, 0.99).  No bin
+    arithmetic: the edges are not k / 100 (edge 57 is 0.5700000000000001, so a printed 0.570 lies in the bin below)"""
+    v = np.arange(1001) / 1000
+    b = np.searchsorted(_MASKED_EDGES, v, side="right") - 1
+    b[v == _MASKED_EDGES[-1]] = _MASKED_EDGES.size - 2
+    b[v > _MASKED_EDGES[-1]] = 99
+    return b.astype(np.int64)
+
+
+_MASKED_BIN = masked_bin_table()
+
+
+def masked_fraction_hist(frac_thou, device: int = 0, lib=None):
+    """np.histogram(fractions, bins=np.arange(0, 1.0, 0.01)) of the masked-fraction figure (lq_mask.py:70) from the printed fractions as
+    uint32 thousandths (0xffffffff: "-nan", counted nowhere) -> (edges, counts).  The device counts the 1001 possible values (lqfig_hist
+    with the unit edges 0 .. 1001); masked_bin_table folds them into the figure's 99 bins"""
+    a, _ = _values(frac_thou, U32)
+    per_value = hist(a, np.arange(1002, dtype=np.float64), device, lib)
+    counts = np.zeros(100, dtype=np.int64)
+    np.add.at(counts, _MASKED_BIN, per_value)
+    return _MASKED_EDGES.copy(), counts[:99]
 
 
 # ---- the gamma fit ------------------------------------------------------------------------------------------------------

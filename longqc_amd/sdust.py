@@ -194,7 +194,8 @@ class LqMaskMI355X:
     chunk_n) per chunk, close_pool() at the end, get_outfile_path() -> analysis table `longqc_sdust<suffix>.txt` with one
     row per read in submission order.  Reads are LongQC's [name, seq, qual, ...] records (str or bytes); no temporary
     FASTQ files, no process pool: every chunk is one call into the device.  Nothing is plotted: length_figure_data() gives the numbers of
-    the length figure (histogram, gamma fit); the masked-fraction histogram and the QV box plot of lq_mask.py:43-79 are not built.
+    the length figure (histogram, gamma fit), masked_fraction_data() and qscore_figure_data() those of the masked-fraction histogram and of
+    the QV box plot by length bin (lq_mask.py:43-79), from the two "%.3f" columns kept per chunk as the thousandths the file shows.
     table (table_mode's) "device": a chunk's rows are formatted on the device and kept as bytes (ReadChunk.sdust_table); the file is the
     same.  summary() and json_block() give what longQC.py:369-371, 452-471, 495-502 read back from the file, from arrays kept at submit
     time in either mode."""
@@ -209,6 +210,7 @@ class LqMaskMI355X:
         self.outf = os.path.join(work_dir, "longqc_sdust" + self.suffix + ".txt")
         self._chunks = {}
         self._lens, self._excl = {}, {}                        # per chunk: the lengths; the names on the two exclusion lists
+        self._cols = {}                                        # per chunk: the printed fraction and meanQ as thousandths (columns_of_rows)
         self._masked = self._q7 = 0
 
     @staticmethod
@@ -231,7 +233,7 @@ class LqMaskMI355X:
                 text, st = chunk.sdust_table(split=self.split)
                 self._chunks[chunk_n] = text
                 self._note(chunk_n, chunk.lens, st["masked"], st["q7"], [chunk.names[i] for i in st["exclude_first"]],
-                           [chunk.names[i] for i in st["exclude_second"]])
+                           [chunk.names[i] for i in st["exclude_second"]], *chunk.sdust_columns())
             finally:
                 if own:
                     chunk.close()
@@ -246,10 +248,15 @@ class LqMaskMI355X:
         self._chunks[chunk_n] = _rows(names, n, off, qflat, masked, psum, qv)
         lens = np.diff(np.asarray(off).astype(np.int64))
         first, second = exclusion_lists(masked[:n], lens)
-        self._note(chunk_n, lens, int(masked[:n].sum(dtype=np.uint64)), int(qv[:n].sum(dtype=np.uint64)), [names[i] for i in first], [names[i] for i in second])
+        self._note(chunk_n, lens, int(masked[:n].sum(dtype=np.uint64)), int(qv[:n].sum(dtype=np.uint64)), [names[i] for i in first], [names[i] for i in second],
+                   *columns_of_rows(self._chunks[chunk_n]))
 
-    def _note(self, chunk_n, lens, masked, q7, first, second):
+    def _note(self, chunk_n, lens, masked, q7, first, second, frac_thou=None, qv_thou=None):
+        """frac_thou, qv_thou: the chunk's two printed columns; None: not kept, every read counts as "-nan" in the per-read figures"""
         self._lens[chunk_n] = np.array(lens, dtype=np.int64)
+        n = self._lens[chunk_n].shape[0]
+        self._cols[chunk_n] = (np.array(frac_thou, dtype=np.uint32) if frac_thou is not None else np.full(n, 0xffffffff, np.uint32),
+                               np.array(qv_thou, dtype=np.int32) if qv_thou is not None else np.full(n, -2 ** 31, np.int32))
         self._excl[chunk_n] = (first, second)
         self._masked += int(masked)
         self._q7 += int(q7)
@@ -310,6 +317,44 @@ class LqMaskMI355X:
         return {"hist": figdata.density_hist(u, int(lo), s["longest"] + b_width, b_width, self.device, self.lib),
                 "gamma_params": figdata.gamma_fit(n, total, sum_log), "mean_length": s["mean_length"], "n50": s["n50"], "longest": s["longest"]}
 
+    def columns(self):
+        """-> (lengths int64, printed fractions as uint32 thousandths, printed meanQ as int32 thousandths) of every chunk submitted so far,
+        in file order: what pandas reads from columns 2, 3 and 4 of the file, times 1000; "-nan" is 0xffffffff / figdata.MISSING"""
+        if not self._lens:
+            return np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.int32)
+        return (np.concatenate([self._lens[k] for k in self._lens]), np.concatenate([self._cols[k][0] for k in self._cols]),
+                np.concatenate([self._cols[k][1] for k in self._cols]))
+
+    def qscore_figure_data(self, interval=None, platform="ont") -> dict:
+        """What lq_mask.py:43-68 computes for the QV box plot by length bin, on the device (figdata.box_stats), every chunk submitted so
+        far: the reads are binned by np.floor(length / interval), interval 3000 or n50 / 2 where n50 < 3000 (longQC.py:478-481) unless the
+        caller names one, and each bin's printed meanQ values get matplotlib's box (whis 1.5; a read without qualities is left out, as pandas
+        drops its NaN).  -> box_stats' dict and "interval", "mid_threshold" (7 for ont, else 8: lq_mask.py:44-47).  ValueError for no reads"""
+        from . import figdata
+        lens, _, qv = self.columns()
+        if lens.shape[0] == 0:
+            raise ValueError("no reads submitted")
+        if int(lens.max()) >= 1 << 32:
+            raise ValueError("a read of 2^32 bases or more")
+        if interval is None:
+            n50 = self.summary()["n50"]
+            interval = 3000 if n50 >= 3000 else n50 / 2
+        if not interval > 0:
+            raise ValueError("the length interval must be positive, not %r" % (interval,))
+        out = figdata.box_stats(lens.astype(np.uint32), qv, float(interval), 1.5, self.device, self.lib)
+        out["interval"], out["mid_threshold"] = interval, 7 if platform == "ont" else 8
+        return out
+
+    def masked_fraction_data(self):
+        """What lq_mask.py:70 computes for the masked-fraction figure, on the device: (edges, counts) of np.histogram(fractions,
+        bins=np.arange(0, 1.0, 0.01)) on the printed fractions of every chunk submitted so far (figdata.masked_fraction_hist).  A read of
+        length 0 ("-nan") and a fraction printed above 0.990 are counted nowhere, as there.  ValueError for no reads"""
+        from . import figdata
+        _, frac, _ = self.columns()
+        if frac.shape[0] == 0:
+            raise ValueError("no reads submitted")
+        return figdata.masked_fraction_hist(frac, self.device, self.lib)
+
     def json_block(self, with_gamma=False):
         """the entries of longQC.py:495-502 that come from the table; with_gamma: Length_stats also holds "gamma_params": [a, scale], the
         fit of longQC.py:487,500 (length_figure_data, figdata.gamma_fit), in the reference's place"""
@@ -322,6 +367,26 @@ class LqMaskMI355X:
             stats = {"gamma_params": [float(a), float(scale)], **stats}
         return {"Yield": s["yield"], "Q7 bases": "%.2f%%" % float(100 * s["q7_bases"] / s["yield"]), "Longest_read": s["longest"],
                 "Num_of_reads": s["n_reads"], "Length_stats": stats}
+
+
+def thou_of_text(t: str):
+    """a "%.3f" field -> its thousandths as an int ("-0.000" is 0), None for "-nan" / "nan"; an infinite value raises ValueError"""
+    if t.endswith("nan"):
+        return None
+    if t[-4:-3] != ".":
+        raise ValueError("not a %%.3f number: %r" % (t,))
+    return int(t[:-4] + t[-3:])
+
+
+def columns_of_rows(rows):
+    """the table's rows (sdust._rows') -> (fractions uint32, meanQ int32): the thousandths their two "%.3f" fields show; "-nan" is
+    0xffffffff / figdata.MISSING -- lqchunk_sdust_columns' arrays"""
+    frac, qv = np.zeros(len(rows), np.uint32), np.zeros(len(rows), np.int32)
+    for i, row in enumerate(rows):
+        f, q = (thou_of_text(t) for t in row.rsplit("\t", 3)[1:3])
+        frac[i] = 0xffffffff if f is None else f
+        qv[i] = -2 ** 31 if q is None else q
+    return frac, qv
 
 
 def _printed_above(thou: int) -> float:
