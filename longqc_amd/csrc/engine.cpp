@@ -1166,7 +1166,7 @@ void lqcov_handle::map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, 
 		L.prune = tie_mode == 2 && !sink; L.prune_n_want = n_want; L.prune_n_sub = ns;
 		struct PruneGuard { MapLane &L; ~PruneGuard() { L.prune = false; } } prune_guard{L};
 		sort_checked(L, sort_geom(pt), L.sub_off.as<u64>(), L.sub_klib.as<u32>(), ns, 0, nA2, so, sk, tie_mode == 2 ? 2u : 0u, sq.data());
-		if (lq_timeline) { LQ_HIP_CHECK(hipStreamSynchronize(L.stream)); int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_; lq_tl("lane", lane_id, "  second pass sorted"); }
+		if (lq_timeline) { LQ_HIP_CHECK(hipStreamSynchronize(L.stream)); lq_tl("lane", L.id, "  second pass sorted"); }
 		chain_stage(L, pt, L.sub_off.as<u64>(), 0, ns, 0, L.sub_q.as<u32>(), nA2, tie_mode, n_want, ivl_cap, dbg, sink);
 	}
 }
@@ -1178,7 +1178,7 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	L.drop_arena_buffers();
 	lq_arena = L.arena.base ? &L.arena : nullptr;
 	struct ArenaGuard { ~ArenaGuard() { lq_arena = nullptr; } } arena_guard;
-	int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_;
+	const int lane_id = L.id;
 	lq_tl("lane", lane_id, "batch begins, queries", (double)(q1 - q0));
 	L.gate_passed = false;
 	struct GateGuard { lqcov_handle *h; MapLane &L; ~GateGuard() { if (!L.gate_passed) { L.gate_passed = true; h->open_gate(); } } } gate_guard{this, L};
@@ -1413,11 +1413,6 @@ void lqcov_handle::psort_tail(MapLane &L, int set, hipStream_t s, u64 nA, const 
 	throw std::logic_error("parallel sort: segments above the LDS capacity left after 84 passes");
 }
 
-// Sort every query's anchors by x, in klib's order wherever that order can be told apart (lqmap.c:238).
-//   * queries without repeated (hash, strand) minimizers hold no equal x: the parallel sort, on the lane's second stream;
-//   * the others (their anchors are in B, the originals) go through klib's passes byte by byte as 8-byte records
-//     (kernels_sort.hpp, kernels_rsort.hpp); buckets of a pass that received fewer than two marked anchors leave for the
-//     parallel sort as well (set 1, after the last pass), the others are written to A when they are finished.
 SortGeom lqcov_handle::sort_geom(const Part &pt)
 {
 	SortGeom g; g.n_targets = pt.rs.n;
@@ -1425,27 +1420,14 @@ SortGeom lqcov_handle::sort_geom(const Part &pt)
 	return g;
 }
 
-void lqcov_handle::sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA)
+KeyMap SortGeom::key_map() const { KeyMap km; km.pbits = pbits(); km.rbits = rbits(); return km; }
+
+// The batch's lists, sized before anything is launched: the counters, both sets of parallel-sort lists with the scratch of their passes,
+// klib's two sub-array lists and the records R0.  Capacities: a segment in any list has more than 64 elements.
+static void sort_list_buffers(MapLane &L, u32 ps_shift, u32 nqb, u64 nA)
 {
-	mm128 *dA = L.A.as<mm128>(), *dB = L.B.as<mm128>();
-	hipStream_t sD = L.stream, sC = L.stream2;
-	if (nA >= 0x7ffffff0ULL) throw std::domain_error("more than 2^31 anchors in one query batch");
-	// varying key bits of this part: x = strand:1 | rid:31 | position:32 (lqmap.c:190-196)
-	const u32 max_len = g.max_len, n_targets = g.n_targets;
-	KeyMap km; km.pbits = 1; km.rbits = 0;
-	while (km.pbits < 32 && ((u64)1 << km.pbits) < (u64)max_len) ++km.pbits;
-	while (km.rbits < 31 && ((u64)1 << km.rbits) < (u64)n_targets) ++km.rbits;
-	u32 const_levels = 0;                                    // key bytes that are zero in every anchor of this part
-	if (!K.no_level_skip) {
-		if (n_targets <= (1u << 16)) const_levels |= 1u << 6;
-		if (n_targets <= (1u << 8)) const_levels |= 1u << 5;
-		if (max_len <= (1u << 24)) const_levels |= 1u << 3;
-		if (max_len <= (1u << 16)) const_levels |= 1u << 2;
-		if (max_len <= (1u << 8)) const_levels |= 1u << 1;
-	}
-	// list capacities: a segment in any list has more than 64 elements
 	const u64 max_segs = nA / (LQ_RS_MIN + 1) + nqb + 1;
-	const u64 cap_big = nA / ((LQ_PS_FIN_BIG >> K.ps_shift) + 1) + nqb + 16;
+	const u64 cap_big = nA / ((LQ_PS_FIN_BIG >> ps_shift) + 1) + nqb + 16;
 	L.sort_cnt.ensure(LQ_C_N * 4);
 	for (int set = 0; set < 2; ++set) {
 		PsWork &W = L.ps[set];
@@ -1459,19 +1441,290 @@ void lqcov_handle::sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 
 		W.tmap.ensure((nA / LQ_PS_TILE + W.big[0].cap / sizeof(PSeg) + 2) * 4);   // (a segment's last tile may be partial)
 	}
 	L.segs0.ensure(max_segs * sizeof(SortSeg)); L.segs1.ensure(max_segs * sizeof(SortSeg));
-	dzero(L.sort_cnt.p, LQ_C_N * 4, sD);
-	auto lists = [&](int set) { return ps_lists(L, set, K.ps_shift); };
-	u32 *cnt = L.sort_cnt.as<u32>();
-	// records: R0 of its own, R1 in the part of the scratch area that is only used after the sort (map_batch)
-	const u64 nA4 = ((nA + 1) * 4 + 15) & ~(u64)15;
 	L.R0.ensure((nA + 1) * sizeof(RRec));
-	RRec *R[2] = { L.R0.as<RRec>(), (RRec*)((u8*)L.scr.p + 3 * nA4) };
-	PsData pd; pd.A = dA; pd.B = dB; pd.R[0] = R[0]; pd.R[1] = R[1];
-	WalkCaps wcaps; wcaps.c[0] = 4096; wcaps.c[1] = 16384; wcaps.c[2] = 65536; wcaps.c[3] = 159744;
-	for (int c = 0; c < 4; ++c) wcaps.c[c] >>= K.walk_shift;   // test knob
+}
+
+// ---- klib's passes over the queries with repeated minimizers: the level loop of sort_batch, step by step ----
+// What the batch fixes for its levels (first two lines), and what kl_advance steps from one level to the next.
+struct KlibLevels {
+	u64 nA; u32 tile; WalkCaps wcaps; u32 *cnt;   // tile: anchors per tile of the streaming kernels; cnt: the lane's counters (L.sort_cnt)
+	RRec *R[2]; u32 *hx, *py;             // the two record arrays; the two-bucket passes' position lists (both in the lane's scratch area)
+	SortSeg *cur, *nxt; u32 cur_slot, nxt_slot;   // the level's sub-arrays and the ones it makes; where cnt holds how many there are
+	u32 ns, shift, rb; int level;         // ns: sub-arrays of the level, as the host read it; rb: the record array the level reads
+};
+
+// What the host decides about a level before its first launch.
+struct LevelPlan {
+	u32 g_seg, g_tile; u64 max_tiles;     // grids by sub-array and by tile; bound of the level's tile list
+	u32 max_digit;                        // SortGeom::max_digit of the level's byte
+	u32 lenc[LQ_WALK_CLASSES];            // sub-arrays per walk size class (upper bounds)
+	bool any_walk, ck_small, ck3;         // the byte can take more than two values; the few-bucket solver family; the 65-160 k class is checkpointed too
+	bool ck_walks, whole_walks;           // the first / second walker stream gets work
+	u64 n_ck_segs; int first_plain_class; // sub-arrays walked in pieces; the longest class that is walked whole
+	u32 ck_unit, ck_quantum, ck_min_len, per_ck;
+	u64 cks_max, ck_max, tiles_max;       // bounds: checkpointed sub-arrays, checkpoints, prefix tiles
+};
+
+// Fills the plan from the geometry, the level's byte, the counters as the host last saw them (hl) and the knobs.  No HIP call; the only
+// place that reads the knobs for these choices.
+static LevelPlan level_plan(const SortGeom &g, u32 shift, u32 ns, u64 nA, const u32 *hl, const Knobs &K, const WalkCaps &wcaps, u32 tile)
+{
+	LevelPlan P;
+	P.g_seg = std::min<u32>(ns, 1u << 18);
+	// tiles of the level's sub-arrays for the two streaming kernels
+	P.max_tiles = nA / tile + ns + 1;
+	P.g_tile = ((u32)std::min<u64>(P.max_tiles, K.tile_grid) + 7) & ~7u;   // a multiple of the XCD count (LQ_TILE_LOOP); blocks stride over the device-side tile list
+	// the largest digit of this level decides how many register groups the long walker needs
+	P.max_digit = g.max_digit(shift);
+	// What the host knows of this level's sub-arrays: how many there are of every walk size class (counted by length when they
+	// were made: an upper bound of the class lists, which hold the general passes only), and whether the level's byte can take
+	// more than two values at all (byte 7 is strand << 7 | rid >> 24: two buckets below 2^24 targets -- no walk, ever).
+	// Launches of empty classes are skipped, the others sized by the bound: a grid sized for the worst case has every block
+	// placed, LDS included, only to find its list empty, and a level has up to ten such launches on its critical path.
+	for (int c = 0; c < LQ_WALK_CLASSES; ++c) P.lenc[c] = hl[LQ_C_LEN0 + c];
+	P.any_walk = g.max_buckets(shift) > 2 || K.no_level_skip;
+	P.ck_small = K.reg_walker && P.max_digit < LQ_CK_B;
+	P.ck3 = P.ck_small || K.ckpt3;                            // (round 6: on by default for passes with many buckets too -- their states are found by sub-chains side by side, a 65-160 k walk took 8-21 ms whole)
+	P.n_ck_segs = K.ckpt ? (u64)(P.ck3 ? P.lenc[3] : 0) + P.lenc[4] : 0;
+	P.first_plain_class = K.ckpt ? (P.ck3 ? 2 : 3) : LQ_WALK_CLASSES - 1;
+	P.ck_unit = std::max<u32>((P.ck_small ? LQ_CK_UNIT : LQ_CK_UNIT_MANY) >> K.walk_shift, 8);
+	P.ck_quantum = P.ck_small ? 1u : (u32)LQ_CKM_Q;           // many buckets: checkpoints come in sub-chains of LQ_CKM_Q (k_ck_chain256)
+	P.ck_min_len = wcaps.c[P.ck3 ? 2 : 3] + 1;
+	P.cks_max = std::min<u64>(std::min<u64>(nA / P.ck_min_len + 1, ns), P.n_ck_segs);
+	P.ck_max = nA / P.ck_unit + (2 + P.ck_quantum) * P.cks_max;
+	P.tiles_max = nA / LQ_CK_TILE + P.cks_max;
+	P.per_ck = P.ck_small ? LQ_CK_B : 256;                    // cursors per checkpoint
+	P.ck_walks = P.any_walk && P.n_ck_segs;
+	P.whole_walks = false;
+	for (int c = 0; c <= P.first_plain_class; ++c) if (P.any_walk && P.lenc[c]) P.whole_walks = true;
+	return P;
+}
+
+// Level buffers: everything the level's kernels use on any of its three streams is sized here, before the level's first launch, the
+// checkpoint buffers included.  The rule: nothing the walker streams use may be allocated on the lane's stream after ev_w0 is recorded --
+// a block that the lane's stream allocates after the event the walker streams wait for would not be ordered before their kernels.
+static void kl_buffers(MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	const u64 ns = S.ns;
+	L.hist.ensure(ns * 1024); L.begs.ensure(ns * 1024); L.mhist.ensure(ns * 1024);
+	L.seg_info.ensure(ns * sizeof(SegInfo)); L.walk_list.ensure(ns * 4 * LQ_WALK_CLASSES); L.two_list.ensure(ns * 4);
+	L.tile_list.ensure(P.max_tiles * sizeof(SortTile));
+	L.two_tiles.ensure(P.max_tiles * sizeof(SortTile)); L.two_tile0.ensure(ns * 4); L.two_tcnt.ensure(P.max_tiles * 8); L.two_m.ensure(ns * 4);
+	if (P.ck_walks) {
+		L.ck_segs.ensure(P.cks_max * sizeof(CkSeg)); L.ck_S.ensure(P.ck_max * P.per_ck * 4); L.ck_slot.ensure(P.ck_max * 4 + 4);
+		if (P.ck_small) { L.ck_T.ensure((P.tiles_max + 1) * LQ_CK_B * 4); L.ck_E.ensure(P.cks_max * LQ_CK_B * LQ_CK_B * 4); }
+	}
+}
+
+// Tiles, digit histogram, classify: on the lane's stream.  Reads the level's sub-arrays (cur) and the records of R[rb] -- at the first level
+// the anchors in B, whose records it makes; writes the tile list, every element's digit (sort_d), the histograms and bucket starts per
+// sub-array, the kind of pass each gets (seg_info) and the lists of the two-bucket sub-arrays and of every walk size class.
+static void kl_digits(lqcov_handle *h, MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	hipStream_t sD = L.stream;
+	u32 *cnt = S.cnt;
+	// (the counters of the level -- next list, two-bucket and walk class lists, two-bucket tiles -- are zeroed by k_sort_tiles, the
+	// tile counter by the k_rs_children of the level before or the batch's memset: no memset dispatches inside the level loop)
+	LQ_LAUNCH(k_sort_tiles, std::min<u32>(S.ns / 256 + 1, 4096), 256, sD, S.cur, cnt + S.cur_slot, S.tile, L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, L.hist.as<u32>(), L.mhist.as<u32>(),
+	          cnt + S.nxt_slot, cnt + LQ_C_TWO, (u32)(1 + LQ_WALK_CLASSES), cnt + LQ_C_TWO_TILES, cnt + LQ_C_LEN0, (u32)LQ_WALK_CLASSES);
+	check_launch();
+	{	// the first level's kernel differs in its template argument, its stage name and its tally's slot (the name stays literal: LQ_LAUNCH prints it)
+		const bool first = S.level == 0;
+		StageTimer t(h, sD, first ? "k_rs_hist<first>" : "k_rs_hist");
+#define LQ_RS_HIST(FIRST, SLOT) LQ_LAUNCH((k_rs_hist<FIRST>), P.g_tile, 256, sD, S.cur, L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, S.tile, 1, L.B.as<mm128>(), S.R[S.rb], \
+		L.sort_d.as<u8>(), L.hist.as<u32>(), L.mhist.as<u32>(), (unsigned long long*)(cnt + SLOT))
+		if (first) LQ_RS_HIST(true, LQ_C_HIST0); else LQ_RS_HIST(false, LQ_C_HIST);
+#undef LQ_RS_HIST
+		check_launch();
+	}
+	LQ_LAUNCH(k_sort_classify, P.g_seg, LQ_CLASSIFY_THREADS, sD, S.cur, cnt + S.cur_slot, S.ns, L.hist.as<u32>(), L.begs.as<u32>(), L.seg_info.as<SegInfo>(),
+	          L.walk_list.as<u32>(), L.two_list.as<u32>(), cnt + LQ_C_TWO, cnt + LQ_C_WALK0, S.wcaps);
+	check_launch();
+}
+
+// Closed-form two-bucket passes (the strand bit at the top level), over tiles, on the lane's stream: count the X / Y elements of every
+// tile, scan per sub-array, position lists, then destinations + the move of the records.  Reads the two-bucket list, the digits and
+// R[rb]; writes their records to R[rb ^ 1].
+static void kl_two(lqcov_handle *h, MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	hipStream_t sD = L.stream;
+	StageTimer t(h, sD, "k_sort_two");
+	const SortSeg *cur = S.cur;
+	const u32 tile = S.tile, ns = S.ns;
+	u32 *cnt = S.cnt, *hx = S.hx, *py = S.py;
+	const SortTile *tt = L.two_tiles.as<SortTile>();
+	const u32 *ntt = cnt + LQ_C_TWO_TILES;
+	const u32 g_two = std::min<u32>(P.g_tile, 2048);         // grid-stride: a level without two-bucket sub-arrays costs near-empty launches
+	const u64 *rc = (const u64*)S.R[S.rb]; u64 *rn = (u64*)S.R[S.rb ^ 1];
+	LQ_LAUNCH(k_two_tiles, std::min<u32>(ns / 256 + 1, 4096), 256, sD, cur, L.two_list.as<u32>(), cnt + LQ_C_TWO, tile, L.two_tiles.as<SortTile>(), cnt + LQ_C_TWO_TILES, L.two_tile0.as<u32>()); check_launch();
+	LQ_LAUNCH((k_sort_two_tiled<0>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
+	LQ_LAUNCH(k_sort_two_scan, std::min<u32>(ns, 16384), 64, sD, cur, L.two_list.as<u32>(), cnt + LQ_C_TWO, tile, L.two_tile0.as<u32>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>()); check_launch();
+	LQ_LAUNCH((k_sort_two_tiled<1>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
+	LQ_LAUNCH((k_sort_two_tiled<2>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
+}
+
+// LQCOV_DEBUG_SORT: the level's counters as the device has them now (one more round trip on the lane's stream)
+static void kl_debug_line(MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	u32 hc[LQ_C_N]; d2h(hc, S.cnt, LQ_C_N, L.stream);
+	fprintf(stderr, "[sort] level %d shift %u max_digit %u ns %u two %u walk %u %u %u %u %u nA %llu\n", S.level, S.shift, P.max_digit, S.ns, hc[LQ_C_TWO],
+	        hc[LQ_C_WALK0], hc[LQ_C_WALK1], hc[LQ_C_WALK2], hc[LQ_C_WALK3], hc[LQ_C_WALK4], (unsigned long long)S.nA);
+	fflush(stderr);
+}
+
+// Checkpointed walks, on streamW.  Long sub-arrays: the walk's state at evenly spread checkpoints is computed without walking
+// (kernels_ckpt.hpp) and one walker per checkpoint runs a short piece.  Few buckets (the byte of rid above 65536 targets: the
+// (query, strand) arrays of the longest queries, millions of anchors each): states from prefix counts; up to 256 buckets: bulk-follow
+// solver, longest size class only (finding the states costs about as much as walking 50-100 k elements there).
+// The plan (which sub-arrays, their tiles and checkpoints) is laid out on the device from the class lists.
+// Reads the digits, histograms, bucket starts and class lists; writes the checkpoint buffers and the destinations (sort_dst).
+static void kl_ck_walks(lqcov_handle *h, MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	hipStream_t sW = L.streamW;
+	const SortSeg *cur = S.cur;
+	const u8 *dD = L.sort_d.as<u8>(); const u32 *dH = L.hist.as<u32>(), *dBg = L.begs.as<u32>(); u32 *dDst = L.sort_dst.as<u32>();
+	const u32 wgrid = LQ_WALK_GRID;
+	const CkSeg *dck = L.ck_segs.as<CkSeg>();
+	const u32 *ckn = L.ck_n.as<u32>();
+	LQ_LAUNCH(k_ck_plan, 1, 256, sW, cur, L.walk_list.as<u32>(), S.ns, S.cnt + LQ_C_WALK0, (int)P.ck3, P.ck_unit, P.ck_small ? 512u : 256u, P.ck_quantum, L.ck_segs.as<CkSeg>(), (u32)P.cks_max, L.ck_n.as<u32>()); check_launch();
+	const u32 g_ck = (u32)std::min<u64>(P.ck_max, wgrid), g_cks = (u32)std::min<u64>(P.cks_max, wgrid);
+	if (P.ck_small) {
+		{
+			StageTimer t(h, sW, "k_ck_prefix");
+			LQ_LAUNCH(k_ck_tilehist, (u32)std::min<u64>(P.tiles_max, 1u << 16), 256, sW, dck, ckn, cur, dD, L.ck_T.as<u32>()); check_launch();
+			LQ_LAUNCH(k_ck_tilescan, std::min<u32>(g_cks, 8192), 256, sW, dck, ckn, cur, L.ck_T.as<u32>()); check_launch();
+		}
+		{
+			StageTimer t(h, sW, "k_ck_solve");
+			LQ_LAUNCH(k_ck_phases, (u32)std::min<u64>(P.cks_max * LQ_CK_B, 1u << 16), 64, sW, dck, ckn, cur, dD, dH, dBg, L.ck_T.as<u32>(), L.ck_E.as<u32>()); check_launch();
+			LQ_LAUNCH(k_ck_solve, g_ck, 64, sW, dck, ckn, cur, dD, dH, dBg, L.ck_T.as<u32>(), L.ck_E.as<u32>(), L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
+		}
+		{
+			StageTimer t(h, sW, "k_sort_walk_reg<1>ck");
+			LQ_LAUNCH((k_sort_walk_reg<1>), g_ck, 64, sW, cur, (const u32*)nullptr, ckn, dD, dH, dBg, dDst, dck, ckn, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
+		}
+	} else {
+		{
+			StageTimer t(h, sW, "k_ck_chain256");
+			LQ_LAUNCH(k_ck_chain256, (u32)std::min<u64>(P.ck_max / LQ_CKM_Q + 1, wgrid), LQ_CKM_THREADS, sW, dck, ckn, cur, dD, dH, dBg, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
+		}
+		{
+			StageTimer t(h, sW, "k_sort_walk_solo_ck");
+			LQ_LAUNCH(k_sort_walk_solo, g_ck, 64, sW, cur, (const u32*)nullptr, ckn, dD, dH, dBg, dDst, dck, ckn, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
+		}
+	}
+}
+
+// Whole walks, on streamW2, longest class first: they outlast everything else of the level on a handful of CUs.  Then the two classes
+// that fit the LDS.  Reads what the checkpointed walks read, of other sub-arrays; writes their destinations (sort_dst).
+// The long walker: register lanes with as many register groups as the level's largest digit needs (64 buckets a group), the solo
+// walker beyond two groups or with LQCOV_WALK=solo -- one argument list, the kernel and its stage name chosen by `groups`.
+static void kl_whole_walks(lqcov_handle *h, MapLane &L, const KlibLevels &S, const LevelPlan &P)
+{
+	hipStream_t sW2 = L.streamW2;
+	const SortSeg *cur = S.cur;
+	const u8 *dD = L.sort_d.as<u8>(); const u32 *dH = L.hist.as<u32>(), *dBg = L.begs.as<u32>(), *wl = L.walk_list.as<u32>(); u32 *dDst = L.sort_dst.as<u32>(), *cnt = S.cnt;
+	const u32 wgrid = LQ_WALK_GRID, ns = S.ns;
+	const int groups = !h->K.reg_walker || P.max_digit >= 128 ? 0 : P.max_digit < 64 ? 1 : 2;
+	for (int c = P.first_plain_class; c >= 2; --c) {
+		if (!P.lenc[c]) continue;
+		const u32 g = std::min<u32>(P.lenc[c], std::min<u32>(8192, wgrid));
+		StageTimer t(h, sW2, groups == 1 ? "k_sort_walk_reg<1>" : groups == 2 ? "k_sort_walk_reg<2>" : "k_sort_walk_solo");
+#define LQ_WALK_WHOLE(KERN) LQ_LAUNCH(KERN, g, 64, sW2, cur, wl + (u64)c * ns, cnt + LQ_C_WALK0 + c, dD, dH, dBg, dDst, (const CkSeg*)nullptr, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr)
+		if (groups == 1) LQ_WALK_WHOLE((k_sort_walk_reg<1>)); else if (groups == 2) LQ_WALK_WHOLE((k_sort_walk_reg<2>)); else LQ_WALK_WHOLE(k_sort_walk_solo);
+#undef LQ_WALK_WHOLE
+		check_launch();
+	}
+	if (P.lenc[1]) { StageTimer t(h, sW2, "k_sort_walk_lds<16384>"); LQ_LAUNCH((k_sort_walk_lds<16384>), std::min<u32>(P.lenc[1], std::min<u32>(8192, wgrid)), 64, sW2, cur, wl + (u64)1 * ns, cnt + LQ_C_WALK1, dD, dH, dBg, dDst); check_launch(); }
+	if (P.lenc[0]) { StageTimer t(h, sW2, "k_sort_walk_lds<4096>"); LQ_LAUNCH((k_sort_walk_lds<4096>), std::min<u32>(P.lenc[0], std::min<u32>(1u << 16, wgrid * 4)), 64, sW2, cur, wl + (u64)0 * ns, cnt + LQ_C_WALK0, dD, dH, dBg, dDst); check_launch(); }
+}
+
+// Scatter and children, on the lane's stream, once it has waited for both walker streams.  k_rs_scatter moves the records of R[rb] to
+// their destinations in R[rb ^ 1]; k_rs_children makes the next level's sub-arrays (nxt) from the buckets that still need klib's order,
+// hands the others to the parallel sort's set 1 (lists1) or, finished, writes their anchors to A, and counts the next level's classes.
+static void kl_scatter_children(lqcov_handle *h, MapLane &L, const KlibLevels &S, const LevelPlan &P, u32 const_levels, const PsLists &lists1, const KeyMap &km)
+{
+	hipStream_t sD = L.stream;
+	u32 *cnt = S.cnt;
+	{
+		StageTimer t(h, sD, "k_rs_scatter");
+		LQ_LAUNCH(k_rs_scatter, P.g_tile, 256, sD, S.cur, L.seg_info.as<SegInfo>(), L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, S.tile, 1, S.R[S.rb], S.R[S.rb ^ 1], L.sort_dst.as<u32>(), (unsigned long long*)(cnt + LQ_C_SCATTERED));
+		check_launch();
+	}
+	// second pass: only the buckets with a listed run go on to the next level -- unless whole arrays are checked or recorded
+	const bool prune = L.prune && !h->K.debug_sort && !(h->debug_flags & 2);
+	const PruneWant want = prune ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0};
+	StageTimer t(h, sD, "k_rs_children");
+	LQ_LAUNCH(k_rs_children, (u32)std::min<u64>((u64)S.ns * 4, 1u << 20), LQ_CHILD_THREADS, sD, S.cur, cnt + S.cur_slot, S.R[S.rb ^ 1], S.rb ^ 1, L.B.as<mm128>(), L.A.as<mm128>(), L.hist.as<u32>(), L.mhist.as<u32>(), L.begs.as<u32>(),
+	          S.nxt, cnt + S.nxt_slot, const_levels, lists1, km, (int)h->K.all_klib, cnt + LQ_C_TILES, cnt + LQ_C_LEN0, S.wcaps, want);
+	check_launch();
+}
+
+// Advance: the level's one round trip (hl: the counters as the device has them behind k_rs_children, on the lane's stream), then the
+// lists, their slots and the record arrays change places and the shift steps to the next byte that varies.
+static void kl_advance(MapLane &L, KlibLevels &S, u32 *hl, u32 const_levels)
+{
+	d2h(hl, S.cnt, LQ_C_N, L.stream);
+	if (lq_timeline) lq_tl("lane", L.id, "  klib level done, shift", (double)S.shift);
+	S.ns = hl[S.nxt_slot];
+	std::swap(S.cur, S.nxt); std::swap(S.cur_slot, S.nxt_slot);
+	S.rb ^= 1;
+	if (S.shift >= 8) { S.shift -= 8; while (S.shift > 0 && (const_levels >> (S.shift >> 3) & 1)) S.shift -= 8; }
+	++S.level;
+}
+
+// After the join: the batch's last look at the counters (on the lane's stream) -- overflow of the parallel sort's lists, the algorithmic
+// bytes of the sort's stages, and the segments the passes issued without looking have left (psort_tail).
+static void sort_tails(lqcov_handle *h, MapLane &L, u64 nA, const KeyMap &km, const PsData &pd)
+{
+	hipStream_t sD = L.stream;
+	u32 hc[LQ_C_N];
+	d2h(hc, L.sort_cnt.as<u32>(), LQ_C_N, sD);
+	if (hc[LQ_C_PS0 + LQ_P_OVERFLOW] || hc[LQ_C_PS1 + LQ_P_OVERFLOW]) throw std::runtime_error("parallel sort: list or counter space overflow");
+	if (h->profiling) {	// algorithmic bytes of the sort's stages from what the kernels really moved
+		auto t64 = [&](int i) { return (u64)hc[i] | (u64)hc[i + 1] << 32; };
+		h->add_stage_bytes("k_rs_hist<first>", t64(LQ_C_HIST0) * 25);          // anchor in, record + digit byte out
+		h->add_stage_bytes("k_rs_hist", t64(LQ_C_HIST) * 9);                   // record in, digit byte out
+		h->add_stage_bytes("k_rs_scatter", t64(LQ_C_SCATTERED) * 20);          // destination + record in, record out
+		h->add_stage_bytes("k_ps_hist", (t64(LQ_C_PART0) + t64(LQ_C_PART1)) * 16);
+		h->add_stage_bytes("k_ps_scatter", (t64(LQ_C_PART0) + t64(LQ_C_PART1)) * 32);
+		h->add_stage_bytes("k_ps_finish<8192>", (t64(LQ_C_FINB0) + t64(LQ_C_FINB1)) * 32);
+		h->add_stage_bytes("k_ps_finish<1024>", (t64(LQ_C_FINS0) + t64(LQ_C_FINS1)) * 32);
+	}
+	if (hc[LQ_C_PS0 + LQ_P_BIG0]) h->psort_tail(L, 0, sD, nA, km, pd);
+	if (hc[LQ_C_PS1 + LQ_P_BIG0]) h->psort_tail(L, 1, sD, nA, km, pd);
+}
+
+// Sort every query's anchors by x, in klib's order wherever that order can be told apart (lqmap.c:238).
+//   * queries without repeated (hash, strand) minimizers hold no equal x: the parallel sort, on the lane's second stream;
+//   * the others (their anchors are in B, the originals) go through klib's passes byte by byte as 8-byte records
+//     (kernels_sort.hpp, kernels_rsort.hpp); buckets of a pass that received fewer than two marked anchors leave for the
+//     parallel sort as well (set 1, after the last pass), the others are written to A when they are finished.
+// A level of klib's passes runs on three streams.  The steps above launch; what keeps the streams apart is written out here: ev_w0 behind
+// the level's digits, histograms, bucket starts and class lists, both walker streams wait for it; ev_w1 / ev_w2 behind their walks, the
+// lane's stream waits for both before the scatter.
+void lqcov_handle::sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 *qkb, u32 nqb, u64 a_base, u64 nA)
+{
+	hipStream_t sD = L.stream, sC = L.stream2, sW = L.streamW, sW2 = L.streamW2;
+	if (nA >= 0x7ffffff0ULL) throw std::domain_error("more than 2^31 anchors in one query batch");
+	const KeyMap km = g.key_map();
+	const u32 const_levels = K.no_level_skip ? 0 : g.const_levels();
+	sort_list_buffers(L, K.ps_shift, nqb, nA);
+	auto lists = [&](int set) { return ps_lists(L, set, K.ps_shift); };
+	const u64 nA4 = ((nA + 1) * 4 + 15) & ~(u64)15;
+	KlibLevels S;
+	S.nA = nA; S.tile = K.sort_tile ? K.sort_tile : LQ_SORT_TILE; S.cnt = L.sort_cnt.as<u32>();
+	S.wcaps.c[0] = 4096; S.wcaps.c[1] = 16384; S.wcaps.c[2] = 65536; S.wcaps.c[3] = 159744;
+	for (int c = 0; c < 4; ++c) S.wcaps.c[c] >>= K.walk_shift;   // test knob
+	// records: R0 of its own, R1 in the part of the scratch area that is only used after the sort (map_batch)
+	S.R[0] = L.R0.as<RRec>(); S.R[1] = (RRec*)((u8*)L.scr.p + 3 * nA4); S.hx = (u32*)L.scr.p; S.py = (u32*)((u8*)L.scr.p + nA4);
+	S.cur = L.segs0.as<SortSeg>(); S.nxt = L.segs1.as<SortSeg>(); S.cur_slot = LQ_C_KLIB0; S.nxt_slot = LQ_C_KLIB1;
+	S.shift = 56; S.rb = 0; S.level = 0;
+	PsData pd; pd.A = L.A.as<mm128>(); pd.B = L.B.as<mm128>(); pd.R[0] = S.R[0]; pd.R[1] = S.R[1];
+	dzero(L.sort_cnt.p, LQ_C_N * 4, sD);
 	{
 		StageTimer t(this, sD, "k_sort_init");
-		LQ_LAUNCH(k_sort_init, nblk(nqb, 64), 64, sD, aqb, a_base, nqb, qkb, dA, L.segs0.as<SortSeg>(), cnt, lists(0), km, wcaps);
+		LQ_LAUNCH(k_sort_init, nblk(nqb, 64), 64, sD, aqb, a_base, nqb, qkb, pd.A, L.segs0.as<SortSeg>(), S.cnt, lists(0), km, S.wcaps);
 		check_launch();
 	}
 	// the parallel sort of the clean queries runs beside klib's passes
@@ -1481,195 +1734,32 @@ void lqcov_handle::sort_batch(MapLane &L, SortGeom g, const u64 *aqb, const u32 
 	LQ_HIP_CHECK(hipEventRecord(L.ev_join, sC));
 	// ---- klib's passes over the queries with repeated minimizers ----
 	u32 hl[LQ_C_N];                                         // the level's counters as the host last saw them
-	d2h(hl, cnt, LQ_C_N, sD);
-	u32 ns = hl[LQ_C_KLIB0];
-	if (ns) {
-		u32 *hx = (u32*)L.scr.p, *py = (u32*)((u8*)L.scr.p + nA4);
-		const u32 tile = K.sort_tile ? K.sort_tile : LQ_SORT_TILE;
-		const u32 wgrid = LQ_WALK_GRID;
-		L.sort_d.ensure(nA + 256); L.sort_dst.ensure((nA + 1) * 4);
-		L.ck_n.ensure(16);
-		SortSeg *cur = L.segs0.as<SortSeg>(), *nxt = L.segs1.as<SortSeg>();
-		u32 cur_slot = LQ_C_KLIB0, nxt_slot = LQ_C_KLIB1;
-		u32 shift = 56, rb = 0;                                // rb: the record array the level reads
+	d2h(hl, S.cnt, LQ_C_N, sD);
+	S.ns = hl[LQ_C_KLIB0];
+	if (S.ns) {
+		L.sort_d.ensure(nA + 256); L.sort_dst.ensure((nA + 1) * 4); L.ck_n.ensure(16);
 		bool gated = false;
-		for (int level = 0; level < 8 && ns > 0; ++level) {
-			L.hist.ensure((u64)ns * 1024); L.begs.ensure((u64)ns * 1024); L.mhist.ensure((u64)ns * 1024);
-			L.seg_info.ensure((u64)ns * sizeof(SegInfo)); L.walk_list.ensure((u64)ns * 4 * LQ_WALK_CLASSES); L.two_list.ensure((u64)ns * 4);
-			const u32 g_seg = std::min<u32>(ns, 1u << 18);
-			// tiles of the level's sub-arrays for the two streaming kernels
-			const u64 max_tiles = nA / tile + ns + 1;
-			const u32 g_tile = ((u32)std::min<u64>(max_tiles, K.tile_grid) + 7) & ~7u;   // a multiple of the XCD count (LQ_TILE_LOOP); blocks stride over the device-side tile list
-			L.tile_list.ensure(max_tiles * sizeof(SortTile));
-			// (the counters of the level -- next list, two-bucket and walk class lists, two-bucket tiles -- are zeroed by k_sort_tiles, the
-			// tile counter by the k_rs_children of the level before or the batch's memset: no memset dispatches inside the level loop)
-			LQ_LAUNCH(k_sort_tiles, std::min<u32>(ns / 256 + 1, 4096), 256, sD, cur, cnt + cur_slot, tile, L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, L.hist.as<u32>(), L.mhist.as<u32>(),
-			          cnt + nxt_slot, cnt + LQ_C_TWO, (u32)(1 + LQ_WALK_CLASSES), cnt + LQ_C_TWO_TILES, cnt + LQ_C_LEN0, (u32)LQ_WALK_CLASSES);
-			check_launch();
-			{
-				StageTimer t(this, sD, level == 0 ? "k_rs_hist<first>" : "k_rs_hist");
-				if (level == 0) LQ_LAUNCH((k_rs_hist<true>), g_tile, 256, sD, cur, L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, tile, 1, dB, R[rb], L.sort_d.as<u8>(), L.hist.as<u32>(), L.mhist.as<u32>(), (unsigned long long*)(cnt + LQ_C_HIST0));
-				else LQ_LAUNCH((k_rs_hist<false>), g_tile, 256, sD, cur, L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, tile, 1, dB, R[rb], L.sort_d.as<u8>(), L.hist.as<u32>(), L.mhist.as<u32>(), (unsigned long long*)(cnt + LQ_C_HIST));
-				check_launch();
-			}
-			LQ_LAUNCH(k_sort_classify, g_seg, LQ_CLASSIFY_THREADS, sD, cur, cnt + cur_slot, ns, L.hist.as<u32>(), L.begs.as<u32>(), L.seg_info.as<SegInfo>(),
-			          L.walk_list.as<u32>(), L.two_list.as<u32>(), cnt + LQ_C_TWO, cnt + LQ_C_WALK0, wcaps);
-			check_launch();
-			{	// closed-form two-bucket passes (the strand bit at the top level), over tiles: count the X / Y elements of every tile, scan
-				// per sub-array, position lists, then destinations + the move of the records
-				StageTimer t(this, sD, "k_sort_two");
-				L.two_tiles.ensure(max_tiles * sizeof(SortTile)); L.two_tile0.ensure((u64)ns * 4); L.two_tcnt.ensure(max_tiles * 8); L.two_m.ensure((u64)ns * 4);
-				const SortTile *tt = L.two_tiles.as<SortTile>();
-				const u32 *ntt = cnt + LQ_C_TWO_TILES;
-				const u32 g_two = std::min<u32>(g_tile, 2048);         // grid-stride: a level without two-bucket sub-arrays costs near-empty launches
-				const u64 *rc = (const u64*)R[rb]; u64 *rn = (u64*)R[rb ^ 1];
-				LQ_LAUNCH(k_two_tiles, std::min<u32>(ns / 256 + 1, 4096), 256, sD, cur, L.two_list.as<u32>(), cnt + LQ_C_TWO, tile, L.two_tiles.as<SortTile>(), cnt + LQ_C_TWO_TILES, L.two_tile0.as<u32>()); check_launch();
-				LQ_LAUNCH((k_sort_two_tiled<0>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
-				LQ_LAUNCH(k_sort_two_scan, std::min<u32>(ns, 16384), 64, sD, cur, L.two_list.as<u32>(), cnt + LQ_C_TWO, tile, L.two_tile0.as<u32>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>()); check_launch();
-				LQ_LAUNCH((k_sort_two_tiled<1>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
-				LQ_LAUNCH((k_sort_two_tiled<2>), g_two, 256, sD, cur, L.seg_info.as<SegInfo>(), tt, ntt, tile, L.sort_d.as<u8>(), L.two_tcnt.as<u32>(), L.two_m.as<u32>(), hx, py, rc, rn); check_launch();
-			}
-			{
-				const u8 *dD = L.sort_d.as<u8>(); const u32 *dH = L.hist.as<u32>(), *dBg = L.begs.as<u32>(); u32 *dDst = L.sort_dst.as<u32>();
-				const u32 *wl = L.walk_list.as<u32>();
-				// two walker streams: the checkpointed walks with their solvers on one, the whole walks of the shorter size classes on the
-				// other -- they concern different sub-arrays, and a level waits for the slower of the two, not for their sum
-				hipStream_t sW = L.streamW, sW2 = L.streamW2;
-				// the largest digit of this level decides how many register groups the long walker needs
-				u32 max_digit = 255;
-				if (shift == 48) max_digit = (n_targets ? n_targets - 1 : 0) >> 16;
-				else if (shift == 40 && n_targets <= (1u << 16)) max_digit = (n_targets ? n_targets - 1 : 0) >> 8;
-				else if (shift == 32 && n_targets <= (1u << 8)) max_digit = n_targets ? n_targets - 1 : 0;
-				else if (shift == 24) max_digit = (max_len ? max_len - 1 : 0) >> 24;
-				else if (shift == 16 && max_len <= (1u << 24)) max_digit = (max_len ? max_len - 1 : 0) >> 16;
-				else if (shift == 8 && max_len <= (1u << 16)) max_digit = (max_len ? max_len - 1 : 0) >> 8;
-				if (K.debug_sort) {
-					u32 hc[LQ_C_N]; d2h(hc, cnt, LQ_C_N, sD);
-					fprintf(stderr, "[sort] level %d shift %u max_digit %u ns %u two %u walk %u %u %u %u %u nA %llu\n", level, shift, max_digit, ns, hc[LQ_C_TWO],
-					        hc[LQ_C_WALK0], hc[LQ_C_WALK1], hc[LQ_C_WALK2], hc[LQ_C_WALK3], hc[LQ_C_WALK4], (unsigned long long)nA);
-					fflush(stderr);
-				}
-				// What the host knows of this level's sub-arrays: how many there are of every walk size class (counted by length when they
-				// were made: an upper bound of the class lists, which hold the general passes only), and whether the level's byte can take
-				// more than two values at all (byte 7 is strand << 7 | rid >> 24: two buckets below 2^24 targets -- no walk, ever).
-				// Launches of empty classes are skipped, the others sized by the bound: a grid sized for the worst case has every block
-				// placed, LDS included, only to find its list empty, and a level has up to ten such launches on its critical path.
-				u32 lenc[LQ_WALK_CLASSES];
-				for (int c = 0; c < LQ_WALK_CLASSES; ++c) lenc[c] = hl[LQ_C_LEN0 + c];
-				const u32 max_buckets = shift == 56 ? 2 * (((n_targets ? n_targets - 1 : 0) >> 24) + 1) : max_digit + 1;
-				const bool any_walk = max_buckets > 2 || K.no_level_skip;
-				const bool ck_small = K.reg_walker && max_digit < LQ_CK_B;
-				const bool ck3 = ck_small || K.ckpt3;                             // (round 6: on by default for passes with many buckets too -- their states are found by sub-chains side by side, a 65-160 k walk took 8-21 ms whole)
-				const u64 n_ck_segs = K.ckpt ? (u64)(ck3 ? lenc[3] : 0) + lenc[4] : 0;
-				int first_plain_class = K.ckpt ? (ck3 ? 2 : 3) : LQ_WALK_CLASSES - 1;
-				bool w1 = false, w2 = false;                          // which walker streams got work
-				// (the checkpoint buffers are sized before the fork: a block that the lane's stream allocates after the event the walker
-				// streams wait for would not be ordered before their kernels)
-				const u32 ck_unit = std::max<u32>((ck_small ? LQ_CK_UNIT : LQ_CK_UNIT_MANY) >> K.walk_shift, 8);
-				const u32 ck_quantum = ck_small ? 1u : (u32)LQ_CKM_Q;   // many buckets: checkpoints come in sub-chains of LQ_CKM_Q (k_ck_chain256)
-				const u32 ck_min_len = wcaps.c[ck3 ? 2 : 3] + 1;
-				const u64 cks_max = std::min<u64>(std::min<u64>(nA / ck_min_len + 1, ns), n_ck_segs), ck_max = nA / ck_unit + (2 + ck_quantum) * cks_max, tiles_max = nA / LQ_CK_TILE + cks_max;
-				const u32 per_ck = ck_small ? LQ_CK_B : 256;          // cursors per checkpoint
-				if (any_walk && n_ck_segs) {
-					L.ck_segs.ensure(cks_max * sizeof(CkSeg)); L.ck_S.ensure(ck_max * per_ck * 4); L.ck_slot.ensure(ck_max * 4 + 4);
-					if (ck_small) { L.ck_T.ensure((tiles_max + 1) * LQ_CK_B * 4); L.ck_E.ensure(cks_max * LQ_CK_B * LQ_CK_B * 4); }
-				}
-				if (any_walk) { LQ_HIP_CHECK(hipEventRecord(L.ev_w0, sD)); }
-				if (!gated && !L.gate_passed) { L.gate_passed = true; open_gate(); gated = true; }   // let the next lane start under these walks
-				// Long sub-arrays: the walk's state at evenly spread checkpoints is computed without walking (kernels_ckpt.hpp) and
-				// one walker per checkpoint runs a short piece.  Few buckets (the byte of rid above 65536 targets: the (query, strand)
-				// arrays of the longest queries, millions of anchors each): states from prefix counts; up to 256 buckets: bulk-follow
-				// solver, longest size class only (finding the states costs about as much as walking 50-100 k elements there).
-				// The plan (which sub-arrays, their tiles and checkpoints) is laid out on the device from the class lists.
-				if (any_walk && n_ck_segs) {
-					LQ_HIP_CHECK(hipStreamWaitEvent(sW, L.ev_w0, 0)); w1 = true;
-					const u32 unit = ck_unit;
-					const CkSeg *dck = L.ck_segs.as<CkSeg>();
-					const u32 *ckn = L.ck_n.as<u32>();
-					LQ_LAUNCH(k_ck_plan, 1, 256, sW, cur, wl, ns, cnt + LQ_C_WALK0, (int)ck3, unit, ck_small ? 512u : 256u, ck_quantum, L.ck_segs.as<CkSeg>(), (u32)cks_max, L.ck_n.as<u32>()); check_launch();
-					const u32 g_ck = (u32)std::min<u64>(ck_max, wgrid), g_cks = (u32)std::min<u64>(cks_max, wgrid);
-					if (ck_small) {
-						{
-							StageTimer t(this, sW, "k_ck_prefix");
-							LQ_LAUNCH(k_ck_tilehist, (u32)std::min<u64>(tiles_max, 1u << 16), 256, sW, dck, ckn, cur, dD, L.ck_T.as<u32>()); check_launch();
-							LQ_LAUNCH(k_ck_tilescan, std::min<u32>(g_cks, 8192), 256, sW, dck, ckn, cur, L.ck_T.as<u32>()); check_launch();
-						}
-						{
-							StageTimer t(this, sW, "k_ck_solve");
-							LQ_LAUNCH(k_ck_phases, (u32)std::min<u64>(cks_max * LQ_CK_B, 1u << 16), 64, sW, dck, ckn, cur, dD, dH, dBg, L.ck_T.as<u32>(), L.ck_E.as<u32>()); check_launch();
-							LQ_LAUNCH(k_ck_solve, g_ck, 64, sW, dck, ckn, cur, dD, dH, dBg, L.ck_T.as<u32>(), L.ck_E.as<u32>(), L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
-						}
-						{
-							StageTimer t(this, sW, "k_sort_walk_reg<1>ck");
-							LQ_LAUNCH((k_sort_walk_reg<1>), g_ck, 64, sW, cur, (const u32*)nullptr, ckn, dD, dH, dBg, dDst, dck, ckn, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
-						}
-					} else {
-						{
-							StageTimer t(this, sW, "k_ck_chain256");
-							LQ_LAUNCH(k_ck_chain256, (u32)std::min<u64>(ck_max / LQ_CKM_Q + 1, wgrid), LQ_CKM_THREADS, sW, dck, ckn, cur, dD, dH, dBg, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
-						}
-						{
-							StageTimer t(this, sW, "k_sort_walk_solo_ck");
-							LQ_LAUNCH(k_sort_walk_solo, g_ck, 64, sW, cur, (const u32*)nullptr, ckn, dD, dH, dBg, dDst, dck, ckn, L.ck_S.as<u32>(), L.ck_slot.as<u32>()); check_launch();
-						}
-					}
-				}
-				// whole walks, longest class first: they outlast everything else of the level on a handful of CUs
-				auto fork2 = [&]() { if (!w2) { LQ_HIP_CHECK(hipStreamWaitEvent(sW2, L.ev_w0, 0)); w2 = true; } };
-				for (int c = first_plain_class; any_walk && c >= 2; --c) {
-					if (!lenc[c]) continue;
-					fork2();
-					const u32 g = std::min<u32>(lenc[c], std::min<u32>(8192, wgrid));
-					const CkSeg *nock = nullptr;
-					if (K.reg_walker && max_digit < 64) { StageTimer t(this, sW2, "k_sort_walk_reg<1>"); LQ_LAUNCH((k_sort_walk_reg<1>), g, 64, sW2, cur, wl + (u64)c * ns, cnt + LQ_C_WALK0 + c, dD, dH, dBg, dDst, nock, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr); }
-					else if (K.reg_walker && max_digit < 128) { StageTimer t(this, sW2, "k_sort_walk_reg<2>"); LQ_LAUNCH((k_sort_walk_reg<2>), g, 64, sW2, cur, wl + (u64)c * ns, cnt + LQ_C_WALK0 + c, dD, dH, dBg, dDst, nock, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr); }
-					else { StageTimer t(this, sW2, "k_sort_walk_solo"); LQ_LAUNCH(k_sort_walk_solo, g, 64, sW2, cur, wl + (u64)c * ns, cnt + LQ_C_WALK0 + c, dD, dH, dBg, dDst, nock, (const u32*)nullptr, (const u32*)nullptr, (const u32*)nullptr); }
-					check_launch();
-				}
-				if (any_walk && lenc[1]) { fork2(); StageTimer t(this, sW2, "k_sort_walk_lds<16384>"); LQ_LAUNCH((k_sort_walk_lds<16384>), std::min<u32>(lenc[1], std::min<u32>(8192, wgrid)), 64, sW2, cur, wl + (u64)1 * ns, cnt + LQ_C_WALK1, dD, dH, dBg, dDst); check_launch(); }
-				if (any_walk && lenc[0]) { fork2(); StageTimer t(this, sW2, "k_sort_walk_lds<4096>"); LQ_LAUNCH((k_sort_walk_lds<4096>), std::min<u32>(lenc[0], std::min<u32>(1u << 16, wgrid * 4)), 64, sW2, cur, wl + (u64)0 * ns, cnt + LQ_C_WALK0, dD, dH, dBg, dDst); check_launch(); }
-				if (w1) { LQ_HIP_CHECK(hipEventRecord(L.ev_w1, sW)); LQ_HIP_CHECK(hipStreamWaitEvent(sD, L.ev_w1, 0)); }
-				if (w2) { LQ_HIP_CHECK(hipEventRecord(L.ev_w2, sW2)); LQ_HIP_CHECK(hipStreamWaitEvent(sD, L.ev_w2, 0)); }
-			}
-			{
-				StageTimer t(this, sD, "k_rs_scatter");
-				LQ_LAUNCH(k_rs_scatter, g_tile, 256, sD, cur, L.seg_info.as<SegInfo>(), L.tile_list.as<SortTile>(), cnt + LQ_C_TILES, tile, 1, R[rb], R[rb ^ 1], L.sort_dst.as<u32>(), (unsigned long long*)(cnt + LQ_C_SCATTERED));
-				check_launch();
-			}
-			{
-				StageTimer t(this, sD, "k_rs_children");
-				LQ_LAUNCH(k_rs_children, (u32)std::min<u64>((u64)ns * 4, 1u << 20), LQ_CHILD_THREADS, sD, cur, cnt + cur_slot, R[rb ^ 1], rb ^ 1, dB, dA, L.hist.as<u32>(), L.mhist.as<u32>(), L.begs.as<u32>(),
-				          nxt, cnt + nxt_slot, const_levels, lists(1), km, (int)K.all_klib, cnt + LQ_C_TILES, cnt + LQ_C_LEN0, wcaps,
-			          L.prune && !K.debug_sort && !(debug_flags & 2) ? PruneWant{L.want.as<unsigned long long>(), L.prune_n_want, L.sub_off.as<u64>(), L.sub_q.as<u32>(), L.prune_n_sub} : PruneWant{nullptr, 0, nullptr, nullptr, 0});
-				check_launch();
-			}
-			d2h(hl, cnt, LQ_C_N, sD);
-			if (lq_timeline) { int lane_id = 0; for (size_t i_ = 0; i_ < lanes.size(); ++i_) if (lanes[i_].get() == &L) lane_id = (int)i_; lq_tl("lane", lane_id, "  klib level done, shift", (double)shift); }
-			ns = hl[nxt_slot];
-			std::swap(cur, nxt); std::swap(cur_slot, nxt_slot);
-			rb ^= 1;
-			if (shift >= 8) { shift -= 8; while (shift > 0 && (const_levels >> (shift >> 3) & 1)) shift -= 8; }
+		while (S.level < 8 && S.ns > 0) {
+			const LevelPlan P = level_plan(g, S.shift, S.ns, nA, hl, K, S.wcaps, S.tile);
+			kl_buffers(L, S, P);
+			kl_digits(this, L, S, P);
+			kl_two(this, L, S, P);
+			if (K.debug_sort) kl_debug_line(L, S, P);
+			// two walker streams: the checkpointed walks with their solvers on one, the whole walks of the shorter size classes on the
+			// other -- they concern different sub-arrays, and a level waits for the slower of the two, not for their sum
+			if (P.any_walk) { LQ_HIP_CHECK(hipEventRecord(L.ev_w0, sD)); }
+			if (!gated && !L.gate_passed) { L.gate_passed = true; open_gate(); gated = true; }   // let the next lane start under these walks
+			if (P.ck_walks) { LQ_HIP_CHECK(hipStreamWaitEvent(sW, L.ev_w0, 0)); kl_ck_walks(this, L, S, P); }
+			if (P.whole_walks) { LQ_HIP_CHECK(hipStreamWaitEvent(sW2, L.ev_w0, 0)); kl_whole_walks(this, L, S, P); }
+			if (P.ck_walks) { LQ_HIP_CHECK(hipEventRecord(L.ev_w1, sW)); LQ_HIP_CHECK(hipStreamWaitEvent(sD, L.ev_w1, 0)); }
+			if (P.whole_walks) { LQ_HIP_CHECK(hipEventRecord(L.ev_w2, sW2)); LQ_HIP_CHECK(hipStreamWaitEvent(sD, L.ev_w2, 0)); }
+			kl_scatter_children(this, L, S, P, const_levels, lists(1), km);
+			kl_advance(L, S, hl, const_levels);
 		}
 		psort_run(L, 1, sD, nA, km, pd);                      // the buckets that left klib's passes
 	}
 	LQ_HIP_CHECK(hipStreamWaitEvent(sD, L.ev_join, 0));
-	{
-		u32 hc[LQ_C_N];
-		d2h(hc, cnt, LQ_C_N, sD);
-		if (hc[LQ_C_PS0 + LQ_P_OVERFLOW] || hc[LQ_C_PS1 + LQ_P_OVERFLOW]) throw std::runtime_error("parallel sort: list or counter space overflow");
-		if (profiling) {	// algorithmic bytes of the sort's stages from what the kernels really moved
-			auto t64 = [&](int i) { return (u64)hc[i] | (u64)hc[i + 1] << 32; };
-			add_stage_bytes("k_rs_hist<first>", t64(LQ_C_HIST0) * 25);          // anchor in, record + digit byte out
-			add_stage_bytes("k_rs_hist", t64(LQ_C_HIST) * 9);                   // record in, digit byte out
-			add_stage_bytes("k_rs_scatter", t64(LQ_C_SCATTERED) * 20);          // destination + record in, record out
-			add_stage_bytes("k_ps_hist", (t64(LQ_C_PART0) + t64(LQ_C_PART1)) * 16);
-			add_stage_bytes("k_ps_scatter", (t64(LQ_C_PART0) + t64(LQ_C_PART1)) * 32);
-			add_stage_bytes("k_ps_finish<8192>", (t64(LQ_C_FINB0) + t64(LQ_C_FINB1)) * 32);
-			add_stage_bytes("k_ps_finish<1024>", (t64(LQ_C_FINS0) + t64(LQ_C_FINS1)) * 32);
-		}
-		if (hc[LQ_C_PS0 + LQ_P_BIG0]) psort_tail(L, 0, sD, nA, km, pd);
-		if (hc[LQ_C_PS1 + LQ_P_BIG0]) psort_tail(L, 1, sD, nA, km, pd);
-	}
+	sort_tails(this, L, nA, km, pd);
 }
 
 void lqcov_handle::open_gate()
@@ -1978,6 +2068,7 @@ void lqcov_handle::swap_plan(SeedPlan &S)
 void lqcov_handle::add_lane()
 {
 	lanes.emplace_back(new MapLane());
+	lanes.back()->id = (int)lanes.size() - 1;
 	LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream));
 	LQ_HIP_CHECK(hipStreamCreate(&lanes.back()->stream2));
 	{	// Token walks are latency-bound single-lane waves that live for milliseconds: left alone they fill the wave slots and

@@ -146,7 +146,82 @@ struct PsWork {                           // one set of psort lists + the scratc
 // What the anchor sort needs to know of a part: how many targets it holds and how long the longest one is (the key bits that vary,
 // the levels that are identity passes: sort_batch).  From the part's reads (lqcov_handle::sort_geom) or stated by a test
 // (lqcov_debug_sort_anchors).
-struct SortGeom { u32 n_targets = 0, max_len = 0; };
+// Everything the sort derives from the two numbers is derived here: the key is x = strand:1 | rid:31 | position:32 (lqmap.c:190-196),
+// a level is one key byte, level 7 (shift 56) the top one.
+struct SortGeom {
+	u32 n_targets = 0, max_len = 0;
+	constexpr u32 top_rid() const { return n_targets ? n_targets - 1 : 0; }
+	constexpr u32 top_pos() const { return max_len ? max_len - 1 : 0; }
+	// varying low bits of the position and of rid in this part (KeyMap)
+	constexpr u32 pbits() const { u32 b = 1; while (b < 32 && ((u64)1 << b) < (u64)max_len) ++b; return b; }
+	constexpr u32 rbits() const { u32 b = 0; while (b < 31 && ((u64)1 << b) < (u64)n_targets) ++b; return b; }
+	KeyMap key_map() const;               // {pbits(), rbits()} (engine.cpp: KeyMap is kernels_psort.hpp's)
+	// key bytes that are zero in every anchor of this part, bit i for the byte at shift 8 i: the levels sort_batch steps over.  Never the
+	// strand's byte (7), the lowest byte of rid (4: shift 32 is walked even with one target) or of the position (0)
+	constexpr u32 const_levels() const
+	{
+		return (n_targets <= (1u << 16) ? 1u << 6 : 0) | (n_targets <= (1u << 8) ? 1u << 5 : 0)
+		     | (max_len <= (1u << 24) ? 1u << 3 : 0) | (max_len <= (1u << 16) ? 1u << 2 : 0) | (max_len <= (1u << 8) ? 1u << 1 : 0);
+	}
+	// the largest digit the byte at `shift` can hold where that is known to be less than a byte's 255: the top byte of rid or of the
+	// position that varies, not the bytes below it
+	constexpr u32 max_digit(u32 shift) const
+	{
+		return shift == 48 ? top_rid() >> 16 : shift == 40 && n_targets <= (1u << 16) ? top_rid() >> 8 : shift == 32 && n_targets <= (1u << 8) ? top_rid()
+		     : shift == 24 ? top_pos() >> 24 : shift == 16 && max_len <= (1u << 24) ? top_pos() >> 16 : shift == 8 && max_len <= (1u << 16) ? top_pos() >> 8 : 255;
+	}
+	// buckets a pass over that byte can fill (byte 7 is strand << 7 | rid >> 24: two buckets below 2^24 targets)
+	constexpr u32 max_buckets(u32 shift) const { return shift == 56 ? 2 * ((top_rid() >> 24) + 1) : max_digit(shift) + 1; }
+};
+namespace sort_geom_pins {                    // the values above at the edges where a bit or a level changes
+constexpr u32 edges[] = {0, 1, 256, 257, 65536, 65537, 1u << 24, (1u << 24) + 1, 0x7fffffffu};
+constexpr bool rid_side(u32 n, u32 rbits, u32 levels, u32 d48, u32 d40, u32 d32, u32 b56)
+{
+	const SortGeom g{n, 0};
+	return g.rbits() == rbits && (g.const_levels() & 0xf0) == levels && g.max_digit(48) == d48 && g.max_digit(40) == d40 && g.max_digit(32) == d32 && g.max_buckets(56) == b56;
+}
+constexpr bool pos_side(u32 len, u32 pbits, u32 levels, u32 d24, u32 d16, u32 d8)
+{
+	const SortGeom g{0, len};
+	return g.pbits() == pbits && (g.const_levels() & 0x0f) == levels && g.max_digit(24) == d24 && g.max_digit(16) == d16 && g.max_digit(8) == d8;
+}
+// every pair of edges: bytes 0, 4 and 7 are never stepped over, a level that is stepped over holds one digit, and the bytes without a
+// bound (7 and 0 always) say 255
+constexpr bool consistent()
+{
+	for (u32 n : edges) for (u32 len : edges) {
+		const SortGeom g{n, len};
+		if (g.const_levels() & 0x91) return false;
+		for (u32 lv = 0; lv < 8; ++lv) {
+			if ((g.const_levels() >> lv & 1) && g.max_digit(8 * lv) != 0) return false;
+			if (lv != 7 && g.max_buckets(8 * lv) != g.max_digit(8 * lv) + 1) return false;
+		}
+		if (g.max_digit(56) != 255 || g.max_digit(0) != 255) return false;
+	}
+	return true;
+}
+static_assert(consistent(), "SortGeom: a constant level with more than one digit, or a level that must be walked marked constant");
+//                     targets      rbits levels  >>16   >>8  byte 4  buckets at 56
+static_assert(rid_side(0,             0,  0x60,     0,     0,     0,    2), "");
+static_assert(rid_side(1,             0,  0x60,     0,     0,     0,    2), "");
+static_assert(rid_side(256,           8,  0x60,     0,     0,   255,    2), "");
+static_assert(rid_side(257,           9,  0x40,     0,     1,   255,    2), "");
+static_assert(rid_side(65536,        16,  0x40,     0,   255,   255,    2), "");
+static_assert(rid_side(65537,        17,  0x00,     1,   255,   255,    2), "");
+static_assert(rid_side(1u << 24,     24,  0x00,   255,   255,   255,    2), "");
+static_assert(rid_side((1u << 24) + 1, 25, 0x00,  256,   255,   255,    4), "");   // (rid >> 16 is not cut to a byte: 256 and up mean "any digit")
+static_assert(rid_side(0x7fffffffu,  31,  0x00, 32767,   255,   255,  256), "");
+//                     longest      pbits levels  >>24  >>16   >>8
+static_assert(pos_side(0,             1,  0x0e,     0,     0,     0), "");
+static_assert(pos_side(1,             1,  0x0e,     0,     0,     0), "");
+static_assert(pos_side(256,           8,  0x0e,     0,     0,     0), "");
+static_assert(pos_side(257,           9,  0x0c,     0,     0,     1), "");
+static_assert(pos_side(65536,        16,  0x0c,     0,     0,   255), "");
+static_assert(pos_side(65537,        17,  0x08,     0,     1,   255), "");
+static_assert(pos_side(1u << 24,     24,  0x08,     0,   255,   255), "");
+static_assert(pos_side((1u << 24) + 1, 25, 0x00,    1,   255,   255), "");
+static_assert(pos_side(0x7fffffffu,  31,  0x00,   127,   255,   255), "");
+}
 
 // One call of sort_checked as lqcov_set_debug's bit 1 records it (lqcov_get_sort_batches)
 struct SortBatchRec {
@@ -157,6 +232,7 @@ struct SortBatchRec {
 };
 
 struct MapLane {
+	int id = 0;                           // its place in lqcov_handle::lanes (add_lane): the timeline's lane number
 	hipStream_t stream = nullptr;         // klib's passes (queries with repeated minimizers), then runs and chains
 	hipStream_t stream2 = nullptr;        // the parallel sort of every other query, meanwhile
 	hipStream_t streamW = nullptr;        // the serial token walks: streams confined to a quarter of the CUs (see map_part):
