@@ -442,6 +442,39 @@ int lqfig_boxstats(int device, const uint32_t *key, const int32_t *thou, uint64_
                    int32_t *sorted, lqfig_box *boxes, uint32_t box_cap, uint32_t *n_boxes,
                    char *errbuf, size_t errbuf_len);
 
+/* ---- the coverage estimate's two mixture fits (lq_coverage.py:552-621) ------------------------------------------------------------- */
+/* n_fits independent fits in one launch, one workgroup per fit, the whole EM loop and its stopping rule on the device.  x: the fits'
+ * values one after the other, off (n_fits + 1 ascending entries): fit f has x[off[f] .. off[f + 1]).  Every segment is sorted ascending
+ * on the host first and every sum over it is added in an order fixed by its length alone (tiles of 256 values in index order, a pairwise
+ * tree over the tiles): a fit is a function of its segment's values as a multiset -- the same bytes whatever the order of
+ * the rows, the batch around it, the grid and the run.  LQCOV_E_ARG: null buffers, n_fits == 0, offsets not ascending, a segment of fewer
+ * than 2 or more than LQMIX_MAX_N values, a value that is not finite, a segment whose values are all equal (no variance), and what
+ * each call names.                                                                                                                      */
+#define LQMIX_MAX_N 9216
+#define LQMIX_EXIT_TOL 0           /* the stopping rule's tolerance was met */
+#define LQMIX_EXIT_MAX 1           /* max_iter was reached */
+#define LQMIX_EXIT_NAN 2           /* lqmix_lognorm: the log-likelihood became NaN; the numbers are reported as they are */
+typedef struct lqmix_fit {
+	double   w[2], mu[2];
+	double   s[2];                 /* lqmix_gmm2: the variances; lqmix_lognorm: the sigmas */
+	double   ll;                   /* lqmix_gmm2: the last lower bound; lqmix_lognorm: the last log-likelihood */
+	uint32_t n_iter, exit;         /* E/M passes made (lqmix_lognorm: mixem's iteration + 1), LQMIX_EXIT_* */
+	uint64_t n;                    /* the segment's size */
+} lqmix_fit;
+/* sklearn's GaussianMixture(n_components=2).fit of 1-D data after its initialisation (tol, max_iter, reg_covar: its 1e-3, 100, 1e-6),
+ * from a deterministic start in place of its seeded k-means: the split of the sorted values into {first k} + {rest} with the smallest
+ * two-cluster squared error (the smallest such k), as one-hot responsibilities.  The parameters are those after the M-step of the last
+ * iteration; the components come out ascending in their mean.  tol < 0 never stops early.  LQCOV_E_ARG also for max_iter == 0, a
+ * negative or non-finite reg_covar, a NaN tol.                                                                                          */
+int lqmix_gmm2(int device, const double *x, const uint64_t *off, uint32_t n_fits, double tol, uint32_t max_iter, double reg_covar,
+               lqmix_fit *out, char *errbuf, size_t errbuf_len);
+/* mixem.em(data, [NormalDistribution(mu_bg, sigma_bg), LogNormalDistribution(mu_logn, sigma_logn)], max_iterations=max_iter, tol=tol,
+ * tol_iters=tol_iters) (mixem's 1e-15 and 10; LongQC's max_iterations is 500): init has the four numbers of every fit; component 0 is
+ * the normal, 1 the log-normal; initial weights (1, 1).  LQCOV_E_ARG also for a value <= 0, a sigma that is not positive and finite, a
+ * mu that is not finite, tol_iters outside [1, 64], a NaN tol.                                                                          */
+int lqmix_lognorm(int device, const double *x, const uint64_t *off, uint32_t n_fits, const double *init, double tol, uint32_t tol_iters,
+                  uint32_t max_iter, lqmix_fit *out, char *errbuf, size_t errbuf_len);
+
 /* ---- one upload per chunk: the chunk loop of sampleqc (longQC.py:299-360) and the coverage call on the same device bytes ---------- */
 /* A resident chunk: lqchunk_load uploads the reads (ASCII, seq_off with n+1 ascending entries, qual NULL or parallel to seq as in
  * lqsdust_reads) once into device buffers the handle owns and reuses, growing, from chunk to chunk.  lqchunk_sdust, lqchunk_adapt and

@@ -11,6 +11,7 @@ SampleQCPass is the loop's body and the coverage call: add_chunk(reads) per chun
 subsample, GC fractions, then the chunk is 2-bit packed on the device and kept there -- and coverage(), which maps the subsample
 against the kept chunks without touching the input again.  No CPU fallback: without liblqcov.so or a HIP device the calls raise."""
 import ctypes as C
+import io
 import math
 import os
 import sys
@@ -691,7 +692,7 @@ class SampleQCPass:
     writes longqc_sdust<suffix>.txt), the adapter search trims a copy of the records (kept in `trimmed`, for --trim; `adapters` is the
     AdapterStats) as the reference's pool does, the subsample (`s_reads`, seed-7 reservoir of `nsample`) and the GC fractions (`gc`, an
     LqGCMI355X) see the untrimmed reads; then the chunk is packed on the device and appended to `store`.
-    coverage() maps the subsample against the stored chunks; figures() gives the numbers behind the GC and the length figure."""
+    coverage() maps the subsample against the stored chunks, coverage_stats() estimates the coverage from its table; figures() gives the numbers behind the GC and the length figure."""
 
     def __init__(self, work_dir: str, preset: str, adp5=None, adp3=None, nsample=5000, gc_draw: str = "device", device: int = 0,
                  fast: bool = False, inds: int = 4000000000, suffix: Optional[str] = None, gc_seed: int = 0, lib=None,
@@ -807,10 +808,23 @@ class SampleQCPass:
                 text = tuple(self._pass([(main_reads, argv_main), (short_reads, argv_short)]))
             else:                                                  # other index options: a pass of its own over the same stored chunks
                 text = (self._pass([(main_reads, argv_main)])[0], self._pass([(short_reads, argv_short)])[0])
+        self.table_text = text if isinstance(text, str) else "".join(text)       # (for coverage_stats)
         if out:
             with open(out, "w") as f:
-                f.write(text if isinstance(text, str) else "".join(text))
+                f.write(self.table_text)
         return text
+
+    def coverage_stats(self, is_transcript=False):
+        """The Coverage_stats entries of the run's JSON (longQC.py:659-681) from the table coverage() made last (with short_threshold: the
+        pair concatenated, LongQC's merged table): covtable.CoverageTable(table).est_coverage(is_transcript).json_block(throughput) with
+        both mixture fits on the device (mixfit) and the bases of every chunk added as the throughput (longQC.py:468).  `coverage_table`
+        keeps the CoverageTable for the getters and the figure data"""
+        from . import covtable
+        if getattr(self, "table_text", None) is None:
+            raise RuntimeError("coverage_stats() reads the table of coverage(): call that first")
+        self.coverage_table = covtable.CoverageTable(io.StringIO(self.table_text))
+        self.coverage_table.est_coverage(is_transcript, device=self.device, lib=self.lib)
+        return self.coverage_table.json_block(self.n_bases)
 
     def _pass(self, sets):
         """one run over the stored chunks for every (reads, argv) of `sets` -> one table per set"""
