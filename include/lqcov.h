@@ -757,6 +757,57 @@ int  lqfastq_close(lqfastq *w);
 const char *lqfastq_last_error(const lqfastq *w);
 double lqfastq_kernel_ms(const lqfastq *w);
 
+/* ---- Sequel platform QC: the polymerase reads of a run from *.scraps.bam and *.subreads.bam (lq_sequel.run_platformqc) ------------- */
+/* A handle collects items (zmw, start, end, class) on the device, 16 bytes each, and lqpol_finish makes of them what
+ * lq_sequel.py:260-336 makes of its dict: per ZMW construct_polread's hq, tot, is_pol and ad_num, and over the ZMWs with is_pol the
+ * sums, N50 and N90.  kind: 0 the scraps file, 1 the subreads file; every scraps item arrives before every subreads
+ * item (scraps after subreads: LQCOV_E_STATE), and within a ZMW items with equal (start, end) keep their arrival order.
+ * lqpol_add_bytes: bytes[0 .. n) on the host, inflated BAM bytes, a parser that stands at start_pos, a record boundary behind the BAM
+ * header; the records that are whole are taken, *resume_pos is the first byte of the one that is not (or n), as lqbam_scan's.  The
+ * device walk (k_bam_*) finds the records it vouches for, k_pol_fields reads their names and -- in the scraps file -- their sz and sc
+ * tags; a record outside its domain (name not "x/zmw/start_end" with zmw, start, end of 1 to 9 digits and zmw without leading zeros;
+ * an sz or sc that is not of type A; a tag area that does not end at the record's end) and a record the walk does not vouch for are
+ * read by the host instead, which fails with LQCOV_E_IO where lq_sequel.py would raise and with LQCOV_E_DOMAIN where a value does
+ * not fit an item; the message names the record.
+ * lqpol_add_file: the whole BAM file in pieces; inflate_mode LQREADER_INFLATE_*, host_copy_mode LQREADER_HOSTCOPY_*: with the device's
+ * inflate and LQREADER_HOSTCOPY_NEEDED the inflated bytes stay on the device (the blocks' CRC32 is made there) and the host fetches the
+ * BAM header, 36 bytes of the record that straddles a piece's end, the records it has to read itself and, for a scan with a flagged
+ * record, that scan's flags and rows (20 bytes a record).  lqpol_header_text: the header text of the file added last for `kind` (*len
+ * its length, at most cap bytes copied); lqpol_file_header: the same of a file, read from its first blocks alone, without a handle --
+ * for a caller that checks the header before it reads on.
+ * lqpol_add_items: items given directly (cls: the class letter), in any state before lqpol_finish.
+ * lqpol_finish: once; *control the control throughput.  lqpol_get: the per-ZMW arrays (n_zmw entries, ascending zmw; NULL: not wanted).
+ * lqpol_stats: LQPOL_STATS_WORDS words -- sum of hq, max hq, min tot, max tot, N50, N90, the is_pol ZMWs with tot == 0 (the reference
+ * divides by it), min and max ad_num, all over the is_pol ZMWs; the ZMWs the second walk launch took; records read by k_pol_fields,
+ * re-read by the host because flagged, walked by the host; inflated bytes, bytes fetched to the host, pieces; the is_pol ZMWs whose hq or
+ * tot is negative or above 2^32-1 (with any, the sums are void and lqpol_hist / lqpol_logsum return LQCOV_E_DOMAIN).
+ * lqpol_hist / lqpol_logsum: lqfig_hist / lqfig_logsum over the resident uint32 array `which` of the is_pol ZMWs (logsum: LQPOL_HQ).
+ * lqpol_fields / lqpol_twin: the two readers of a record alone, for tests -- the device's flags (bit 0 item, bit 1 flagged, bit 2
+ * control) and compacted slots (16 bytes each; a flagged record's slot holds zmw 0x7fffffff) over the vouched records of a range, and
+ * the host's reading of one whole record. */
+typedef struct lqpol lqpol;
+#define LQPOL_STATS_WORDS 17
+#define LQPOL_HQ  0
+#define LQPOL_TOT 1
+#define LQPOL_AD  2
+lqpol *lqpol_create(int device);                     /* NULL without a HIP device */
+void   lqpol_destroy(lqpol *p);
+const char *lqpol_last_error(const lqpol *p);
+int lqpol_add_bytes(lqpol *p, int kind, const uint8_t *bytes, uint64_t n, uint64_t start_pos, uint64_t *resume_pos);
+int lqpol_add_file(lqpol *p, int kind, const char *path, int inflate_mode, int host_copy_mode);
+int lqpol_header_text(const lqpol *p, int kind, char *buf, uint64_t cap, uint64_t *len);
+int lqpol_file_header(const char *path, char *buf, uint64_t cap, uint64_t *len, char *errbuf, size_t errbuf_len);
+int lqpol_add_items(lqpol *p, const uint32_t *zmw, const uint32_t *start, const uint32_t *end, const uint8_t *cls, uint64_t n);
+int lqpol_finish(lqpol *p, uint64_t *n_zmw, uint64_t *n_pol, int64_t *control);
+int lqpol_get(lqpol *p, uint32_t *zmw, int64_t *hq, int64_t *tot, uint32_t *ad, uint8_t *is_pol);
+int lqpol_stats(const lqpol *p, uint64_t out[LQPOL_STATS_WORDS]);
+int lqpol_hist(lqpol *p, int which, const double *edges, uint32_t n_edges, uint64_t *counts);
+int lqpol_logsum(lqpol *p, uint64_t *sum, double *sum_log, uint64_t *n_zero);
+int lqpol_fields(int device, int kind, const uint8_t *bytes, uint64_t n, uint64_t start_pos, uint32_t *flags, uint32_t *items, uint64_t cap,
+                 uint64_t *n_rows, uint64_t *n_slots, int64_t *control, uint64_t *resume_pos, char *errbuf, size_t errbuf_len);
+int lqpol_twin(int kind, const uint8_t *rec, uint64_t len, uint64_t rec_no, uint32_t item[4], int64_t *control, uint32_t *flags,
+               char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 
 struct BamScan : FxScan {
 	DBuf link;
+	bool fetch_rows = true;                                   // false: h_rows stays empty, the rows are the device's alone (polread.cpp fetches them when it needs them)
 
 	// d[0 .. n): the bytes (d + n + 16 readable); the parser stands at start_pos, a record boundary behind the BAM header.  Positions in
 	// rows, segments and resume_pos are relative to d.  with_qual: the quality segments name the file's bytes, else LQ_GATHER_FILL.
@@ -57,9 +58,11 @@ struct BamScan : FxScan {
 		sseg.ensure((size_t)(n_sseg + 1) * sizeof(GatherSeg)); qseg.ensure((size_t)(n_qseg + 1) * sizeof(GatherSeg));
 		emit(1);
 		LQ_HIP_CHECK(hipGetLastError());
-		h_rows.resize((size_t)n_rows);
 		u32 h_res = 0;
-		LQ_HIP_CHECK(hipMemcpyAsync(h_rows.data(), rows.p, (size_t)n_rows * sizeof(FxRow), hipMemcpyDeviceToHost, stream));
+		if (fetch_rows) {
+			h_rows.resize((size_t)n_rows);
+			LQ_HIP_CHECK(hipMemcpyAsync(h_rows.data(), rows.p, (size_t)n_rows * sizeof(FxRow), hipMemcpyDeviceToHost, stream));
+		}
 		LQ_HIP_CHECK(hipMemcpyAsync(&h_res, resume.p, 4, hipMemcpyDeviceToHost, stream));
 		LQ_HIP_CHECK(hipStreamSynchronize(stream));
 		resume_pos = h_res;

@@ -4,6 +4,7 @@
 // on n alone; the grid only decides which wave takes which tile.
 #include "lq_cabi.hpp"
 #include "kernels_figdata.hpp"
+#include "figdata_dev.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -54,6 +55,38 @@ void fold(DBuf &part, u64 rows, u32 m, double *out, hipStream_t s)
 }
 } // namespace
 
+// ---- the same two passes over an array that lies on the device already (polread.cpp: the polymerase reads' lengths stay resident) ----
+// d_x[0 .. n), n >= 1, n_edges >= 2, the arguments checked by the caller; both wait for the stream
+void lq_fig_hist_dev(hipStream_t s, int dtype, const void *d_x, u64 n, const double *edges, u32 n_edges, u64 *counts)
+{
+	const u32 nb = n_edges - 1;
+	DBuf d_e, d_c;
+	upload(d_e, edges, (size_t)n_edges * 8, s);
+	d_c.ensure((size_t)nb * 8);
+	LQ_HIP_CHECK(hipMemsetAsync(d_c.p, 0, (size_t)nb * 8, s));
+	const u32 grid = grid_for(n, LQ_FIG_THREADS);
+	if (dtype == LQFIG_F32) LQ_LAUNCH(k_fig_hist<float>, grid, LQ_FIG_THREADS, s, (const float*)d_x, (u64)n, d_e.as<double>(), n_edges, d_c.as<unsigned long long>());
+	else LQ_LAUNCH(k_fig_hist<u32>, grid, LQ_FIG_THREADS, s, (const u32*)d_x, (u64)n, d_e.as<double>(), n_edges, d_c.as<unsigned long long>());
+	LQ_HIP_CHECK(hipGetLastError());
+	LQ_HIP_CHECK(hipMemcpyAsync(counts, d_c.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+	LQ_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void lq_fig_logsum_dev(hipStream_t s, const u32 *d_x, u64 n, uint64_t *sum, double *sum_log, uint64_t *n_zero)
+{
+	const u64 n_tiles = (n + LQ_FIG_TILE - 1) / LQ_FIG_TILE;
+	DBuf d_tot, d_part;
+	d_tot.ensure(16);
+	LQ_HIP_CHECK(hipMemsetAsync(d_tot.p, 0, 16, s));
+	d_part.ensure((size_t)n_tiles * 8);
+	LQ_LAUNCH(k_fig_logsum, grid_for(n_tiles, LQ_FIG_THREADS / 64), LQ_FIG_THREADS, s, d_x, (u64)n, d_tot.as<unsigned long long>(), d_part.as<double>());
+	LQ_HIP_CHECK(hipGetLastError());
+	unsigned long long tot[2];
+	LQ_HIP_CHECK(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, s));
+	fold(d_part, n_tiles, 1, sum_log, s);                     // (waits for the stream)
+	*sum = tot[0]; *n_zero = tot[1];
+}
+
 extern "C" {
 
 int lqfig_range(int device, int dtype, const void *x, uint64_t n, void *min_out, void *max_out, char *errbuf, size_t errbuf_len)
@@ -93,17 +126,9 @@ int lqfig_hist(int device, int dtype, const void *x, uint64_t n, const double *e
 		for (u32 k = 0; k < nb; ++k) counts[k] = 0;
 		if (n == 0) return;
 		lq_cabi::ScopedStream s(device);
-		DBuf d_x, d_e, d_c;
+		DBuf d_x;
 		upload(d_x, x, (size_t)n * 4, s);
-		upload(d_e, edges, (size_t)n_edges * 8, s);
-		d_c.ensure((size_t)nb * 8);
-		LQ_HIP_CHECK(hipMemsetAsync(d_c.p, 0, (size_t)nb * 8, s));
-		const u32 grid = grid_for(n, LQ_FIG_THREADS);
-		if (dtype == LQFIG_F32) LQ_LAUNCH(k_fig_hist<float>, grid, LQ_FIG_THREADS, s, d_x.as<float>(), (u64)n, d_e.as<double>(), n_edges, d_c.as<unsigned long long>());
-		else LQ_LAUNCH(k_fig_hist<u32>, grid, LQ_FIG_THREADS, s, d_x.as<u32>(), (u64)n, d_e.as<double>(), n_edges, d_c.as<unsigned long long>());
-		LQ_HIP_CHECK(hipGetLastError());
-		LQ_HIP_CHECK(hipMemcpyAsync(counts, d_c.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
-		LQ_HIP_CHECK(hipStreamSynchronize(s));
+		lq_fig_hist_dev(s, dtype, d_x.p, n, edges, n_edges, counts);
 	});
 }
 
@@ -138,18 +163,9 @@ int lqfig_logsum(int device, const uint32_t *x, uint64_t n, uint64_t *sum, doubl
 		*sum = 0; *sum_log = 0.0; *n_zero = 0;
 		if (n == 0) return;
 		lq_cabi::ScopedStream s(device);
-		const u64 n_tiles = (n + LQ_FIG_TILE - 1) / LQ_FIG_TILE;
-		DBuf d_x, d_tot, d_part;
+		DBuf d_x;
 		upload(d_x, x, (size_t)n * 4, s);
-		d_tot.ensure(16);
-		LQ_HIP_CHECK(hipMemsetAsync(d_tot.p, 0, 16, s));
-		d_part.ensure((size_t)n_tiles * 8);
-		LQ_LAUNCH(k_fig_logsum, grid_for(n_tiles, LQ_FIG_THREADS / 64), LQ_FIG_THREADS, s, d_x.as<u32>(), (u64)n, d_tot.as<unsigned long long>(), d_part.as<double>());
-		LQ_HIP_CHECK(hipGetLastError());
-		unsigned long long tot[2];
-		LQ_HIP_CHECK(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, s));
-		fold(d_part, n_tiles, 1, sum_log, s);                     // (waits for the stream)
-		*sum = tot[0]; *n_zero = tot[1];
+		lq_fig_logsum_dev(s, d_x.as<u32>(), n, sum, sum_log, n_zero);
 	});
 }
 

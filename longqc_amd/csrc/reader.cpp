@@ -688,6 +688,21 @@ template <class F> int one_shot(F &&f)
 
 } // namespace
 
+// ---- k_bgzf_inflate for another byte loop (polread.cpp; the kernel is compiled in this file alone): the listed blocks of `win` are
+// inflated to d_out + at + their .out, one status per block as BgzfInflater's device hook wants them.  Waits for the stream ----
+struct LqDevInflate { InflateDev inf; };
+LqDevInflate *lq_dev_inflate_new() { return new LqDevInflate(); }
+void lq_dev_inflate_free(LqDevInflate *d) { delete d; }
+void lq_dev_inflate_run(LqDevInflate *d, hipStream_t stream, const std::vector<BgzfInflater::Block> &blocks, const u8 *win, u8 *d_out, u64 at, std::vector<u32> &status)
+{
+	status.assign(blocks.size(), 0);
+	if (blocks.empty()) return;
+	const u64 lo = blocks.front().in & ~(u64)15, hi = blocks.back().in + blocks.back().in_len;
+	std::vector<InflateJob> jobs(blocks.size());
+	for (size_t i = 0; i < blocks.size(); ++i) jobs[i] = {blocks[i].in - lo, at + blocks[i].out, (u32)blocks[i].in_len, (u32)blocks[i].isize};
+	d->inf.run(stream, win + lo, hi - lo, jobs, d_out, status.data());
+}
+
 extern "C" {
 
 lqreader *lqreader_open(const char *path, int device, uint64_t chunk_size, int is_upper, uint32_t str_overhead, int n_threads)
