@@ -363,11 +363,7 @@ int lqcov_part_add_packed_shares_dev(lqcov_handle *h, int part, const uint64_t *
 int lqcov_part_clear(lqcov_handle *h, int part)
 {
 	return guard(h, [&] {
-		Part &pt = h->part(part);
-		ReadSetDev &rs = pt.rs;
-		rs.n = 0; rs.n_chunks = 0; rs.n_bases = 0; rs.n_mini = 0; rs.sketched = false; rs.dp_n = 0; rs.dp_tiles = 0;
-		rs.h_coff.assign(1, 0); rs.h_len.clear(); rs.names.clear();
-		pt.built = false; pt.n_keys = 0;
+		h->part(part).clear();
 		h->sat_last_valid = false;
 	});
 }

@@ -7,8 +7,7 @@
 #include "kernels_walk.hpp"
 #include "kernels_psort.hpp"
 #include "kernels_chain.hpp"
-#include "fastx.hpp"
-#include "fastx_mem.hpp"
+#include "mmi.hpp"
 #include "sat_replay.hpp"
 #ifndef LQ_EMU
 extern "C" void lq_segv_altstack();                      // api.cpp (LQCOV_SEGV_TRACE)
@@ -2349,70 +2348,7 @@ void lqcov_handle::finish()
 	finished = true;
 }
 
-// rows as text (minimap2-coverage.c:567-605); name_of(i) = the name of the query of row i
-void lq_format_rows(FILE *out, int filter_flag, const lqcov_row *rows, u32 n_rows, const lqcov_region *regs, const lqcov_region *mregs,
-                    const std::function<const char *(u32)> &name_of)
-{
-	std::string line;
-	char buf[128];
-	for (u32 i = 0; i < n_rows; ++i) {
-		const lqcov_row &r = rows[i];
-		const double div = r.n_match > 0 ? logf((float)r.n_mini / (float)(int32_t)r.n_match) / r.avg_k : 1.0;   // :563
-		double mq;
-		if (r.has_qual) mq = -10 * log10(r.qual_psum / (int)r.qlen);                                          // lqutils.c:57
-		else { volatile double z = 0.0; volatile int zl = 0; mq = -10 * log10(z / zl); }                                      // FASTA query: the reference's 0/0
-		line.clear();
-		line += name_of(i); line += '\t';
-		snprintf(buf, sizeof(buf), "%d\t%" PRIu64 "\t", (int)r.qlen, r.lambda); line += buf;
-		if (r.n_reg > 0) {
-			u32 tot = 0;
-			for (u32 k = 0; k < r.n_reg; ++k) {
-				const lqcov_region &g = regs[r.reg_off + k];
-				snprintf(buf, sizeof(buf), "%s%d-%d", k ? "," : "", (int)g.start, (int)g.end); line += buf;
-				tot += g.end - g.start;
-			}
-			line += '\t';
-			if (r.n_mreg > 0) {
-				for (u32 k = 0; k < r.n_mreg; ++k) {
-					const lqcov_region &g = mregs[r.mreg_off + k];
-					snprintf(buf, sizeof(buf), "%s%d-%d", k ? "," : "", (int)g.start, (int)g.end); line += buf;
-				}
-			} else line += '0';
-			if (filter_flag) snprintf(buf, sizeof(buf), "\t%.3f\t%.3f\t%.3f\t0.0\n", (double)tot / (int)r.qlen, mq, div);
-			else snprintf(buf, sizeof(buf), "\t%.3f\t%.3f\t%.3f\t%.3f\n", (double)r.lambda / tot, mq, div, (double)r.lambda2 / tot);
-			line += buf;
-		} else {
-			snprintf(buf, sizeof(buf), "0\t0\t0.0\t%.3f\t%.3f\t0.0\n", mq, div); line += buf;
-		}
-		fwrite(line.data(), 1, line.size(), out);
-	}
-}
-
-void lqcov_handle::write_table(FILE *out)
-{
-	if (!finished) throw std::logic_error("finish() has not run");
-	lq_format_rows(out, P.filter_flag, rows.data(), q.n, regs.data(), mregs.data(), [&](u32 i) { return q.names[q_inv[i]].c_str(); });
-}
-
-void lqcov_handle::write_table_set(u32 set, FILE *out)
-{
-	if (!finished) throw std::logic_error("finish() has not run");
-	if (set + 1 >= set_first.size()) throw std::invalid_argument("no such query set");
-	const u32 a = set_first[set];
-	lq_format_rows(out, P.filter_flag, rows.data() + a, set_first[set + 1] - a, regs.data(), mregs.data(), [&](u32 i) { return q.names[q_inv[a + i]].c_str(); });
-}
-
-// ---- the whole run from files (minimap2-coverage.c:406-617) -----------------------------------------
 // ---- prebuilt indexes: the reference's .mmi files (index.c:385-540) ----------------------------------
-#define LQ_MMI_MAGIC "MMI\2"
-#define LQ_MMI_BUCKET_BITS 14           // mm_idxopt_init (index.c:33); the option table has no switch for it
-#define LQ_MMI_NO_SEQ 0x2
-
-static void fwrite_or_throw(const void *p, size_t sz, size_t n, FILE *fp)
-{
-	if (n && fwrite(p, sz, n, fp) != n) throw std::runtime_error("write to the index dump failed");
-}
-
 // A prebuilt index brings its own k, w and -H (index.c:529-531), which the mapping then uses (lqmap.c:126-138), while the
 // reference has already sized every query's counter array -- and with it the n of the count statistics -- from a sketch
 // with the command-line values (minimap2-coverage.c:419-422, 552-563).  Keep those sizes, sketch the queries again with
@@ -2472,10 +2408,7 @@ void lqcov_handle::build_part_from_host_minimizers(Part &pt, const std::vector<u
 	build_index(pt);
 }
 
-// One part in the reference's on-disk layout.  What a reader needs is reproduced exactly (header, names with their
-// one-byte length, per-bucket position arrays with every list ascending, key = minimizer>>b<<1 | singleton, value = the
-// position or start<<32 | n, 4-bit sequences); the order of the (key, value) pairs inside a bucket is ascending key here,
-// khash slot order in the reference -- mm_idx_load re-inserts them one by one, so the order is immaterial.
+// One part as mmi.hpp lays it out: the index from the build's work space, then the sequences, 4 bits a base.
 void lqcov_handle::dump_part(Part &pt, FILE *fp)
 {
 	if (!pt.built) throw std::logic_error("part not built");
@@ -2484,53 +2417,17 @@ void lqcov_handle::dump_part(Part &pt, FILE *fp)
 	if (ix_owner != &pt) throw std::logic_error("this part's index can no longer be dumped: another part was built after it (dump a part before the next lqcov_part_build)");
 	ReadSetDev &rs = pt.rs;
 	const u64 M = rs.n_mini, K = pt.n_keys;
-	const u32 b = LQ_MMI_BUCKET_BITS, nb = 1u << b;
 	std::vector<u64> hkey(K), hstart(K), hpos(M);
 	std::vector<u32> hcnt(K);
 	if (K) {
 		d2h(hkey.data(), ix_ukey.as<u64>(), K, stream); d2h(hstart.data(), ix_ustart.as<u64>(), K, stream);
 		d2h(hcnt.data(), ix_ucnt.as<u32>(), K, stream); d2h(hpos.data(), pt.pos.as<u64>(), M, stream);
 	}
-	u32 hdr[5] = {(u32)P.w, (u32)P.k, b, rs.n, (u32)(P.hpc ? 1 : 0)};
-	fwrite_or_throw(LQ_MMI_MAGIC, 1, 4, fp);
-	fwrite_or_throw(hdr, 4, 5, fp);
-	u64 sum_len = 0;
-	std::vector<u64> boff(rs.n + 1, 0);
-	for (u32 i = 0; i < rs.n; ++i) {
-		const u8 l = (u8)rs.names[i].size();                    // index.c:401: the length is stored in one byte
-		fwrite_or_throw(&l, 1, 1, fp);
-		fwrite_or_throw(rs.names[i].data(), 1, l, fp);
-		fwrite_or_throw(&rs.h_len[i], 4, 1, fp);
-		sum_len += rs.h_len[i]; boff[i + 1] = sum_len;
-	}
-	// keys by bucket (low b bits); hkey is ascending, so every bucket's keys stay ascending
-	std::vector<u64> bstart(nb + 1, 0);
-	for (u64 i = 0; i < K; ++i) ++bstart[(hkey[i] & (nb - 1)) + 1];
-	for (u32 i = 0; i < nb; ++i) bstart[i + 1] += bstart[i];
-	std::vector<u64> order(K), fill(bstart.begin(), bstart.end() - 1);
-	for (u64 i = 0; i < K; ++i) order[fill[hkey[i] & (nb - 1)]++] = i;
-	std::vector<u64> pbuf, kv;
-	for (u32 bi = 0; bi < nb; ++bi) {
-		pbuf.clear(); kv.clear();
-		for (u64 t = bstart[bi]; t < bstart[bi + 1]; ++t) {
-			const u64 i = order[t];
-			const u64 key = hkey[i] >> b << 1;
-			if (hcnt[i] == 1) { kv.push_back(key | 1); kv.push_back(hpos[hstart[i]]); }
-			else {
-				kv.push_back(key); kv.push_back((u64)pbuf.size() << 32 | hcnt[i]);
-				pbuf.insert(pbuf.end(), hpos.begin() + hstart[i], hpos.begin() + hstart[i] + hcnt[i]);
-			}
-		}
-		if (pbuf.size() > 0x7fffffffULL) throw std::domain_error("index bucket too large for the .mmi format");
-		const i32 n_p = (i32)pbuf.size();
-		const u32 size = (u32)(kv.size() / 2);
-		fwrite_or_throw(&n_p, 4, 1, fp);
-		fwrite_or_throw(pbuf.data(), 8, pbuf.size(), fp);
-		fwrite_or_throw(&size, 4, 1, fp);
-		fwrite_or_throw(kv.data(), 8, kv.size(), fp);
-	}
+	mmi_write_index(fp, MmiHeader{P.w, P.k, LQ_MMI_BUCKET_BITS, rs.n, (u32)(P.hpc ? 1 : 0)}, rs.names, rs.h_len, hkey, hstart, hcnt, hpos);
 	// mi->S
-	const u64 n_words = (sum_len + 7) / 8;
+	std::vector<u64> boff(rs.n + 1, 0);
+	for (u32 i = 0; i < rs.n; ++i) boff[i + 1] = boff[i] + rs.h_len[i];
+	const u64 n_words = (boff[rs.n] + 7) / 8;
 	if (n_words) {
 		if (rs.codes.p == nullptr) throw std::logic_error("this part has no sequences to dump (it was loaded from an index)");
 		DBuf d_boff, d_out;
@@ -2540,336 +2437,22 @@ void lqcov_handle::dump_part(Part &pt, FILE *fp)
 		check_launch();
 		std::vector<u32> hs(n_words);
 		d2h(hs.data(), d_out.as<u32>(), n_words, stream);
-		fwrite_or_throw(hs.data(), 4, n_words, fp);
+		mmi_write_seq(fp, hs);
 	}
 	fflush(fp);
 }
 
-static bool fread_exact(void *p, size_t sz, size_t n, FILE *fp) { return n == 0 || fread(p, sz, n, fp) == n; }
-
 bool lqcov_handle::load_part(FILE *fp, Part &pt)
 {
-	char magic[4];
-	if (fread(magic, 1, 4, fp) != 4) return false;              // end of file (index.c:436)
-	if (memcmp(magic, LQ_MMI_MAGIC, 4) != 0) return false;
-	u32 hdr[5];
-	if (!fread_exact(hdr, 4, 5, fp)) throw std::runtime_error("truncated index file");
-	const i32 w = (i32)hdr[0], k = (i32)hdr[1]; const u32 b = hdr[2], n_seq = hdr[3], flag = hdr[4];
-	if (k != P.k || w != P.w || ((flag & 1) != 0) != (P.hpc != 0)) throw std::logic_error("index part with other k / w / -H than the handle's (adopt_index_params first)");
-	if (b > 30) throw std::runtime_error("corrupt index file (bucket bits)");
-	std::vector<std::string> names(n_seq);
-	std::vector<u32> lens(n_seq);
-	u64 sum_len = 0;
-	for (u32 i = 0; i < n_seq; ++i) {
-		u8 l;
-		char buf[256];
-		if (!fread_exact(&l, 1, 1, fp) || !fread_exact(buf, 1, l, fp) || !fread_exact(&lens[i], 4, 1, fp)) throw std::runtime_error("truncated index file");
-		names[i].assign(buf, strnlen(buf, l));                     // the reference holds it as a C string (index.c:448-450)
-		sum_len += lens[i];
-	}
-	std::vector<u64> x, y, pbuf;
-	for (u32 bi = 0; bi < (1u << b); ++bi) {
-		i32 n_p; u32 size;
-		if (!fread_exact(&n_p, 4, 1, fp) || n_p < 0) throw std::runtime_error("truncated index file");
-		pbuf.resize((size_t)n_p);
-		if (!fread_exact(pbuf.data(), 8, (size_t)n_p, fp) || !fread_exact(&size, 4, 1, fp)) throw std::runtime_error("truncated index file");
-		for (u32 j = 0; j < size; ++j) {
-			u64 kv[2];
-			if (!fread_exact(kv, 8, 2, fp)) throw std::runtime_error("truncated index file");
-			const u64 minier = (kv[0] >> 1) << b | bi;             // index.c:69-86 read backwards
-			if (kv[0] & 1) { x.push_back(minier << 8); y.push_back(kv[1]); }
-			else {
-				const u64 st = kv[1] >> 32, n = (u32)kv[1];
-				if (st + n > (u64)n_p) throw std::runtime_error("corrupt index file (position list)");
-				for (u64 t = 0; t < n; ++t) { x.push_back(minier << 8); y.push_back(pbuf[st + t]); }
-			}
-		}
-	}
-	if (!(flag & LQ_MMI_NO_SEQ)) {                                // mi->S: not used on this path; skipped
-		const u64 bytes = (sum_len + 7) / 8 * 4;
-		if (fseeko(fp, (off_t)bytes, SEEK_CUR) != 0) throw std::runtime_error("truncated index file");
-	}
+	MmiHeader hdr;
+	if (!mmi_read_header(fp, hdr)) return false;
+	if (hdr.k != P.k || hdr.w != P.w || ((hdr.flag & 1) != 0) != (P.hpc != 0)) throw std::logic_error("index part with other k / w / -H than the handle's (adopt_index_params first)");
+	std::vector<std::string> names;
+	std::vector<u32> lens;
+	std::vector<u64> x, y;
+	mmi_read_part(fp, hdr, names, lens, x, y);
 	build_part_from_host_minimizers(pt, x, y, std::move(names), std::move(lens));
 	return true;
-}
-
-int lqcov_handle::run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path, const QuerySetFiles *sets)
-{
-	if (sets) query = nullptr;
-	const bool has_query = query || sets;
-	bool is_idx = false;
-	i32 ik = 0, iw = 0, ihpc = 0;
-	{
-		FILE *t = fopen(target, "rb");
-		if (!t) throw lq_open_error(target);
-		char magic[4]; u32 hdr[5];
-		if (fread(magic, 1, 4, t) == 4 && memcmp(magic, LQ_MMI_MAGIC, 4) == 0) {       // mm_idx_is_idx (index.c:481-498)
-			is_idx = true;
-			if (fread(hdr, 4, 5, t) != 5) { fclose(t); throw std::runtime_error("truncated index file"); }
-			iw = (i32)hdr[0]; ik = (i32)hdr[1]; ihpc = (i32)(hdr[4] & 1);
-		}
-		fclose(t);
-	}
-	if (is_idx && dump_path) throw std::domain_error("-d with a prebuilt index as the target is not supported");
-	const double t_run0 = lq_now_s();
-	// The queries (read, upload, sketch: minimap2-coverage.c:406-431) while the host makes the first part -- parse, page-locked
-	// buffers, 2-bit packing, all host work; joined before anything of the targets touches the device.
-	auto load_queries = [&]() {
-		LQ_HIP_CHECK(hipSetDevice(device));
-		ReadBatch qb;
-		if (!sets) {
-			FastxReader fq(query);
-			while (fq.read_minibatch(INT64_MAX, qb, true) > 0) {}
-		} else {                                                  // the files one after the other, each parsed as a call of its own parses it
-			std::vector<u32> first{0};
-			int with_qual = -1;
-			for (size_t f = 0; f < sets->paths.size(); ++f) {
-				FastxReader fq(sets->paths[f]);
-				ReadBatch b;
-				while (fq.read_minibatch(INT64_MAX, b, true) > 0) {}
-				if (b.size()) {
-					if (with_qual >= 0 && with_qual != (int)b.any_qual)
-						throw std::domain_error("query sets with qualities mixed with sets without: the mean quality column is per call (FASTQ and FASTA sets cannot share one)");
-					with_qual = (int)b.any_qual;
-				}
-				const u64 sb = qb.seq.size(), nb = qb.names.size();
-				qb.seq.insert(qb.seq.end(), b.seq.begin(), b.seq.end()); qb.qual.insert(qb.qual.end(), b.qual.begin(), b.qual.end());
-				qb.names.insert(qb.names.end(), b.names.begin(), b.names.end());
-				for (u32 i = 1; i < b.seq_off.size(); ++i) qb.seq_off.push_back(sb + b.seq_off[i]);
-				for (u32 i = 1; i < b.name_off.size(); ++i) qb.name_off.push_back(nb + b.name_off[i]);
-				qb.any_qual = qb.any_qual || b.any_qual;
-				first.push_back(qb.size());
-			}
-			const double tq = lq_now_s();
-			set_query_sets(qb.size(), qb.seq.data(), qb.seq_off.data(), qb.any_qual ? qb.qual.data() : nullptr, qb.names.data(), qb.name_off.data(),
-			               (u32)sets->paths.size(), first.data(), sets->med.data(), sets->good.data());
-			if (log) fprintf(log, "[lqcov] loaded %u query sequence(s) in %zu set(s), %" PRIu64 " bases, %" PRIu64 " minimizers (read %.3f s, upload + sketch %.3f s)\n", qb.size(), sets->paths.size(), qb.bases(), q.n_mini, tq - t_run0, lq_now_s() - tq);
-			return;
-		}
-		const double tq = lq_now_s();
-		set_queries(qb.size(), qb.seq.data(), qb.seq_off.data(), qb.any_qual ? qb.qual.data() : nullptr, qb.names.data(), qb.name_off.data());
-		if (log) fprintf(log, "[lqcov] loaded %u query sequence(s), %" PRIu64 " bases, %" PRIu64 " minimizers (read %.3f s, upload + sketch %.3f s)\n", qb.size(), qb.bases(), q.n_mini, tq - t_run0, lq_now_s() - tq);
-	};
-	std::future<void> queries_loaded;
-	if (has_query) {
-#ifndef LQ_EMU
-		if (!is_idx) queries_loaded = std::async(std::launch::async, load_queries);
-		else load_queries();
-#else
-		load_queries();                                           // (the test emulator runs its kernels on the calling thread, one at a time)
-#endif
-	}
-	struct QueriesJoin { std::future<void> &f; ~QueriesJoin() { if (f.valid()) { try { f.get(); } catch (...) {} } } } queries_join{queries_loaded};   // (never leave the task behind when something else throws)
-	FILE *dump = nullptr;
-	if (dump_path) { dump = fopen(dump_path, "wb"); if (!dump) throw lq_open_error(dump_path); }
-	struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } dump_closer{dump};
-	int n_parts = 0;
-	if (is_idx) {
-		if (ik != P.k || iw != P.w || (ihpc != 0) != (P.hpc != 0)) {
-			if (log) fprintf(log, "[WARNING] Indexing parameters (-k, -w or -H) overridden by parameters used in the prebuilt index.\n");
-			adopt_index_params(ik, iw, ihpc);
-		}
-		FILE *fi = fopen(target, "rb");
-		if (!fi) throw lq_open_error(target);
-		Closer fi_closer{fi};
-		for (;;) {
-			parts.emplace_back(new Part());
-			const int id = (int)parts.size() - 1;
-			parts[id]->live = true;
-			if (!load_part(fi, *parts[id])) { parts[id].reset(); break; }
-			Part &pt = *parts[id];
-			if (log) fprintf(log, "[lqcov] part %d (prebuilt): %u target sequence(s), %" PRIu64 " minimizers, %" PRIu64 " distinct, mid_occ = %d\n",
-			                 n_parts, pt.rs.n, pt.rs.n_mini, pt.n_keys, mid_occ);
-			if (has_query) map_part(pt);
-			parts[id].reset();
-			++n_parts;
-		}
-	} else {
-		// One part = mini-batches of `chunk` bases while the running total is <= -I (index.c:244,311-316).  The parts go through a
-		// pipeline of three stages that overlap: the host makes part k + 2 (a plain file: parsed by many threads from the mapping and
-		// 2-bit packed into page-locked memory, fastx_mem.hpp; gzip or a pipe: the streaming reader, one thread like the
-		// reference's kseq), the build stream uploads, sketches and indexes part k + 1, the lanes map part k.  (-d and the index-only
-		// call keep one part at a time.)
-		const int64_t chunk = (int)((u64)P.idx_mini_batch < P.batch_size ? (u64)P.idx_mini_batch : P.batch_size);   // index.c:316
-		struct HostPart {
-			bool packed = false, last = false;                         // last: the input ended inside this part
-			std::vector<ReadBatch> bs;                                 // streaming form (ASCII)
-			u64 *codes = nullptr; u32 *amb = nullptr; u64 cap_words = 0;   // packed form, page-locked
-			std::vector<u32> lens; std::vector<char> names; std::vector<u64> name_off{0};
-			u32 n = 0; u64 bases = 0;
-			std::atomic<bool> any_amb{false};                           // packed form: a read of the part holds an ambiguous base
-			bool empty() const { return packed ? n == 0 : bs.empty(); }
-			~HostPart() { if (codes) hipHostFree(codes); if (amb) hipHostFree(amb); }
-		};
-		HostPart hp[2];
-		MemFastx mf;
-		MemRecords recs;
-		struct FlatRec { const u8 *name; u32 name_len; const u8 *seq; u32 seq_len; };
-		std::vector<FlatRec> flat;
-		std::vector<std::pair<size_t, size_t>> ranges;                 // records of every part (memory path)
-		size_t next_range = 0;
-		std::unique_ptr<FastxReader> ft;
-		bool mem = K.parse_threads != 1 && mf.open(target);
-		const double t_parse0 = lq_now_s();
-		if (mem) {
-			// (records of several lines are copied out of the mapping: a wrapped FASTA of many gigabases would be held twice, so
-			// past LQCOV_PARSE_SIDE bytes of copies the file is streamed like a gzip instead, one part in memory at a time)
-			lq_parse_all(mf, K.parse_threads, K.parse_piece, recs, K.parse_side);
-			if (recs.too_wrapped) { mem = false; mf.close(); if (log) fprintf(log, "[lqcov] target records span several lines: streaming reader\n"); }
-		}
-		if (mem) {
-			const double t0 = t_parse0;
-			flat.reserve(recs.n_recs);
-			for (MemPiece &pc : recs.pieces) for (MemRec &r : pc.recs)
-				flat.push_back(FlatRec{mf.data() + r.name_off, r.name_len, (r.own ? pc.side.data() : mf.data()) + r.seq_off, r.seq_len});
-			for (const auto &rg : lq_part_ranges(flat.size(), [&](size_t i) { return (u64)flat[i].seq_len; }, P.batch_size, (u64)P.idx_mini_batch))
-				ranges.emplace_back(rg);                                // index.c:244,311-316 and bseq.c:86-98 on the record lengths
-			if (log) fprintf(log, "[lqcov] parsed %zu target sequence(s) from the mapped file in %.3f s (%zu pieces, %u parsed again in order), %zu part(s)\n",
-			                 flat.size(), lq_now_s() - t0, recs.pieces.size(), recs.reparsed, ranges.size());
-		} else ft.reset(new FastxReader(target));
-		double t_host[2] = {0, 0}, t_alloc[2] = {0, 0};
-		auto produce = [&](int slot) {
-			LQ_HIP_CHECK(hipSetDevice(device));                         // (may run on a thread of its own: page-locked allocations)
-			const double tp0 = lq_now_s();
-			struct Tm { double &t; double t0; ~Tm() { t = lq_now_s() - t0; } } tm{t_host[slot], tp0};
-			HostPart &h = hp[slot];
-			h.bs.clear(); h.n = 0; h.bases = 0; h.lens.clear(); h.names.clear(); h.name_off.assign(1, 0); h.last = false; h.any_amb.store(false);
-			if (!mem) {
-				h.packed = false;
-				u64 sum_len = 0;
-				for (;;) {
-					if (sum_len > P.batch_size) break;
-					h.bs.emplace_back();
-					if (ft->read_minibatch(chunk, h.bs.back(), false) == 0) { h.bs.pop_back(); h.last = true; break; }
-					sum_len += h.bs.back().bases();
-				}
-				for (ReadBatch &b : h.bs) h.bases += b.bases();
-				return;
-			}
-			h.packed = true;
-			if (next_range >= ranges.size()) { h.last = true; return; }
-			const size_t r0 = ranges[next_range].first, r1 = ranges[next_range].second;
-			++next_range;
-			h.last = next_range >= ranges.size();
-			h.n = (u32)(r1 - r0);
-			h.lens.resize(h.n);
-			std::vector<u64> coff(h.n + 1, 0);
-			u64 name_bytes = 0;
-			for (u32 i = 0; i < h.n; ++i) { const FlatRec &r = flat[r0 + i]; h.lens[i] = r.seq_len; coff[i + 1] = coff[i] + ((u64)r.seq_len + LQ_CHUNK - 1) / LQ_CHUNK; h.bases += r.seq_len; name_bytes += r.name_len + 1; }
-			const u64 n_words = coff[h.n] * LQ_CHUNK_WORDS;
-			const double ta0 = lq_now_s();
-			if (n_words > h.cap_words) {
-				if (h.codes) hipHostFree(h.codes);
-				if (h.amb) hipHostFree(h.amb);
-				h.codes = nullptr; h.amb = nullptr;
-				h.cap_words = n_words + n_words / 16 + 64;
-				LQ_HIP_CHECK(hipHostMalloc((void**)&h.codes, h.cap_words * 8, 0));
-				LQ_HIP_CHECK(hipHostMalloc((void**)&h.amb, h.cap_words * 4, 0));
-				t_alloc[slot] = lq_now_s() - ta0;
-			}
-			h.names.resize(name_bytes); h.name_off.resize(h.n + 1);
-			{ u64 o = 0; for (u32 i = 0; i < h.n; ++i) { const FlatRec &r = flat[r0 + i]; h.name_off[i] = o; memcpy(h.names.data() + o, r.name, r.name_len); h.names[o + r.name_len] = 0; o += r.name_len + 1; } h.name_off[h.n] = o; }
-			// pack, read by read, equal shares of bases per thread
-			int nt = K.parse_threads > 0 ? K.parse_threads : (int)std::min<unsigned>(64, std::max(1u, std::thread::hardware_concurrency()));
-			std::atomic<u32> next(0);
-			auto work = [&]() {
-				for (;;) {
-					const u32 i0 = next.fetch_add(64);
-					if (i0 >= h.n) break;
-					for (u32 i = i0; i < std::min<u32>(i0 + 64, h.n); ++i) {
-						const FlatRec &r = flat[r0 + i];
-						const u64 off[2] = {0, r.seq_len};
-						lq_pack_host(1, r.seq, off, h.codes + coff[i] * LQ_CHUNK_WORDS, h.amb + coff[i] * LQ_CHUNK_WORDS, 1);
-						if (!h.any_amb.load(std::memory_order_relaxed) && lq_packed_read_ambiguous(h.amb + coff[i] * LQ_CHUNK_WORDS, r.seq_len)) h.any_amb.store(true);
-					}
-				}
-			};
-			if (nt <= 1 || h.n < 256) work();
-			else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(work); for (auto &t : th) t.join(); }
-		};
-		int n_built = 0;
-		auto build = [&](int slot, Part &pt) {                      // upload + sketch + index of hp[slot] (the build stream)
-			HostPart &h = hp[slot];
-			{	// (a Part object is used again: what lqcov_part_clear does)
-				ReadSetDev &rs = pt.rs;
-				rs.n = 0; rs.n_chunks = 0; rs.n_bases = 0; rs.n_mini = 0; rs.sketched = false; rs.dp_n = 0; rs.dp_tiles = 0;
-				rs.h_coff.assign(1, 0); rs.h_len.clear(); rs.names.clear();
-				pt.built = false; pt.n_keys = 0; pt.live = true;
-			}
-			const double tb0 = lq_now_s();
-			if (h.packed) add_reads_packed(pt.rs, h.n, h.codes, h.any_amb.load() || K.upload_amb ? h.amb : nullptr, h.lens.data(), h.names.data(), h.name_off.data());   // (a part without an N: the codes alone cross PCIe)
-			else for (ReadBatch &tb : h.bs) { add_reads(pt.rs, tb.size(), tb.seq.data(), tb.seq_off.data(), tb.names.data(), tb.name_off.data()); tb = ReadBatch(); }
-			const double tu = lq_now_s();
-			sketch(pt.rs, true);
-			const double ts = lq_now_s();
-			build_index(pt);
-			if (log) fprintf(log, "[lqcov] part %d: %u target sequence(s), %" PRIu64 " bases, %" PRIu64 " minimizers, %" PRIu64 " distinct, mid_occ = %d  (host %.3f s of which page-locked allocation %.3f, upload %.3f s, sketch %.3f s, index %.3f s)\n",
-			                 n_built, pt.rs.n, pt.rs.n_bases, pt.rs.n_mini, pt.n_keys, mid_occ, t_host[slot], t_alloc[slot], tu - tb0, ts - tu, lq_now_s() - ts);
-			++n_built;
-			if (dump) dump_part(pt, dump);                          // mm_idx_reader_read (index.c:533)
-		};
-#ifndef LQ_EMU
-		const bool pipeline = K.pipeline && has_query && !dump && profiling != 1;
-#else
-		const bool pipeline = false;                                // (the test emulator runs one kernel at a time, on the calling thread)
-#endif
-		parts.emplace_back(new Part()); parts.emplace_back(new Part());
-		Part *dev[2] = { parts[parts.size() - 2].get(), parts[parts.size() - 1].get() };
-		produce(0);
-		if (queries_loaded.valid()) queries_loaded.get();          // (a query file that cannot be read: reported here)
-		if (!hp[0].empty()) {
-			std::future<void> fut_h;
-			if (!hp[0].last) fut_h = std::async(std::launch::async, produce, 1);
-			build(0, *dev[0]);
-			// the lanes size their work space from what is free when the first part stands: leave room for the part that is built meanwhile
-			if (pipeline && !hp[0].last && hbm_reserve == 0) hbm_reserve = (u64)((double)std::min<u64>(hp[0].bases, P.batch_size + (u64)chunk) * 9.5);
-			for (int k = 0;; ++k) {
-				const int cur = k & 1, nxt = cur ^ 1;
-				std::future<bool> next_ready;
-				auto advance = [&, k, nxt]() -> bool {                  // part k + 1 from the host, then the host starts on part k + 2
-					LQ_HIP_CHECK(hipSetDevice(device));
-					if (!fut_h.valid()) return false;
-					fut_h.get();
-					if (hp[nxt].empty()) return false;
-					build(nxt, *dev[nxt]);
-					if (!hp[nxt].last) fut_h = std::async(std::launch::async, produce, nxt ^ 1);   // (slot of part k: uploaded long ago)
-					return true;
-				};
-				if (pipeline) next_ready = std::async(std::launch::async, advance);
-				if (has_query) {
-					const double tm0 = lq_now_s();
-					map_part(*dev[cur]);
-					if (log) fprintf(log, "[lqcov] part %d: mapped %u queries in %.3f s, %" PRIu64 " anchors (%" PRIu64 " written; so far %" PRIu64 " runs of %" PRIu64 " queries chained in klib's order, %" PRIu64 " anchors)\n",
-					                 n_parts, q.n, lq_now_s() - tm0, last_n_anchors, last_n_written, (u64)stat_sens_runs, (u64)stat_p2_queries, (u64)stat_p2_anchors);
-				}
-				++n_parts;
-				const bool more = pipeline ? next_ready.get() : advance();
-				if (!more) break;
-			}
-			if (fut_h.valid()) fut_h.get();
-		}
-		for (Part *d : dev) for (auto &up : parts) if (up.get() == d) up.reset();
-	}
-	if (!has_query) return 0;                                         // index only (minimap2-coverage.c:460-468)
-	const double tf0 = lq_now_s();
-	finish();
-	if (sets) for (size_t f = 0; f < sets->outs.size(); ++f) write_table_set((u32)f, sets->outs[f]);
-	else write_table(out);
-	if (log) fprintf(log, "[lqcov] rows and table in %.3f s; the whole call %.3f s (device allocations of this process so far: %.3f s for %.1f GB)\n", lq_now_s() - tf0, lq_now_s() - t_run0,
-	                 (double)lq_alloc_ns * 1e-9, (double)lq_alloc_bytes * 1e-9);
-	// A uint16 match counter that reaches 65535 makes the reference's result depend on the order in which it processed the
-	// chains (esterr.c:130,136 test a[st], not a[j]).  Such a query's counters were replayed in that order (sat_replay_part) and its
-	// row is the reference's; only counters that reached the limit after being summed over ranks (accum_import) cannot be, and
-	// then the run says so and does not report success.
-	u32 n_sat = 0, n_rep = 0;
-	for (u32 i = 0; i < q.n; ++i) if (rows[i].flags & LQCOV_ROW_SATURATED) {
-		if (rows[i].flags & LQCOV_ROW_REPLAYED) { ++n_rep; continue; }
-		if (log && n_sat < 10) fprintf(log, "[WARNING] query %s: a match counter reached 65535 (esterr.c:130,136) in counters merged from several ranks: its row is not guaranteed to equal the reference's\n", q.names[q_inv[i]].c_str());
-		++n_sat;
-	}
-	if (log && n_rep) fprintf(log, "[lqcov] %u quer%s with a match counter at its 16-bit limit (esterr.c:130,136): %llu chains replayed in the reference's order\n", n_rep, n_rep == 1 ? "y" : "ies", (unsigned long long)stat_sat_chains);
-	if (n_sat) throw std::domain_error(std::to_string(n_sat) + " quer" + (n_sat == 1 ? "y" : "ies") + " with a saturated uint16 match counter (esterr.c:130,136) in merged counters: table written, rows flagged LQCOV_ROW_SATURATED without LQCOV_ROW_REPLAYED are not guaranteed");
-	return 0;
 }
 
 // ---- tests: the device-wide primitives on host arrays (lqcov_debug_sort_pairs / lqcov_debug_scan) ----------------------------------

@@ -135,6 +135,13 @@ struct Part {
 	u64 n_keys = 0;
 	DBuf self_off, self_rid;              // per query: same-name targets (lqmap.c:180-186)
 	DBuf t_rank, q_lo;                    // -X only: name ranks for strcmp(qname, tname) > 0 (lqmap.c:187)
+	// the object is used again for other reads: reads, sketch and index are forgotten, the buffers stay (lqcov_part_clear; run_files' two parts)
+	void clear()
+	{
+		rs.n = 0; rs.n_chunks = 0; rs.n_bases = 0; rs.n_mini = 0; rs.sketched = false; rs.dp_n = 0; rs.dp_tiles = 0;
+		rs.h_coff.assign(1, 0); rs.h_len.clear(); rs.names.clear();
+		built = false; n_keys = 0;
+	}
 };
 
 // One mapping lane: a stream with its own scan/sort scratch and per-batch work space.  Query batches of a part are
@@ -406,7 +413,8 @@ struct lqcov_handle {
 	void write_table(FILE *out);
 	void write_table_set(u32 set, FILE *out);
 	struct QuerySetFiles { std::vector<const char *> paths; std::vector<i32> med, good; std::vector<FILE *> outs; };
-	// sets != null: the queries are the files of `sets` (query and out are not used), one table per set
+	// the whole run from files, and the table as text above: runfiles.cpp.  sets != null: the queries are the files of `sets` (query and
+	// out are not used), one table per set
 	int run_files(const char *target, const char *query, FILE *out, FILE *log, const char *dump_path = nullptr, const QuerySetFiles *sets = nullptr);
 	void adopt_index_params(i32 k, i32 w, i32 hpc);
 	void dump_part(Part &pt, FILE *fp);                      // mm_idx_dump (index.c:390-426)
