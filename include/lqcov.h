@@ -808,6 +808,69 @@ int lqpol_fields(int device, int kind, const uint8_t *bytes, uint64_t n, uint64_
 int lqpol_twin(int kind, const uint8_t *rec, uint64_t len, uint64_t rec_no, uint32_t item[4], int64_t *control, uint32_t *flags,
                char *errbuf, size_t errbuf_len);
 
+/* ---- box-plot statistics by group over doubles (df.boxplot(column=..., by=...), lq_rs.py:17-19) -------------------------------------- */
+/* lqfig_boxstats on values that are doubles already: the same groups (key[i], or floor((double)key[i] / interval)), the same
+ * matplotlib.cbook.boxplot_stats(x, whis) per group, every operation rounded on its own.  The values are ordered by their sign-corrected
+ * bit pattern (-0.0 in front of +0.0) with two stable radix passes, by value and then by group.  There is no missing value: n == n_all.
+ * LQCOV_E_DOMAIN also for a NaN.                                                                                                        */
+typedef struct lqfig_box_f64 {
+	uint32_t group, reserved;
+	uint64_t first, n_all, n;
+	double   mid_lo, mid_hi;       /* the two middle order statistics (equal for odd n) */
+	double   q1, med, q3, whislo, whishi;
+	uint64_t n_low, n_high;
+} lqfig_box_f64;
+int lqfig_boxstats_f64(int device, const uint32_t *key, const double *x, uint64_t n, double interval, double whis,
+                       double *sorted, lqfig_box_f64 *boxes, uint32_t box_cap, uint32_t *n_boxes,
+                       char *errbuf, size_t errbuf_len);
+
+/* ---- a comma-separated table read into typed columns on the device; RS-II platform QC (lq_rs.run_platformqc) ------------------------ */
+/* The domain: one header line, ',' as the separator, no '"' anywhere, every data row with the header's field count,
+ * lines ending in "\n" or "\r\n" (a last line without either is a row), empty lines skipped.  lqcsv_want names a header column to read
+ * and its kind before any byte arrives (at most 16; of a repeated header name the first column counts); column numbers in the later
+ * calls are the order of the lqcsv_want calls.  An LQCSV_INT64 field is "[+-]?[0-9]{1,18}".  An LQCSV_DOUBLE field of at most 15
+ * significant digits and 22 decimals, without exponent, is read by the device as one IEEE division of its integer mantissa by an exact
+ * power of ten, which is the correctly rounded double; any other number is read by the host with strtod in the C locale.  Everything
+ * else -- a quote, NUL, a lone '\r', a ragged row, a missing wanted column, an empty field, text, nan, inf or 19 digits in a wanted
+ * column -- is LQCOV_E_DOMAIN with the line number and the reason; unwanted columns may hold any text.
+ * lqcsv_add_bytes: bytes[0 .. n) of the file, behind what earlier calls consumed; whole lines are taken, piece by piece, *resume is the
+ * first byte of the line that is not whole (the caller passes it again); with last != 0 that line is a row.  lqcsv_add_file: the whole
+ * file, read and uploaded piece by piece.  lqcsv_set_piece_bytes: the size of a piece (tests; 0: the default, 8 MiB).
+ * lqcsv_get: column col, n_rows int64 or double values.  lqcsv_stats: rows, fields parsed on the device, fields read by the host twin,
+ * pieces, bytes.
+ * lqcsv_lengths (after lqcsv_finish), on the resident columns: len = end_col - start_col per row (int64 columns; a value outside
+ * 0 .. 2^32-1 in any row: LQCOV_E_DOMAIN), the mask score_col > threshold (a double column), and under the mask the compacted len
+ * (LQCSV_HQ) and bases_col (LQCSV_BASES, int64, 0 .. 2^32-1), their sums, minima and maxima, and N50 / N90 of len by get_N50 / get_NXX's
+ * rule (lq_utils.py:33-53).  out: masked rows, sum / min / max of len, N50, N90, sum / min / max of the bases, 0.
+ * lqcsv_get_lengths / lqcsv_hist / lqcsv_logsum: the uint32 array `which` -- LQCSV_HQ, LQCSV_BASES (masked rows), LQCSV_LEN_ALL (every
+ * row) -- fetched, or under lqfig_hist / lqfig_logsum (logsum: LQCSV_HQ).
+ * lqcsv_boxstats: lqfig_boxstats_f64 with key = len of every row and x = the double column value_col, both where they lie.           */
+typedef struct lqcsv lqcsv;
+#define LQCSV_INT64  0
+#define LQCSV_DOUBLE 1
+#define LQCSV_STATS_WORDS 5
+#define LQCSV_LEN_WORDS 10
+#define LQCSV_HQ      0
+#define LQCSV_BASES   1
+#define LQCSV_LEN_ALL 2
+lqcsv *lqcsv_create(int device);                     /* NULL without a HIP device */
+void   lqcsv_destroy(lqcsv *p);
+const char *lqcsv_last_error(const lqcsv *p);
+int lqcsv_want(lqcsv *p, const char *name, int kind);
+int lqcsv_set_piece_bytes(lqcsv *p, uint64_t bytes);
+int lqcsv_add_bytes(lqcsv *p, const uint8_t *bytes, uint64_t n, int last, uint64_t *resume);
+int lqcsv_add_file(lqcsv *p, const char *path);
+int lqcsv_finish(lqcsv *p, uint64_t *n_rows);
+int lqcsv_get(lqcsv *p, uint32_t col, void *out);
+int lqcsv_stats(const lqcsv *p, uint64_t out[LQCSV_STATS_WORDS]);
+int lqcsv_lengths(lqcsv *p, uint32_t score_col, double threshold, uint32_t start_col, uint32_t end_col, uint32_t bases_col,
+                  uint64_t out[LQCSV_LEN_WORDS]);
+int lqcsv_get_lengths(lqcsv *p, int which, uint32_t *out);
+int lqcsv_hist(lqcsv *p, int which, const double *edges, uint32_t n_edges, uint64_t *counts);
+int lqcsv_logsum(lqcsv *p, uint64_t *sum, double *sum_log, uint64_t *n_zero);
+int lqcsv_boxstats(lqcsv *p, uint32_t value_col, double interval, double whis, double *sorted, lqfig_box_f64 *boxes, uint32_t box_cap,
+                   uint32_t *n_boxes);
+
 #ifdef __cplusplus
 }
 #endif
