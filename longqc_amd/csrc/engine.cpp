@@ -8,6 +8,7 @@
 #include "kernels_psort.hpp"
 #include "kernels_chain.hpp"
 #include "mmi.hpp"
+#include "mapplan.hpp"
 #include "sat_replay.hpp"
 #ifndef LQ_EMU
 extern "C" void lq_segv_altstack();                      // api.cpp (LQCOV_SEGV_TRACE)
@@ -1122,7 +1123,7 @@ void lqcov_handle::part_sat_records(Part &pt, u32 qi, std::vector<SatRec> &recs,
 	if (!pt.built) throw std::logic_error("part not built");
 	if (!plan_usable(pt.plan)) plan_part(pt, stream, prim);   // (as map_part does)
 	swap_plan(pt.plan);
-	struct PlanGuard { lqcov_handle *h; SeedPlan &S; ~PlanGuard() { h->swap_plan(S); } } plan_guard{this, pt.plan};
+	PlanGuard plan_guard{this, pt.plan};
 	sat_chains(pt, qi, pt.plan.h_aq, pt.plan.h_qmoff, recs, at);
 	LQ_HIP_CHECK(hipStreamSynchronize(lanes[0]->stream));
 }
@@ -1137,6 +1138,21 @@ void lqcov_handle::sat_replay_host(u32 qi, const SatRec *recs, u64 n_recs, const
 	std::copy(c.begin(), c.end(), counters);
 }
 
+AvaView Part::ava(const lqcov_params &p) const { return AvaView{p.ava ? t_rank.as<u32>() : nullptr, p.ava ? q_lo.as<u32>() : nullptr}; }
+
+// k_seed_emit's one argument list.  Its callers differ in the grid (by the batch's minimizers, or by (block of a query's minimizers, query
+// of the subset)), the batch's minimizers and first anchor, who goes through klib's passes (qzero: nobody), the subset, the stage's bytes.
+void lqcov_handle::emit_hits(MapLane &L, Part &pt, dim3 grid, u64 j0, u64 nj, u64 a_base, const u32 *klib, const EmitSub &sub, u64 bytes)
+{
+	StageTimer t(this, L.stream, "k_seed_emit", bytes);
+	LQ_LAUNCH(k_seed_emit, grid, LQ_EMIT_THREADS, L.stream, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), q.moff.as<u64>(), j0, nj,
+	          pt.pos.as<u64>(), hit_start.as<u64>(), hit_n.as<u32>(), keep.as<u32>(), dup.as<u32>(),
+	          a_off.as<u64>(), a_base, mp_off.as<u64>(), q.d_len.as<u32>(),
+	          (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), pt.ava(P),
+	          klib, L.A.as<mm128>(), L.B.as<mm128>(), mini_pos.as<u64>(), sub);
+	check_launch();
+}
+
 // A subset of the queries through klib's passes and the chain kernels: every anchor of the listed queries (nothing is filtered
 // here: klib's order depends on the whole array), in the order the reference's sort leaves them.  tie_mode 2: only the runs in
 // L.want are chained (the second pass of map_batch); 0 with a sink: every run, the chains recorded for the replay of a saturated
@@ -1144,22 +1160,13 @@ void lqcov_handle::sat_replay_host(u32 qi, const SatRec *recs, u64 n_recs, const
 void lqcov_handle::map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, const std::vector<u32> &sk, const std::vector<u64> &so, u64 max_mini,
                               int tie_mode, u32 n_want, u32 ivl_cap, bool dbg, const SatSink *sink)
 {
-	const AvaView ava{P.ava ? pt.t_rank.as<u32>() : nullptr, P.ava ? pt.q_lo.as<u32>() : nullptr};
 	const u32 ns = (u32)sq.size();
 	const u64 nA2 = so.back();
 	batch_buffers(L, nA2);
 	L.sub_q.ensure(ns * 4 + 4); L.sub_off.ensure((ns + 1) * 8); L.sub_klib.ensure(ns * 4 + 4);
 	h2d(L.sub_q.as<u32>(), sq.data(), ns, L.stream); h2d(L.sub_off.as<u64>(), so.data(), ns + 1, L.stream); h2d(L.sub_klib.as<u32>(), sk.data(), ns, L.stream);
 	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));         // (the host vectors may die with the caller's turn of its loop)
-	{
-		StageTimer t(this, L.stream, "k_seed_emit", nA2 * 24);
-		LQ_LAUNCH(k_seed_emit, dim3(nblk(max_mini, LQ_EMIT_THREADS), ns), LQ_EMIT_THREADS, L.stream, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), q.moff.as<u64>(), (u64)0, (u64)0,
-		          pt.pos.as<u64>(), hit_start.as<u64>(), hit_n.as<u32>(), keep.as<u32>(), dup.as<u32>(),
-		          a_off.as<u64>(), (u64)0, mp_off.as<u64>(), q.d_len.as<u32>(),
-		          (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), ava,
-		          (const u32*)nullptr, L.A.as<mm128>(), L.B.as<mm128>(), mini_pos.as<u64>(), EmitSub{L.sub_q.as<u32>(), L.sub_off.as<u64>(), L.sub_klib.as<u32>()});
-		check_launch();
-	}
+	emit_hits(L, pt, dim3(nblk(max_mini, LQ_EMIT_THREADS), ns), 0, 0, 0, nullptr, EmitSub{L.sub_q.as<u32>(), L.sub_off.as<u64>(), L.sub_klib.as<u32>()}, nA2 * 24);
 	if (nA2) {
 		// (second pass: only the listed runs are chained -- klib's levels drop every bucket without one, k_rs_children)
 		L.prune = tie_mode == 2 && !sink; L.prune_n_want = n_want; L.prune_n_sub = ns;
@@ -1170,6 +1177,60 @@ void lqcov_handle::map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, 
 	}
 }
 
+// ---- one batch of queries [q0, q1) on a lane: map_batch drives the steps below (DESIGN, "Mapping a part, step by step") ----
+// the batch's anchors into L.A: every seed hit (klib's order everywhere, or no filter), or the survivors the part's plan holds
+void lqcov_handle::mb_emit(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_qmoff, u64 a_base, u64 nA)
+{
+	const u64 j0 = h_qmoff[q0], nj = h_qmoff[q1] - j0;
+	if (!nj) return;
+	if (K.ties_klib) emit_hits(L, pt, nblk(nj, LQ_EMIT_THREADS), j0, nj, a_base, qklib.as<u32>(), EmitSub{nullptr, nullptr, nullptr}, nj * 32 + nA * 24);
+	else if (!pt.plan.bucketed)                               // no filter: every hit, nobody through klib's passes (h_aqf == h_aq)
+		emit_hits(L, pt, nblk(nj, LQ_EMIT_THREADS), j0, nj, a_base, qzero.as<u32>(), EmitSub{nullptr, nullptr, nullptr}, nj * 32 + nA * 24);
+	else if (nA) {                                            // the survivors of the batch's queries (the part's seed plan holds them as records)
+		StageTimer t(this, L.stream, "k_seed_emit_s", nA * 24);
+		LQ_LAUNCH(k_seed_emit_s, nblk(nA, 256), 256, L.stream, surv.as<u64>(), a_base, nA, aqf_off.as<u64>(), q0, q1, SeedBits{pt.plan.rec_jb, pt.plan.rec_db},
+		          q.mx.as<u64>(), q.my.as<u64>(), q.moff.as<u64>(), q.d_len.as<u32>(), dup.as<u32>(), L.A.as<mm128>());
+		check_launch();
+	}
+}
+
+// sort and chain the batch's anchors; by default nobody goes through klib's passes and the runs that need them are listed (L.sens)
+void lqcov_handle::mb_first_pass(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_off, u64 a_base, u64 nA, u32 ivl_cap, bool dbg)
+{
+	const bool opt = !K.ties_klib;
+	const u32 nqb = q1 - q0;
+	const u64 *aqb = (opt ? aqf_off : aq_off).as<u64>() + q0;          // batch view of the per-query anchor offsets
+	const u32 *qkb = opt ? qzero.as<u32>() : qklib.as<u32>() + q0;               // (first pass: nobody goes through klib's passes)
+	std::vector<u64> rel; std::vector<u32> hk, hq;
+	if (K.debug_sort || (debug_flags & 2)) {
+		rel.resize(nqb + 1); hk.assign(nqb, 0); hq.resize(nqb);
+		for (u32 i = 0; i <= nqb; ++i) rel[i] = h_off[q0 + i] - a_base;
+		for (u32 i = 0; i < nqb; ++i) hq[i] = q0 + i;
+		if (!opt) d2h(hk.data(), qklib.as<u32>() + q0, nqb, L.stream);
+	}
+	sort_checked(L, sort_geom(pt), aqb, qkb, nqb, a_base, nA, rel, hk, opt ? 1u : 0u, hq.data());
+	if (opt && !L.gate_passed) { L.gate_passed = true; open_gate(); }          // (no walks in the first pass: the next lane may start under this batch's chains)
+	chain_stage(L, pt, aqb, a_base, nqb, q0, nullptr, nA, opt ? 1 : 0, 0, ivl_cap, dbg);
+}
+
+// second pass: the queries that own a run in which klib's order can be observed, subset by subset (lq_second_pass_subsets)
+void lqcov_handle::mb_second_pass(MapLane &L, Part &pt, u32 n_sens, const std::vector<u64> &h_aq, const std::vector<u64> &h_qmoff, u32 ivl_cap, bool dbg)
+{
+	std::vector<u64> want(n_sens);
+	d2h(want.data(), L.sens.as<u64>(), n_sens, L.stream);
+	const std::vector<SecondPassSubset> subsets = lq_second_pass_subsets(want, h_aq, h_qmoff, anchor_budget);
+	L.want.ensure(want.size() * 8);
+	h2d(L.want.as<u64>(), want.data(), want.size(), L.stream);
+	LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+	stat_sens_runs += want.size();
+	for (const SecondPassSubset &S : subsets) {
+		stat_p2_queries += S.sq.size(); stat_p2_anchors += S.so.back();
+		lq_tl("lane", L.id, "second pass begins, anchors", (double)S.so.back());
+		map_subset(L, pt, S.sq, S.sk, S.so, S.max_mini, 2, (u32)want.size(), ivl_cap, dbg, nullptr);
+		if (lq_timeline) { LQ_HIP_CHECK(hipStreamSynchronize(L.stream)); lq_tl("lane", L.id, "second pass done"); }
+	}
+}
+
 void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_aq, const std::vector<u64> &h_aqf, const std::vector<u64> &h_qmoff, bool dbg)
 {
 	// (a batch starts with an empty arena: what the lane's last batch cut from it is dead -- its kernels are ahead of this batch's on
@@ -1177,97 +1238,24 @@ void lqcov_handle::map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::ve
 	L.drop_arena_buffers();
 	lq_arena = L.arena.base ? &L.arena : nullptr;
 	struct ArenaGuard { ~ArenaGuard() { lq_arena = nullptr; } } arena_guard;
-	const int lane_id = L.id;
-	lq_tl("lane", lane_id, "batch begins, queries", (double)(q1 - q0));
+	lq_tl("lane", L.id, "batch begins, queries", (double)(q1 - q0));
 	L.gate_passed = false;
 	struct GateGuard { lqcov_handle *h; MapLane &L; ~GateGuard() { if (!L.gate_passed) { L.gate_passed = true; h->open_gate(); } } } gate_guard{this, L};
 	L.n_segs.ensure(64); L.n_ivl.ensure(4); L.n_sens.ensure(32); L.want.ensure(8);
 	const bool opt = !K.ties_klib;
 	const std::vector<u64> &h_off = opt ? h_aqf : h_aq;
 	const u64 a_base = h_off[q0], nA = h_off[q1] - a_base;
-	const u32 nqb = q1 - q0;
-	const u64 j0 = h_qmoff[q0], nj = h_qmoff[q1] - j0;
 	batch_buffers(L, nA);
-	const AvaView ava{P.ava ? pt.t_rank.as<u32>() : nullptr, P.ava ? pt.q_lo.as<u32>() : nullptr};
-	if (nj && !opt) {
-		StageTimer t(this, L.stream, "k_seed_emit", nj * 32 + nA * 24);
-		LQ_LAUNCH(k_seed_emit, nblk(nj, LQ_EMIT_THREADS), LQ_EMIT_THREADS, L.stream, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), q.moff.as<u64>(), j0, nj,
-		          pt.pos.as<u64>(), hit_start.as<u64>(), hit_n.as<u32>(), keep.as<u32>(), dup.as<u32>(),
-		          a_off.as<u64>(), a_base, mp_off.as<u64>(), q.d_len.as<u32>(),
-		          (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), ava,
-		          qklib.as<u32>(), L.A.as<mm128>(), L.B.as<mm128>(), mini_pos.as<u64>(), EmitSub{nullptr, nullptr, nullptr});
-		check_launch();
-	}
-	if (nj && opt && pt.plan.bucketed) {
-		if (nA) {                                                 // the survivors of the batch's queries (the part's seed plan holds them as records)
-			StageTimer t(this, L.stream, "k_seed_emit_s", nA * 24);
-			LQ_LAUNCH(k_seed_emit_s, nblk(nA, 256), 256, L.stream, surv.as<u64>(), a_base, nA, aqf_off.as<u64>(), q0, q1, SeedBits{pt.plan.rec_jb, pt.plan.rec_db},
-			          q.mx.as<u64>(), q.my.as<u64>(), q.moff.as<u64>(), q.d_len.as<u32>(), dup.as<u32>(), L.A.as<mm128>());
-			check_launch();
-		}
-	} else if (nj && opt) {                                       // no filter: every hit, nobody through klib's passes (h_aqf == h_aq)
-		StageTimer t(this, L.stream, "k_seed_emit", nj * 32 + nA * 24);
-		LQ_LAUNCH(k_seed_emit, nblk(nj, LQ_EMIT_THREADS), LQ_EMIT_THREADS, L.stream, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), q.moff.as<u64>(), j0, nj,
-		          pt.pos.as<u64>(), hit_start.as<u64>(), hit_n.as<u32>(), keep.as<u32>(), dup.as<u32>(),
-		          a_off.as<u64>(), a_base, mp_off.as<u64>(), q.d_len.as<u32>(),
-		          (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), ava,
-		          qzero.as<u32>(), L.A.as<mm128>(), L.B.as<mm128>(), mini_pos.as<u64>(), EmitSub{nullptr, nullptr, nullptr});
-		check_launch();
-	}
+	mb_emit(L, pt, q0, q1, h_qmoff, a_base, nA);
 	const u32 ivl_cap = (u32)std::min<u64>(nA / (P.min_cnt > 0 ? P.min_cnt : 1) + 16, 0xfffffff0ULL);
 	L.ivl.ensure((u64)ivl_cap * sizeof(Ivl));
 	dzero(L.n_ivl.p, 4, L.stream); dzero(L.n_sens.p, 32, L.stream);
-	if (nA) {
-		const u64 *aqb = (opt ? aqf_off : aq_off).as<u64>() + q0;          // batch view of the per-query anchor offsets
-		const u32 *qkb = opt ? qzero.as<u32>() : qklib.as<u32>() + q0;               // (first pass: nobody goes through klib's passes)
-		std::vector<u64> rel; std::vector<u32> hk, hq;
-		if (K.debug_sort || (debug_flags & 2)) {
-			rel.resize(nqb + 1); hk.assign(nqb, 0); hq.resize(nqb);
-			for (u32 i = 0; i <= nqb; ++i) rel[i] = h_off[q0 + i] - a_base;
-			for (u32 i = 0; i < nqb; ++i) hq[i] = q0 + i;
-			if (!opt) d2h(hk.data(), qklib.as<u32>() + q0, nqb, L.stream);
-		}
-		sort_checked(L, sort_geom(pt), aqb, qkb, nqb, a_base, nA, rel, hk, opt ? 1u : 0u, hq.data());
-		if (opt && !L.gate_passed) { L.gate_passed = true; open_gate(); }          // (no walks in the first pass: the next lane may start under this batch's chains)
-		chain_stage(L, pt, aqb, a_base, nqb, q0, nullptr, nA, opt ? 1 : 0, 0, ivl_cap, dbg);
-	}
-	u32 n_sens = 0;
-	if (nA && opt) {
-		u32 ns8[8] = {0};                                         // [0] listed runs, [1..6] by reason (lq_tie_list)
-		d2h(ns8, L.n_sens.as<u32>(), 8, L.stream);
-		n_sens = ns8[0];
-		for (int i = 1; i <= 6; ++i) stat_tie_why[i - 1] += ns8[i];
-	}
-	lq_tl("lane", lane_id, "first pass done, anchors", (double)nA);
-	if (n_sens) {
-		// ---- second pass: the queries that own a run in which klib's order can be observed ----
-		std::vector<u64> want(n_sens);
-		d2h(want.data(), L.sens.as<u64>(), n_sens, L.stream);
-		std::sort(want.begin(), want.end());
-		want.erase(std::unique(want.begin(), want.end()), want.end());
-		std::vector<u32> fq;
-		for (u64 k : want) if (fq.empty() || fq.back() != (u32)(k >> 32)) fq.push_back((u32)(k >> 32));
-		L.want.ensure(want.size() * 8);
-		h2d(L.want.as<u64>(), want.data(), want.size(), L.stream);
-		LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
-		stat_sens_runs += want.size(); stat_p2_queries += fq.size();
-		u64 max_mini = 0;
-		for (size_t i = 0; i < fq.size(); ) {
-			std::vector<u32> sq, sk; std::vector<u64> so{0};
-			size_t k = i;
-			while (k < fq.size() && (k == i || so.back() + (h_aq[fq[k] + 1] - h_aq[fq[k]]) <= anchor_budget)) {
-				const u64 len = h_aq[fq[k] + 1] - h_aq[fq[k]];
-				sq.push_back(fq[k]); sk.push_back(len > LQ_RS_MIN ? 1u : 0u); so.push_back(so.back() + len);
-				max_mini = std::max<u64>(max_mini, h_qmoff[fq[k] + 1] - h_qmoff[fq[k]]);
-				++k;
-			}
-			stat_p2_anchors += so.back();
-			lq_tl("lane", lane_id, "second pass begins, anchors", (double)so.back());
-			map_subset(L, pt, sq, sk, so, max_mini, 2, (u32)want.size(), ivl_cap, dbg, nullptr);
-			if (lq_timeline) { LQ_HIP_CHECK(hipStreamSynchronize(L.stream)); lq_tl("lane", lane_id, "second pass done"); }
-			i = k;
-		}
-	}
+	if (nA) mb_first_pass(L, pt, q0, q1, h_off, a_base, nA, ivl_cap, dbg);
+	u32 ns8[8] = {0};                                         // [0] listed runs, [1..6] by reason (lq_tie_list)
+	if (nA && opt) d2h(ns8, L.n_sens.as<u32>(), 8, L.stream);
+	for (int i = 1; i <= 6; ++i) stat_tie_why[i - 1] += ns8[i];
+	lq_tl("lane", L.id, "first pass done, anchors", (double)nA);
+	if (ns8[0]) mb_second_pass(L, pt, ns8[0], h_aq, h_qmoff, ivl_cap, dbg);
 	if (nA) {
 		// ---- filter_redundant_coords per query (lqmap.c:287) ----
 		u32 ni = 0;
@@ -1297,8 +1285,7 @@ bool lqcov_handle::filter_intervals(MapLane &L, u32 ni)
 		LQ_HIP_CHECK(hipDeviceSynchronize());
 		u32 npv = 0;
 		d2h(&npv, n_pv.as<u32>(), 1, L.stream);
-		grow_keep(pv, (u64)npv * sizeof(Ivl), need * sizeof(Ivl) * 2, L.stream);
-		pv_cap = (u32)std::min<u64>(pv.cap / sizeof(Ivl), 0xfffffff0ULL);
+		grow_pv(npv, need * sizeof(Ivl) * 2, L.stream);
 		grew = true;
 	}
 	pv_reserved = need;
@@ -1414,8 +1401,7 @@ void lqcov_handle::psort_tail(MapLane &L, int set, hipStream_t s, u64 nA, const 
 
 SortGeom lqcov_handle::sort_geom(const Part &pt)
 {
-	SortGeom g; g.n_targets = pt.rs.n;
-	for (u32 v : pt.rs.h_len) g.max_len = std::max(g.max_len, v);
+	SortGeom g; g.n_targets = pt.rs.n; g.max_len = pt.max_len();
 	return g;
 }
 
@@ -1768,22 +1754,20 @@ void lqcov_handle::open_gate()
 }
 
 // ---- the seed hits that can be part of a chain (kernels_seed.hpp) ------------------------------------------------------------
-// Host side of the bucketed filter: the geometry (slices of targets per query, segments of minimizers, chunks of queries that
-// fit the record buffer), then per chunk count -> scan -> scatter -> decide -> scan -> collect.  One host sync per chunk (the
-// survivors' total sizes the plan's array).  The plan holds the survivors of a *group* of chunks -- the queries from q_begin on
-// until LQCOV_SEED_SURV_MAX survivors are reached (ultra-long reads keep a third of tens of billions of hits): map_part maps a
-// group's batches and asks for the next group.  h_aqf / aqf_off of the group's queries count from the group's first survivor.
-bool lqcov_handle::seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u32 n_min, u32 jb, u32 db, SeedJob &J)
+// Host side of the bucketed filter: the geometry (lq_seed_geometry, mapplan.hpp: slices of targets per query, segments of
+// minimizers, chunks of queries that fit the record buffer), then per chunk count -> scan -> scatter -> decide -> scan -> collect.
+// One host sync per chunk (the survivors' total sizes the plan's array).  The plan holds the survivors of a *group* of chunks --
+// the queries from q_begin on until LQCOV_SEED_SURV_MAX survivors are reached (ultra-long reads keep a third of tens of billions
+// of hits): map_part maps a group's batches and asks for the next group.  h_aqf / aqf_off of the group's queries count from the
+// group's first survivor.
+// What the filter's kernels take, the same for every chunk of a run but di's bq, q_lo and n_qc (sf_chunk sets them)
+struct SeedRun { SeedIn in; SeedDecide dp; SeedDecIn di; SeedBits bits; u32 span_const; };
+
+// hits per kept minimizer, scanned (n_qm + 1 entries: the last one is the total); -> hits before every query
+std::vector<u64> lqcov_handle::sf_query_hits(hipStream_t s, Prim &pr, SeedWork &W, const SeedJob &J)
 {
-	std::lock_guard<std::mutex> seed_lock(seed_mu);          // (the build thread plans the next part while this part's groups are made: one at a time)
-	const u32 q_begin = J.q_begin;
-	const std::vector<u64> &h_qmoff = *J.h_qmoff;
 	const u32 n_q = q.n;
 	const u64 n_qm = q.n_mini;
-	const u32 n_targets = std::max<u32>(pt.rs.n, 1);
-	const AvaView ava{P.ava ? pt.t_rank.as<u32>() : nullptr, P.ava ? pt.q_lo.as<u32>() : nullptr};
-	const SeedBits bits{jb, db};
-	// hits per kept minimizer, scanned (n_qm + 1 entries: the last one is the total); hits before every query
 	W.hlen.ensure((n_qm + 1) * 4); W.h_off.ensure((n_qm + 1) * 8); W.hq_off.ensure((n_q + 1) * 8);
 	LQ_LAUNCH(k_hit_len, nblk(n_qm, 256), 256, s, J.hit_n, J.keep, n_qm, W.hlen.as<u32>()); check_launch();
 	dzero(W.hlen.as<u32>() + n_qm, 4, s);
@@ -1791,106 +1775,87 @@ bool lqcov_handle::seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u
 	LQ_LAUNCH(k_query_hoff, nblk(n_q + 1, 256), 256, s, q.moff.as<u64>(), W.h_off.as<u64>(), n_q, W.hq_off.as<u64>()); check_launch();
 	std::vector<u64> h_hq(n_q + 1);
 	d2h(h_hq.data(), W.hq_off.as<u64>(), n_q + 1, s);
-	// geometry
-	std::vector<SeedQ> qg(n_q);
-	for (u32 i = 0; i < q_begin; ++i) memset(&qg[i], 0, sizeof(SeedQ));
-	std::vector<SeedSeg> segs;
-	std::vector<u32> has(n_q, 0);
-	u64 max_hq = 0;
-	for (u32 i = 0; i < n_q; ++i) max_hq = std::max(max_hq, h_hq[i + 1] - h_hq[i]);
-	if (max_hq >= 0xfffffff0ULL) throw std::domain_error("more than 2^32 seed hits of one query against one index part");
-	const u64 chunk_cap = std::max<u64>(K.seed_chunk, max_hq);
-	struct Chunk { u32 q_lo, q_hi, g_lo, g_hi; u64 ne, nb, hits, h0; bool big; size_t bq_at; };
-	std::vector<Chunk> chunks;
-	std::vector<u32> bq_all;
-	const u32 q_stop = std::min(J.q_stop, n_q);
-	for (u32 i = q_begin; i < q_stop; ) {
-		Chunk c; c.q_lo = i; c.g_lo = (u32)segs.size(); c.ne = 0; c.nb = 0; c.hits = 0; c.h0 = h_hq[i]; c.big = false; c.bq_at = bq_all.size();
-		while (i < q_stop && (c.hits == 0 || c.hits + (h_hq[i + 1] - h_hq[i]) <= chunk_cap)) {
-			const u64 hq = h_hq[i + 1] - h_hq[i], nm = h_qmoff[i + 1] - h_qmoff[i];
-			SeedQ g; memset(&g, 0, sizeof(g));
-			g.seg0 = (u32)segs.size(); g.cb = c.ne; g.bk = c.nb;
-			if (hq) {
-				has[i] = 1;
-				u64 nsl = (hq + K.seed_bucket - 1) / K.seed_bucket;
-				nsl = std::min<u64>(nsl, std::min<u64>(LQ_SD_SL_BIG, std::max<u32>(n_targets / 2, 1)));
-				g.nsl = (u32)std::max<u64>(nsl, 1);
-				g.mul = g.nsl == 1 ? 0u : (u32)((((u64)g.nsl) << 32) / n_targets);       // slice of rid = rid * mul >> 32 < nsl for every rid < n_targets
-				g.nseg = (u32)((nm + K.seed_segl - 1) / K.seed_segl);
-				for (u32 p = 0; p < g.nseg; ++p) {
-					SeedSeg sg; memset(&sg, 0, sizeof(sg));
-					sg.j0 = h_qmoff[i] + (u64)p * K.seed_segl; sg.j1 = std::min<u64>(sg.j0 + K.seed_segl, h_qmoff[i + 1]); sg.q = i; sg.ord = p;
-					segs.push_back(sg);
-				}
-				if (g.nsl > LQ_SD_SL_SMALL) c.big = true;
-				c.ne += (u64)g.nsl * g.nseg; c.nb += g.nsl; c.hits += hq;
-			}
-			bq_all.push_back((u32)g.bk);
-			qg[i] = g;
-			++i;
-		}
-		bq_all.push_back((u32)c.nb);
-		c.q_hi = i; c.g_hi = (u32)segs.size();
-		if (c.ne >= 0xfffffff0ULL || c.nb >= 0x7ffffff0ULL) throw std::domain_error("seed filter: too many (query, slice, segment) pieces in one chunk");
-		chunks.push_back(c);
-	}
-	if (segs.size() >= 0x7ffffff0ULL) throw std::domain_error("seed filter: too many segments");
-	u64 max_ne = 0, max_nb = 0, max_hits = 0;
-	for (const Chunk &c : chunks) { max_ne = std::max(max_ne, c.ne); max_nb = std::max(max_nb, c.nb); max_hits = std::max(max_hits, c.hits); }
-	W.qg.ensure(qg.size() * sizeof(SeedQ) + 16); W.segs.ensure(segs.size() * sizeof(SeedSeg) + 16); W.bq.ensure(bq_all.size() * 4 + 4); W.has.ensure((u64)n_q * 4 + 4);
-	W.cnt.ensure((max_ne + 1) * 4); W.off.ensure((max_ne + 1) * 4); W.scnt.ensure((max_nb + 1) * 4); W.soff.ensure((max_nb + 1) * 4); W.bd.ensure((max_nb + 1) * sizeof(SeedBk)); W.big.ensure((max_nb + 2) * 4);
-	W.rec.ensure(max_hits * 8 + 8);
-	h2d(W.qg.as<SeedQ>(), qg.data(), qg.size(), s); h2d(W.segs.as<SeedSeg>(), segs.data(), segs.size(), s);
-	h2d(W.bq.as<u32>(), bq_all.data(), bq_all.size(), s); h2d(W.has.as<u32>(), has.data(), has.size(), s);
-	LQ_HIP_CHECK(hipStreamSynchronize(s));                    // (the host vectors above are pageable)
-	SeedIn in; memset(&in, 0, sizeof(in));
+	return h_hq;
+}
+
+SeedRun lqcov_handle::sf_inputs(Part &pt, SeedWork &W, const SeedJob &J, u32 n_min, u32 jb, u32 db)
+{
+	SeedRun R; memset(&R, 0, sizeof(R));
+	R.bits = SeedBits{jb, db};
+	R.span_const = (u32)(P.hpc ? 0 : P.k);
+	SeedIn &in = R.in;
 	in.segs = W.segs.as<SeedSeg>(); in.qg = W.qg.as<SeedQ>(); in.h_off = W.h_off.as<u64>(); in.hit_start = J.hit_start; in.pos = pt.pos.as<u64>();
 	in.qx = q.mx.as<u64>(); in.qy = q.my.as<u64>(); in.qmoff = q.moff.as<u64>(); in.qlen = q.d_len.as<u32>();
-	SeedDecide dp; memset(&dp, 0, sizeof(dp));
+	SeedDecide &dp = R.dp;
 	dp.n_min = n_min; dp.pair_bits = K.seed_pair_bits; dp.hwords = K.seed_hwords; dp.dcap = K.seed_dcap; dp.bigcap = K.seed_bigcap; dp.no_self = (int)P.no_self;
-	for (u32 v : pt.rs.h_len) dp.max_tlen = std::max(dp.max_tlen, v);
+	dp.max_tlen = pt.max_len();
 	dp.dshift = 1; while (dp.dshift < 30 && (1u << dp.dshift) <= (u32)std::max<i32>(P.bw, 0)) ++dp.dshift;   // bins wider than the band (chain.c:55)
-	const u32 span_const = (u32)(P.hpc ? 0 : P.k);
+	SeedDecIn &di = R.di;
+	di.qg = W.qg.as<SeedQ>(); di.off = W.off.as<u32>();
+	di.qx = q.mx.as<u64>(); di.qy = q.my.as<u64>(); di.qmoff = q.moff.as<u64>(); di.qlen = q.d_len.as<u32>();
+	di.self_off = pt.self_off.as<u32>(); di.self_rid = pt.self_rid.as<u32>(); di.ava = pt.ava(P);
+	di.tlen = pt.rs.d_len.as<u32>(); di.n_targets = pt.rs.n;
+	return R;
+}
+
+// one chunk: count -> scan -> scatter -> buckets -> decide -> scan; -> the chunk's survivors (one host sync), still in their buckets
+u32 lqcov_handle::sf_chunk(hipStream_t s, Prim &pr, SeedWork &W, SeedRun &R, const SeedChunk &c)
+{
+	const u32 ns = c.g_hi - c.g_lo;
+	dzero(W.cnt.as<u32>() + c.ne, 4, s);
+	{
+		StageTimer t(this, s, "k_seed_count", c.hits * 8);
+		LQ_LAUNCH(k_seed_count, ns, LQ_SD_THREADS, s, R.in, c.g_lo, W.cnt.as<u32>()); check_launch();
+	}
+	pr.exclusive_scan_u32_u32(W.cnt.as<u32>(), W.off.as<u32>(), c.ne + 1);
+	{
+		StageTimer t(this, s, "k_seed_scatter", c.hits * 16);
+		if (c.big) LQ_LAUNCH((k_seed_scatter<LQ_SD_SL_BIG>), ns, LQ_SD_THREADS, s, R.in, c.g_lo, W.off.as<u32>(), R.bits, R.span_const, W.rec.as<u64>());
+		else LQ_LAUNCH((k_seed_scatter<LQ_SD_SL_SMALL>), ns, LQ_SD_THREADS, s, R.in, c.g_lo, W.off.as<u32>(), R.bits, R.span_const, W.rec.as<u64>());
+		check_launch();
+	}
+	SeedDecIn &di = R.di;
+	di.bq = W.bq.as<u32>() + c.bq_at; di.q_lo = c.q_lo; di.n_qc = c.q_hi - c.q_lo;
+	dzero(W.big.p, 4, s);
+	LQ_LAUNCH(k_seed_bdesc, nblk(c.nb, 256), 256, s, di, (u32)c.nb, R.dp.dcap, W.bd.as<SeedBk>(), W.big.as<u32>()); check_launch();
+	{
+		StageTimer t(this, s, "k_seed_decide", c.hits * 8);
+		LQ_LAUNCH(k_seed_decide, (u32)c.nb, LQ_SD_DTHREADS, s, di, W.bd.as<SeedBk>(), R.dp, R.bits, R.span_const, W.rec.as<u64>(), W.scnt.as<u32>()); check_launch();
+		LQ_LAUNCH(k_seed_decide_big, (u32)std::min<u64>(c.nb, 1024), LQ_SD_DTHREADS, s, di, W.bd.as<SeedBk>(), W.big.as<u32>(), R.dp, R.bits, R.span_const, W.rec.as<u64>(), W.scnt.as<u32>()); check_launch();
+	}
+	dzero(W.scnt.as<u32>() + c.nb, 4, s);
+	pr.exclusive_scan_u32_u32(W.scnt.as<u32>(), W.soff.as<u32>(), c.nb + 1);
+	u32 n_c = 0;
+	d2h(&n_c, W.soff.as<u32>() + c.nb, 1, s);
+	return n_c;
+}
+
+bool lqcov_handle::seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u32 n_min, u32 jb, u32 db, SeedJob &J)
+{
+	std::lock_guard<std::mutex> seed_lock(seed_mu);          // (the build thread plans the next part while this part's groups are made: one at a time)
+	const u32 q_begin = J.q_begin, n_q = q.n;
+	const std::vector<u64> h_hq = sf_query_hits(s, pr, W, J);
+	const SeedGeometry G = lq_seed_geometry(h_hq, *J.h_qmoff, q_begin, J.q_stop, n_q, pt.rs.n, K.seed_bucket, K.seed_segl, K.seed_chunk);
+	// the work space by the geometry's largest chunk, the geometry itself to the device
+	W.qg.ensure(G.qg.size() * sizeof(SeedQ) + 16); W.segs.ensure(G.segs.size() * sizeof(SeedSeg) + 16); W.bq.ensure(G.bq_all.size() * 4 + 4); W.has.ensure((u64)n_q * 4 + 4);
+	W.cnt.ensure((G.max_ne + 1) * 4); W.off.ensure((G.max_ne + 1) * 4); W.scnt.ensure((G.max_nb + 1) * 4); W.soff.ensure((G.max_nb + 1) * 4); W.bd.ensure((G.max_nb + 1) * sizeof(SeedBk)); W.big.ensure((G.max_nb + 2) * 4);
+	W.rec.ensure(G.max_hits * 8 + 8);
+	h2d(W.qg.as<SeedQ>(), G.qg.data(), G.qg.size(), s); h2d(W.segs.as<SeedSeg>(), G.segs.data(), G.segs.size(), s);
+	h2d(W.bq.as<u32>(), G.bq_all.data(), G.bq_all.size(), s); h2d(W.has.as<u32>(), G.has.data(), G.has.size(), s);
+	LQ_HIP_CHECK(hipStreamSynchronize(s));                    // (the host vectors above are pageable)
+	SeedRun R = sf_inputs(pt, W, J, n_min, jb, db);
 	DBuf d_stats;
-	if (getenv("LQCOV_SEED_STATS")) { d_stats.ensure(64); dzero(d_stats.p, 64, s); dp.stats = d_stats.as<unsigned long long>(); }
+	if (getenv("LQCOV_SEED_STATS")) { d_stats.ensure(64); dzero(d_stats.p, 64, s); R.dp.stats = d_stats.as<unsigned long long>(); }
 	u64 n_surv = 0;
 	DBuf &SV = *J.surv;
 	SV.ensure(std::min<u64>(std::max<u64>(J.room_hint, 1024), K.seed_surv_max) * 8);   // (grows by chunk if the survivors outnumber the guess)
-	u32 q_end = q_stop;
-	for (const Chunk &c : chunks) {
-		const u32 ns = c.g_hi - c.g_lo;
-		if (!ns) continue;
-		dzero(W.cnt.as<u32>() + c.ne, 4, s);
-		{
-			StageTimer t(this, s, "k_seed_count", c.hits * 8);
-			LQ_LAUNCH(k_seed_count, ns, LQ_SD_THREADS, s, in, c.g_lo, W.cnt.as<u32>()); check_launch();
-		}
-		pr.exclusive_scan_u32_u32(W.cnt.as<u32>(), W.off.as<u32>(), c.ne + 1);
-		{
-			StageTimer t(this, s, "k_seed_scatter", c.hits * 16);
-			if (c.big) LQ_LAUNCH((k_seed_scatter<LQ_SD_SL_BIG>), ns, LQ_SD_THREADS, s, in, c.g_lo, W.off.as<u32>(), bits, span_const, W.rec.as<u64>());
-			else LQ_LAUNCH((k_seed_scatter<LQ_SD_SL_SMALL>), ns, LQ_SD_THREADS, s, in, c.g_lo, W.off.as<u32>(), bits, span_const, W.rec.as<u64>());
-			check_launch();
-		}
-		SeedDecIn di; memset(&di, 0, sizeof(di));
-		di.qg = W.qg.as<SeedQ>(); di.bq = W.bq.as<u32>() + c.bq_at; di.q_lo = c.q_lo; di.n_qc = c.q_hi - c.q_lo; di.off = W.off.as<u32>();
-		di.qx = q.mx.as<u64>(); di.qy = q.my.as<u64>(); di.qmoff = q.moff.as<u64>(); di.qlen = q.d_len.as<u32>();
-		di.self_off = pt.self_off.as<u32>(); di.self_rid = pt.self_rid.as<u32>(); di.ava = ava;
-		di.tlen = pt.rs.d_len.as<u32>(); di.n_targets = pt.rs.n;
-		dzero(W.big.p, 4, s);
-		LQ_LAUNCH(k_seed_bdesc, nblk(c.nb, 256), 256, s, di, (u32)c.nb, dp.dcap, W.bd.as<SeedBk>(), W.big.as<u32>()); check_launch();
-		{
-			StageTimer t(this, s, "k_seed_decide", c.hits * 8);
-			LQ_LAUNCH(k_seed_decide, (u32)c.nb, LQ_SD_DTHREADS, s, di, W.bd.as<SeedBk>(), dp, bits, span_const, W.rec.as<u64>(), W.scnt.as<u32>()); check_launch();
-			LQ_LAUNCH(k_seed_decide_big, (u32)std::min<u64>(c.nb, 1024), LQ_SD_DTHREADS, s, di, W.bd.as<SeedBk>(), W.big.as<u32>(), dp, bits, span_const, W.rec.as<u64>(), W.scnt.as<u32>()); check_launch();
-		}
-		dzero(W.scnt.as<u32>() + c.nb, 4, s);
-		pr.exclusive_scan_u32_u32(W.scnt.as<u32>(), W.soff.as<u32>(), c.nb + 1);
-		u32 n_c = 0;
-		d2h(&n_c, W.soff.as<u32>() + c.nb, 1, s);
+	u32 q_end = std::min(J.q_stop, n_q);
+	for (const SeedChunk &c : G.chunks) {
+		if (c.g_hi == c.g_lo) continue;
+		const u32 n_c = sf_chunk(s, pr, W, R, c);
 		if (n_surv + n_c > K.seed_surv_max && n_surv) { q_end = c.q_lo; break; }   // the group is full: this chunk opens the next one
-		if (dp.stats) fprintf(stderr, "[lqcov] seed filter: chunk of queries %u..%u: %llu hits, %llu buckets, %llu pieces, %u survivors (%llu before it; room for %zu)\n",
-		                      c.q_lo, c.q_hi, (unsigned long long)c.hits, (unsigned long long)c.nb, (unsigned long long)c.ne, n_c, (unsigned long long)n_surv, SV.cap / 8);
+		if (R.dp.stats) fprintf(stderr, "[lqcov] seed filter: chunk of queries %u..%u: %llu hits, %llu buckets, %llu pieces, %u survivors (%llu before it; room for %zu)\n",
+		                        c.q_lo, c.q_hi, (unsigned long long)c.hits, (unsigned long long)c.nb, (unsigned long long)c.ne, n_c, (unsigned long long)n_surv, SV.cap / 8);
 		if ((n_surv + n_c) * 8 > SV.cap) {
 			try { grow_keep(SV, n_surv * 8, (n_surv + n_c) * 8, s); }
 			catch (const LqOutOfMemory &) { (void)hipGetLastError(); SV.release(); return false; }   // (no room for the survivors: the part is mapped without the filter)
@@ -1903,11 +1868,11 @@ bool lqcov_handle::seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u
 	if (J.h_aqf->size() != (size_t)n_q + 1) J.h_aqf->assign(n_q + 1, 0);
 	d2h(J.h_aqf->data() + q_begin, J.aqf_off + q_begin, q_end - q_begin + 1, s);
 	J.q_end = q_end; J.n_surv = n_surv;
-	if (dp.stats) {
+	if (R.dp.stats) {
 		unsigned long long st[8];
-		d2h(st, dp.stats, 8, s);
+		d2h(st, R.dp.stats, 8, s);
 		fprintf(stderr, "[lqcov] seed filter: %llu hits in %zu chunks, %zu segments; pairs with %u hits hold %llu (%.2f %%), survivors %llu (%.2f %%) of the queries %u..%u; %llu buckets beyond the block (%llu of them by pairs only), %llu pairs left without a histogram\n",
-		        st[0], chunks.size(), segs.size(), n_min, st[1], st[0] ? 100.0 * st[1] / st[0] : 0.0, st[2], st[0] ? 100.0 * st[2] / st[0] : 0.0, q_begin, q_end, st[3], st[5], st[4]);
+		        st[0], G.chunks.size(), G.segs.size(), n_min, st[1], st[0] ? 100.0 * st[1] / st[0] : 0.0, st[2], st[0] ? 100.0 * st[2] / st[0] : 0.0, q_begin, q_end, st[3], st[5], st[4]);
 	}
 	return true;
 }
@@ -1927,8 +1892,78 @@ bool lqcov_handle::seed_group(Part &pt, SeedPlan &S, bool swapped, hipStream_t s
 	return true;
 }
 
+// seed_group; false as well where it ran out of memory (its bucket buffer is up to 8 GB): the caller goes on without the filter
+bool lqcov_handle::seed_group_or_not(Part &pt, SeedPlan &S, bool swapped, hipStream_t s, Prim &pr, u32 q_begin)
+{
+	try { return seed_group(pt, S, swapped, s, pr, q_begin); }
+	catch (const LqOutOfMemory &) { (void)hipGetLastError(); if (!swapped) S.surv.release(); seed_ws.release_large(); return false; }
+}
+
+// The queries from `from` on without the filter: every hit of theirs is written (h_aqf == h_aq).  aqf / aq: the plan's aqf_off and aq_off, where they are now
+void lqcov_handle::rest_unfiltered(SeedPlan &S, DBuf &aqf, const DBuf &aq, u32 from, hipStream_t s)
+{
+	S.bucketed = false; S.q_begin = from; S.q_end = S.n_q;
+	S.h_aqf = S.h_aq;
+	LQ_HIP_CHECK(hipMemcpyAsync(aqf.p, aq.p, ((u64)S.n_q + 1) * 8, hipMemcpyDeviceToDevice, s));
+	S.n_written = from ? S.n_written + (S.h_aq[S.n_q] - S.h_aq[from]) : S.nA_total;
+}
+
 // ---- map every query against one part (lqmap.c:207-326) -----------------------------------------
-// a part's seed plan (SeedPlan, engine.hpp) on stream s with scan scratch pr
+// A part's seed plan (SeedPlan, engine.hpp) on stream s with scan scratch pr; plan_part drives the steps below.
+// the probe of every query minimizer (where its hits start, how many, how many anchors they make, whether it is kept), then the
+// minimizers / queries whose anchors can repeat an x (kernels_psort.hpp): everything else is sorted without klib's walks
+void lqcov_handle::pp_probe_marks(Part &pt, hipStream_t s)
+{
+	SeedPlan &S = pt.plan;
+	const u32 n_q = q.n;
+	const u64 n_qm = q.n_mini;
+	{
+		StageTimer t(this, s, "k_seed_probe", n_qm * (16 + 16 + 20));
+		LQ_LAUNCH(k_seed_probe, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), n_qm,
+		          pt.tkey.as<u64>(), pt.tstart.as<u64>(), pt.tcnt.as<u32>(), pt.cap_bits, pt.pos.as<u64>(),
+		          mid_occ, (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), pt.ava(P),
+		          S.hit_start.as<u64>(), S.hit_n.as<u32>(), S.a_cnt.as<u32>(), S.keep.as<u32>());
+		check_launch();
+	}
+	u32 tbits = 10;
+	while (((u64)1 << tbits) < 2 * n_qm && tbits < 31) ++tbits;
+	S.dup_table.ensure(((u64)1 << tbits) * 4);
+	dzero(S.dup.p, n_qm * 4, s); dzero(S.qdirty.p, (u64)n_q * 4, s); dzero(S.dup_table.p, ((u64)1 << tbits) * 4, s);
+	StageTimer t(this, s, "k_dup_mark", n_qm * 24);
+	LQ_LAUNCH(k_dup_mark, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), S.a_cnt.as<u32>(), n_qm,
+	          S.dup_table.as<u32>(), tbits, S.dup.as<u32>(), S.qdirty.as<u32>());
+	check_launch();
+}
+
+// The seed hits that can be part of a chain at all (kernels_seed.hpp): records, dense per query.  Without the filter
+// (LQCOV_FILTER=0, a chain may be a single anchor, or a record would not fit 64 bits) the first pass writes every hit.
+void lqcov_handle::pp_survivors(Part &pt, hipStream_t s, Prim &pr)
+{
+	SeedPlan &S = pt.plan;
+	const u32 n_q = q.n;
+	const u64 n_qm = q.n_mini;
+	S.qzero.ensure((u64)n_q * 4 + 4); dzero(S.qzero.p, (u64)n_q * 4 + 4, s);
+	S.aqf_off.ensure((n_q + 1) * 8);
+	if (n_qm) { LQ_LAUNCH(k_mini_pos, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), S.keep.as<u32>(), S.mp_off.as<u64>(), n_qm, S.mini_pos.as<u64>()); check_launch(); }
+	const u32 n_min = K.filter ? run_n_min() : 0;
+	u32 max_qlen = 0; u64 max_nm = 1, max_hits = 0;
+	for (u32 v : q.h_len) max_qlen = std::max(max_qlen, v);
+	for (u32 i = 0; i < n_q; ++i) { max_nm = std::max<u64>(max_nm, S.h_qmoff[i + 1] - S.h_qmoff[i]); max_hits = std::max<u64>(max_hits, S.h_aq[i + 1] - S.h_aq[i]); }
+	const SeedRecordBits b = lq_seed_record_bits(max_nm, pt.max_len(), max_qlen, pt.rs.n);
+	if (S.nA_total && lq_seed_filter_fits(n_min, b, max_hits)) {
+		S.rec_nmin = n_min; S.rec_jb = b.jb; S.rec_db = b.db;
+		// (measured and dropped, round 5: the filter run batch by batch inside map_part, each lane starting as soon as its batch is
+		// decided -- 586-588 ms per step at configs[2] against 576: beside the lanes' kernels the filter's take three times as long.
+		// Round 6, for the first part of a job only, whose plan nothing else could hide -- every lane ran the filter for its own batch
+		// of queries on its own stream, the next lane deciding under this one's mapping: 425 ms per step against 399.  Beside a mapping
+		// lane and the next part's sketch the filter's kernels take twice as long (60 + 55 + 56 ms for the three batches, 85 ms for all
+		// of them alone) and the last lane starts later than it does after a whole plan; two / three batches per lane: 449 / 483 ms)
+		// (running out of memory inside the filter leaves the part without one: every hit is written)
+		S.bucketed = seed_group_or_not(pt, S, false, s, pr, 0);
+	}
+	if (!S.bucketed) rest_unfiltered(S, S.aqf_off, S.aq_off, 0, s);
+}
+
 void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr)
 {
 	SeedPlan &S = pt.plan;
@@ -1938,42 +1973,25 @@ void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr)
 	S.n_q = n_q; S.n_qm = n_qm; S.mid_occ = mid_occ; S.nA_total = 0; S.n_mp_total = 0; S.n_written = 0;
 	S.h_aq.assign(n_q + 1, 0); S.h_qmoff.assign(n_q + 1, 0); S.h_aqf.clear();
 	if (n_q == 0) { S.valid = true; return; }
-	const AvaView ava{P.ava ? pt.t_rank.as<u32>() : nullptr, P.ava ? pt.q_lo.as<u32>() : nullptr};
 	S.dup.ensure(n_qm * 4 + 4); S.qdirty.ensure((u64)n_q * 4 + 4);
 	S.hit_start.ensure(n_qm * 8 + 8); S.hit_n.ensure(n_qm * 4 + 4); S.a_cnt.ensure(n_qm * 4 + 4); S.keep.ensure(n_qm * 4 + 4);
 	S.a_off.ensure(n_qm * 8 + 8); S.mp_off.ensure(n_qm * 8 + 8);
 	S.aq_off.ensure((n_q + 1) * 8); S.mpq_off.ensure((n_q + 1) * 8); S.avg_qspan.ensure((n_q + 1) * 4);
-	u64 nA_total = 0, n_mp_total = 0;
 	if (n_qm) {
-		{
-			StageTimer t(this, s, "k_seed_probe", n_qm * (16 + 16 + 20));
-			LQ_LAUNCH(k_seed_probe, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), n_qm,
-			          pt.tkey.as<u64>(), pt.tstart.as<u64>(), pt.tcnt.as<u32>(), pt.cap_bits, pt.pos.as<u64>(),
-			          mid_occ, (int)P.no_self, pt.self_off.as<u32>(), pt.self_rid.as<u32>(), ava,
-			          S.hit_start.as<u64>(), S.hit_n.as<u32>(), S.a_cnt.as<u32>(), S.keep.as<u32>());
-			check_launch();
-		}
-		{	// minimizers / queries whose anchors can repeat an x (kernels_psort.hpp): everything else is sorted without klib's walks
-			u32 tbits = 10;
-			while (((u64)1 << tbits) < 2 * n_qm && tbits < 31) ++tbits;
-			S.dup_table.ensure(((u64)1 << tbits) * 4);
-			dzero(S.dup.p, n_qm * 4, s); dzero(S.qdirty.p, (u64)n_q * 4, s); dzero(S.dup_table.p, ((u64)1 << tbits) * 4, s);
-			StageTimer t(this, s, "k_dup_mark", n_qm * 24);
-			LQ_LAUNCH(k_dup_mark, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), q_owner.as<u32>(), S.a_cnt.as<u32>(), n_qm,
-			          S.dup_table.as<u32>(), tbits, S.dup.as<u32>(), S.qdirty.as<u32>());
-			check_launch();
-		}
+		pp_probe_marks(pt, s);
+		// where every minimizer's anchors and kept positions start, and the totals
 		pr.exclusive_scan_u32_u64(S.a_cnt.as<u32>(), S.a_off.as<u64>(), n_qm);
 		pr.exclusive_scan_u32_u64(S.keep.as<u32>(), S.mp_off.as<u64>(), n_qm);
 		u64 lo[2]; u32 lc[2];
 		d2h(&lo[0], S.a_off.as<u64>() + n_qm - 1, 1, s); d2h(&lc[0], S.a_cnt.as<u32>() + n_qm - 1, 1, s);
 		d2h(&lo[1], S.mp_off.as<u64>() + n_qm - 1, 1, s); d2h(&lc[1], S.keep.as<u32>() + n_qm - 1, 1, s);
-		nA_total = lo[0] + lc[0]; n_mp_total = lo[1] + lc[1];
+		S.nA_total = lo[0] + lc[0]; S.n_mp_total = lo[1] + lc[1];
 	}
-	S.nA_total = nA_total; S.n_mp_total = n_mp_total; S.n_written = nA_total;
-	S.mini_pos.ensure(n_mp_total * 8 + 8);
-	// (per query: anchor and mini_pos ranges, avg_qspan from the unfiltered totals; the skip verdict of esterr.c:85-91 waits for the mapping)
-	LQ_LAUNCH(k_query_prep, nblk(n_q + 1, 4), 256, s, q.moff.as<u64>(), S.a_off.as<u64>(), S.mp_off.as<u64>(), n_qm, nA_total, n_mp_total, n_q,
+	S.n_written = S.nA_total;
+	S.mini_pos.ensure(S.n_mp_total * 8 + 8);
+	// per query: anchor and mini_pos ranges, avg_qspan from the unfiltered totals (the skip verdict of esterr.c:85-91 waits for the
+	// mapping); who goes through klib's passes; the offsets to the host
+	LQ_LAUNCH(k_query_prep, nblk(n_q + 1, 4), 256, s, q.moff.as<u64>(), S.a_off.as<u64>(), S.mp_off.as<u64>(), n_qm, S.nA_total, S.n_mp_total, n_q,
 	          q.mx.as<u64>(), S.a_cnt.as<u32>(), S.keep.as<u32>(), q.d_len.as<u32>(),
 	          S.aq_off.as<u64>(), S.mpq_off.as<u64>(), S.avg_qspan.as<float>(), (const u64*)nullptr, (float*)nullptr, (u32*)nullptr, 0, 1);
 	check_launch();
@@ -1982,40 +2000,7 @@ void lqcov_handle::plan_part(Part &pt, hipStream_t s, Prim &pr)
 	d2h(S.h_aq.data(), S.aq_off.as<u64>(), n_q + 1, s);
 	d2h(S.h_qmoff.data(), q.moff.as<u64>(), n_q + 1, s);
 	S.bucketed = false;
-	if (!K.ties_klib) {
-		// The seed hits that can be part of a chain at all (kernels_seed.hpp): records, dense per query.  Without the filter
-		// (LQCOV_FILTER=0, a chain may be a single anchor, or a record would not fit 64 bits) the first pass writes every hit.
-		S.qzero.ensure((u64)n_q * 4 + 4); dzero(S.qzero.p, (u64)n_q * 4 + 4, s);
-		S.aqf_off.ensure((n_q + 1) * 8);
-		if (n_qm) { LQ_LAUNCH(k_mini_pos, nblk(n_qm, 256), 256, s, q.mx.as<u64>(), q.my.as<u64>(), S.keep.as<u32>(), S.mp_off.as<u64>(), n_qm, S.mini_pos.as<u64>()); check_launch(); }
-		const u32 n_min = K.filter ? run_n_min() : 0;
-		u32 max_tlen = 0, max_qlen = 0; u64 max_nm = 1;
-		for (u32 v : pt.rs.h_len) max_tlen = std::max(max_tlen, v);
-		for (u32 v : q.h_len) max_qlen = std::max(max_qlen, v);
-		for (u32 i = 0; i < n_q; ++i) max_nm = std::max<u64>(max_nm, S.h_qmoff[i + 1] - S.h_qmoff[i]);
-		auto bits_for = [](u64 v) { u32 b = 1; while (b < 63 && (v >> b)) ++b; return b; };   // bits that hold 0 .. v
-		const u32 jb = bits_for(max_nm - 1), db = bits_for((u64)max_tlen + max_qlen + 257), rb = bits_for(pt.rs.n ? pt.rs.n - 1 : 0);
-		u64 max_hits = 0;
-		for (u32 i = 0; i < n_q; ++i) max_hits = std::max<u64>(max_hits, S.h_aq[i + 1] - S.h_aq[i]);
-		if (n_min >= 2 && n_min <= 15 && nA_total && jb + db + 1 + rb <= 64 && db <= 31 && jb <= 31 && max_hits < 0x7fff0000ULL) {
-			S.rec_nmin = n_min; S.rec_jb = jb; S.rec_db = db;
-			// (measured and dropped, round 5: the filter run batch by batch inside map_part, each lane starting as soon as its batch is
-			// decided -- 586-588 ms per step at configs[2] against 576: beside the lanes' kernels the filter's take three times as long.
-			// Round 6, for the first part of a job only, whose plan nothing else could hide -- every lane ran the filter for its own batch
-			// of queries on its own stream, the next lane deciding under this one's mapping: 425 ms per step against 399.  Beside a mapping
-			// lane and the next part's sketch the filter's kernels take twice as long (60 + 55 + 56 ms for the three batches, 85 ms for all
-			// of them alone) and the last lane starts later than it does after a whole plan; two / three batches per lane: 449 / 483 ms)
-			// (running out of memory inside the filter -- its bucket buffer is up to 8 GB -- leaves the part without one: every hit is written)
-			try { S.bucketed = seed_group(pt, S, false, s, pr, 0); }
-			catch (const LqOutOfMemory &) { (void)hipGetLastError(); S.surv.release(); seed_ws.release_large(); S.bucketed = false; }
-		}
-		if (!S.bucketed) {
-			S.q_begin = 0; S.q_end = n_q;
-			S.h_aqf = S.h_aq;
-			LQ_HIP_CHECK(hipMemcpyAsync(S.aqf_off.p, S.aq_off.p, (n_q + 1) * 8, hipMemcpyDeviceToDevice, s));
-			S.n_written = nA_total;
-		}
-	}
+	if (!K.ties_klib) pp_survivors(pt, s, pr);
 	LQ_HIP_CHECK(hipStreamSynchronize(s));
 	S.valid = true;
 }
@@ -2095,13 +2080,114 @@ void lqcov_handle::add_lane()
 	lanes.back()->prim.stream = lanes.back()->stream;
 }
 
+// ---- one part: map_part drives the steps below (DESIGN, "Mapping a part, step by step") ----
+// the skip verdicts and the estimators' per-query inputs for this part (k_query_prep, mode 2); the pool of debug chains
+void lqcov_handle::mp_prologue(Part &pt, bool dbg)
+{
+	const u32 n_q = q.n;
+	const u64 nA_total = last_n_anchors = pt.plan.nA_total;
+	skip.ensure((n_q + 1) * 4);
+	LQ_LAUNCH(k_query_prep, nblk(n_q + 1, 4), 256, stream, q.moff.as<u64>(), a_off.as<u64>(), mp_off.as<u64>(), q.n_mini, nA_total, pt.plan.n_mp_total, n_q,
+	          q.mx.as<u64>(), a_cnt.as<u32>(), keep.as<u32>(), q.d_len.as<u32>(),
+	          aq_off.as<u64>(), mpq_off.as<u64>(), avg_qspan.as<float>(), lambda.as<u64>(), avg_k.as<float>(), skip.as<u32>(), distributed ? 0 : 1, 2);
+	check_launch();
+	last_n_written = pt.plan.n_written;
+	if (dbg) {
+		dbg_cap = nA_total / (P.min_cnt > 0 ? P.min_cnt : 1) + 16;
+		dbg_chains.ensure(dbg_cap * sizeof(ChainRec)); n_dbg.ensure(8);
+		dzero(n_dbg.p, 8, stream);
+	}
+}
+
+// every lane's work space (prim.hpp, LqArena): as much as its largest batch of this part can need, taken while the device is
+// idle -- from the stream-ordered pool (one block, handed back only when the lanes go: plain hipMalloc of tens of gigabytes
+// takes seconds here, 30 ms per GB measured).  Only where the first pass leaves few of the hits (lq_first_pass_leaves_few).
+void lqcov_handle::mp_arenas(Part &pt)
+{
+	const SeedPlan &S = pt.plan;
+	const size_t need = lq_arena_need(anchor_budget, S.nA_total);
+	const bool bucketed = !K.ties_klib && S.bucketed;
+	const bool few = lq_first_pass_leaves_few(bucketed, S.q_begin, S.n_written, bucketed ? S.h_aq[S.q_end] - S.h_aq[S.q_begin] : 0);
+	if (!few) for (auto &Lp : lanes) if (Lp->arena.base) { Lp->drop_arena_buffers(); Lp->arena.base = nullptr; Lp->arena.size = 0; Lp->arena_buf.release(); }
+	if (few) for (auto &Lp : lanes) if (Lp->arena.size < need) {
+		Lp->drop_arena_buffers();
+		Lp->arena.base = nullptr; Lp->arena.size = 0; Lp->arena.used = 0;
+		lq_alloc_stream = stream;
+		struct AllocGuard { ~AllocGuard() { lq_alloc_stream = nullptr; } } alloc_guard;
+		try { Lp->arena_buf.ensure(need); Lp->arena.base = Lp->arena_buf.as<char>(); Lp->arena.size = Lp->arena_buf.cap; }
+		catch (const LqOutOfMemory &) { (void)hipGetLastError(); }   // (no room for it in one piece: the lane allocates buffer by buffer)
+	}
+	LQ_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// pv grown to want_bytes, the npv intervals it holds kept
+void lqcov_handle::grow_pv(u32 npv, u64 want_bytes, hipStream_t s) { grow_keep(pv, (u64)npv * sizeof(Ivl), want_bytes, s); pv_cap = (u32)std::min<u64>(pv.cap / sizeof(Ivl), 0xfffffff0ULL); }
+
+// room for this part's intervals up front: growing the pool later means draining every lane (filter_intervals)
+void lqcov_handle::mp_pv_room(u64 nA_total)
+{
+	u32 npv = 0;
+	d2h(&npv, n_pv.as<u32>(), 1, stream);
+	pv_reserved = npv;
+	const u64 want = std::min<u64>((u64)npv + nA_total / 16 + 4096, 0xfffffff0ULL);
+	if (want > pv_cap) grow_pv(npv, want * sizeof(Ivl), stream);
+}
+
+// the batches on the lanes: in turn (one lane, one batch, per-kernel profiling, debug chains, the emulator), or a thread per lane
+void lqcov_handle::run_batches(Part &pt, const std::vector<std::pair<u32, u32>> &batches, bool dbg)
+{
+	const std::vector<u64> &h_aq = pt.plan.h_aq, &h_qmoff = pt.plan.h_qmoff, &h_aqf = pt.plan.h_aqf;
+	const bool can_thread =
+#ifndef LQ_EMU
+		profiling != 1 && !dbg;
+#else
+		false;
+#endif
+	const bool concurrent = can_thread && n_lanes > 1 && batches.size() > 1;
+	if (!concurrent) {
+		for (size_t i = 0; i < batches.size(); ++i) {
+			map_batch(*lanes[i % n_lanes], pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
+		}
+		for (auto &L : lanes) LQ_HIP_CHECK(hipStreamSynchronize(L->stream));
+		return;
+	}
+	std::atomic<size_t> next(0);
+	{ std::lock_guard<std::mutex> lk(gate_mu); gate_count = 0; }
+	std::vector<std::exception_ptr> errs(n_lanes);
+	std::vector<std::thread> th;
+	for (int li = 0; li < n_lanes; ++li)
+		th.emplace_back([&, li]() {
+			try {
+				LQ_HIP_CHECK(hipSetDevice(device));
+#ifndef LQ_EMU
+				lq_segv_altstack();
+#endif
+				MapLane &L = *lanes[li];
+				// (round 6: the switch that let a lane's buffers grow from HIP's stream-ordered pool -- rounds 2-4's way, under ROCm 7.2 a
+				// GPU memory fault waiting to happen, see DESIGN.md section 2 -- is gone; only the lanes' arenas come from the pool, taken once)
+				{	// staggered start: lane li begins when li batches have got past their sort (or ended), so that
+					// one lane's serial tails run under another lane's wide kernels instead of side by side
+					std::unique_lock<std::mutex> lk(gate_mu);
+					gate_cv.wait(lk, [&] { return gate_count >= li || next.load() >= batches.size(); });
+				}
+				for (;;) {
+					const size_t i = next.fetch_add(1);
+					if (i >= batches.size()) break;
+					map_batch(L, pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
+				}
+				LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
+			} catch (...) { errs[li] = std::current_exception(); next.store(batches.size()); gate_cv.notify_all(); }
+		});
+	for (auto &t : th) t.join();
+	for (auto &e : errs) if (e) { hipDeviceSynchronize(); std::rethrow_exception(e); }
+}
+
 void lqcov_handle::map_part(Part &pt)
 {
 	if (!pt.built) throw std::logic_error("part not built");
 	finished = false; sat_last_valid = false;
 	{ std::lock_guard<std::mutex> lk(sort_rec_mu); sort_recs.clear(); }
 	const u32 n_q = q.n;
-	const u64 n_qm = q.n_mini;
 	last_n_anchors = 0;
 	n_dbg_host = 0;
 	if (n_q == 0) return;
@@ -2110,173 +2196,38 @@ void lqcov_handle::map_part(Part &pt)
 	if (!plan_usable(pt.plan)) plan_part(pt, stream, prim);
 	lq_tl("main", 0, "map_part begins");
 	swap_plan(pt.plan);
-	struct PlanGuard { lqcov_handle *h; SeedPlan &S; ~PlanGuard() { h->swap_plan(S); } } plan_guard{this, pt.plan};
-	const std::vector<u64> &h_aq = pt.plan.h_aq, &h_qmoff = pt.plan.h_qmoff, &h_aqf = pt.plan.h_aqf;
-	const u64 nA_total = pt.plan.nA_total, n_mp_total = pt.plan.n_mp_total;
-	last_n_anchors = nA_total;
-	skip.ensure((n_q + 1) * 4);
-	LQ_LAUNCH(k_query_prep, nblk(n_q + 1, 4), 256, stream, q.moff.as<u64>(), a_off.as<u64>(), mp_off.as<u64>(), n_qm, nA_total, n_mp_total, n_q,
-	          q.mx.as<u64>(), a_cnt.as<u32>(), keep.as<u32>(), q.d_len.as<u32>(),
-	          aq_off.as<u64>(), mpq_off.as<u64>(), avg_qspan.as<float>(), lambda.as<u64>(), avg_k.as<float>(), skip.as<u32>(), distributed ? 0 : 1, 2);
-	check_launch();
-	last_n_written = pt.plan.n_written;
+	PlanGuard plan_guard{this, pt.plan};
+	SeedPlan &S = pt.plan;
 	const bool opt = !K.ties_klib;
 	const bool dbg = (debug_flags & 1) != 0;
-	if (dbg) {
-		dbg_cap = nA_total / (P.min_cnt > 0 ? P.min_cnt : 1) + 16;
-		dbg_chains.ensure(dbg_cap * sizeof(ChainRec)); n_dbg.ensure(8);
-		dzero(n_dbg.p, 8, stream);
-	}
-	if (anchor_budget == 0) {
-		// The first part stands (reads, minimizers, index, the build's work space -- all kept for the parts to come, of which the
-		// first is the largest: index.c:244) and so do the queries: the lanes share 85 % of what is free now.  Per anchor a lane
-		// holds A and B (32 B), one record array (8), 20 B of scratch, digit + destination (5), ~12 B of lists and per-sub-array
-		// rows, ~6 B of runs and intervals, and the buffers grow with an eighth of head room: ~95 B.
+	mp_prologue(pt, dbg);
+	if (anchor_budget == 0) {                                     // anchors a batch may hold: once per handle, unless LQCOV_ANCHOR_BUDGET states it
 		size_t fr = 0, tot = 0;
 		hipMemGetInfo(&fr, &tot);
-		if (fr > hbm_reserve) fr -= hbm_reserve; else fr = 0;     // (lqcov_reserve_hbm: e.g. the part the caller builds while this one is mapped)
-		{	// ... and the survivors of that part's seed plan: as many as this part's, with the head room they grow by
-			const size_t sv = hbm_reserve ? surv.cap + surv.cap / 2 : 0;
-			if (fr > sv) fr -= sv; else fr = 0;
-		}
-		// (0.75 since round 4: a lane's buffers now grow in more steps -- a small first pass, second passes of varying size -- and a
-		// block the stream-ordered pool got back is not always the one the next, larger request can use; at 0.85 the ultra-long
-		// slice of configs[4] ran the device out of memory inside the runtime (HSA_STATUS_ERROR_OUT_OF_RESOURCES))
-		anchor_budget = (u64)((double)fr * 0.75 / 104.0 / n_lanes);
+		anchor_budget = lq_lane_anchor_budget(fr, hbm_reserve, surv.cap, n_lanes);
 	}
-	if (anchor_budget > (1ULL << 31) - 4096) anchor_budget = (1ULL << 31) - 4096;   // (a record names its anchor in 31 bits)
-	if (anchor_budget < 1024) anchor_budget = 1024;
-	while (lanes.size() < (size_t)n_lanes) {
-		add_lane();
-	}
-	{	// every lane's work space (prim.hpp, LqArena): as much as its largest batch of this part can need, taken while the device is
-		// idle -- from the stream-ordered pool (one block, handed back only when the lanes go: plain hipMalloc of tens of gigabytes
-		// takes seconds here, 30 ms per GB measured)
-		size_t need = (size_t)std::min<u64>(anchor_budget, std::max<u64>(nA_total, 1)) * 104 / 9 * 8 + ((size_t)16 << 20);
-#ifdef LQ_EMU
-		need = std::min<size_t>(need, (size_t)64 << 20);            // (the test emulator fills fresh memory with a pattern)
-#endif
-		// (only where the first pass leaves a small part of the hits: a batch whose first pass fills the lane's share by itself --
-		// ultra-long reads keep a third of their hits -- needs its buffers again in the second pass, and pieces of an arena are not
-		// given back: there the lanes allocate buffer by buffer, grow-only, as before)
-		const u64 group_hits = opt && pt.plan.bucketed ? h_aq[pt.plan.q_end] - h_aq[pt.plan.q_begin] : 0;
-		const bool few = opt && pt.plan.bucketed && pt.plan.q_begin == 0 && pt.plan.n_written * 4 <= group_hits;
-		if (!few) for (auto &Lp : lanes) if (Lp->arena.base) { Lp->drop_arena_buffers(); Lp->arena.base = nullptr; Lp->arena.size = 0; Lp->arena_buf.release(); }
-		if (few) for (auto &Lp : lanes) if (Lp->arena.size < need) {
-			Lp->drop_arena_buffers();
-			Lp->arena.base = nullptr; Lp->arena.size = 0; Lp->arena.used = 0;
-			lq_alloc_stream = stream;
-			struct AllocGuard { ~AllocGuard() { lq_alloc_stream = nullptr; } } alloc_guard;
-			try { Lp->arena_buf.ensure(need); Lp->arena.base = Lp->arena_buf.as<char>(); Lp->arena.size = Lp->arena_buf.cap; }
-			catch (const LqOutOfMemory &) { (void)hipGetLastError(); }   // (no room for it in one piece: the lane allocates buffer by buffer)
-		}
-		LQ_HIP_CHECK(hipStreamSynchronize(stream));
-	}
-	{
-		u32 npv = 0;
-		d2h(&npv, n_pv.as<u32>(), 1, stream);
-		pv_reserved = npv;
-		// room for this part's intervals up front: growing the pool later means draining every lane (map_batch)
-		const u64 want = std::min<u64>((u64)npv + nA_total / 16 + 4096, 0xfffffff0ULL);
-		if (want > pv_cap) {
-			grow_keep(pv, (u64)npv * sizeof(Ivl), want * sizeof(Ivl), stream);
-			pv_cap = (u32)std::min<u64>(pv.cap / sizeof(Ivl), 0xfffffff0ULL);
-		}
-	}
-	const bool can_thread =
-#ifndef LQ_EMU
-		profiling != 1 && !dbg;
-#else
-		false;
-#endif
-	// runs the batches on the lanes
-	auto run_batches = [&](const std::vector<std::pair<u32, u32>> &batches) {
-		const bool concurrent = can_thread && n_lanes > 1 && batches.size() > 1;
-		if (!concurrent) {
-			for (size_t i = 0; i < batches.size(); ++i) {
-				map_batch(*lanes[i % n_lanes], pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
-			}
-			for (auto &L : lanes) LQ_HIP_CHECK(hipStreamSynchronize(L->stream));
-			return;
-		}
-		std::atomic<size_t> next(0);
-		{ std::lock_guard<std::mutex> lk(gate_mu); gate_count = 0; }
-		std::vector<std::exception_ptr> errs(n_lanes);
-		std::vector<std::thread> th;
-		for (int li = 0; li < n_lanes; ++li)
-			th.emplace_back([&, li]() {
-				try {
-					LQ_HIP_CHECK(hipSetDevice(device));
-#ifndef LQ_EMU
-					lq_segv_altstack();
-#endif
-					MapLane &L = *lanes[li];
-					// (round 6: the switch that let a lane's buffers grow from HIP's stream-ordered pool -- rounds 2-4's way, under ROCm 7.2 a
-					// GPU memory fault waiting to happen, see DESIGN.md section 2 -- is gone; only the lanes' arenas come from the pool, taken once)
-					{	// staggered start: lane li begins when li batches have got past their sort (or ended), so that
-						// one lane's serial tails run under another lane's wide kernels instead of side by side
-						std::unique_lock<std::mutex> lk(gate_mu);
-						gate_cv.wait(lk, [&] { return gate_count >= li || next.load() >= batches.size(); });
-					}
-					for (;;) {
-						const size_t i = next.fetch_add(1);
-						if (i >= batches.size()) break;
-						map_batch(L, pt, batches[i].first, batches[i].second, h_aq, h_aqf, h_qmoff, dbg);
-					}
-					LQ_HIP_CHECK(hipStreamSynchronize(L.stream));
-				} catch (...) { errs[li] = std::current_exception(); next.store(batches.size()); gate_cv.notify_all(); }
-			});
-		for (auto &t : th) t.join();
-		for (auto &e : errs) if (e) { hipDeviceSynchronize(); std::rethrow_exception(e); }
-	};
-	// as few batches as the work space allows, a multiple of the lane count, of about equal totals of `off` (the anchors the first
-	// pass writes, or the seed hits): every batch has a serial critical path that does not shrink with the batch.  (Cutting the
-	// last round finer was measured on MI355X at configs[2] in round 3: 1.75-1.78 s per step against 1.68-1.70 s; round 4: the
-	// queries in six chunks with the survivors of a chunk decided under the mapping of the chunk before: 1160 ms per step against 888;
-	// round 6: one batch per lane cut by the seed hits, each lane running the filter for its own batch -- see plan_part.)
-	auto cut_batches = [&](const std::vector<u64> &off, u32 g_begin, u32 g_end) {
-		std::vector<std::pair<u32, u32>> batches;
-		const u64 total = off[g_end] - off[g_begin];
-		u64 nb = (total + anchor_budget - 1) / anchor_budget;
-		if (nb < (u64)n_lanes && h_aq[g_end] - h_aq[g_begin] >= ((u64)n_lanes << 24)) nb = n_lanes;   // (by the seed hits, not by what the filter left of them: the second pass works on the hits)
-		if (nb > (u64)n_lanes) nb = (nb + n_lanes - 1) / n_lanes * n_lanes;
-		if (nb == 0) nb = 1;
-		u64 left = nb;
-		for (u32 q0 = g_begin; q0 < g_end; ) {
-			const u64 rem = off[g_end] - off[q0];
-			const u64 lim = std::min(anchor_budget, left > 1 ? (rem + left - 1) / left : rem);
-			u32 q1 = q0 + 1;
-			while (q1 < g_end && off[q1 + 1] - off[q0] <= lim) ++q1;
-			batches.emplace_back(q0, q1);
-			q0 = q1;
-			if (left > 1) --left;
-		}
-		return batches;
-	};
+	anchor_budget = lq_clamp_anchor_budget(anchor_budget);
+	while (lanes.size() < (size_t)n_lanes) add_lane();
+	mp_arenas(pt);
+	mp_pv_room(S.nA_total);
 	bool regrouped = false;
 	// The plan holds the survivors of a group of queries (all of them, unless survivors abound: SeedPlan::q_end); the group's batches
 	// are mapped, then the next group is planned -- with every lane drained, on the handle's own stream.
 	for (u32 g_begin = 0, g_end = n_q; ; ) {
-		if (opt && pt.plan.bucketed) { g_begin = pt.plan.q_begin; g_end = pt.plan.q_end; }
-		run_batches(cut_batches(opt ? h_aqf : h_aq, g_begin, g_end));   // (cut by the anchors the first pass writes)
+		if (opt && S.bucketed) { g_begin = S.q_begin; g_end = S.q_end; }
+		run_batches(pt, lq_cut_batches(opt ? S.h_aqf : S.h_aq, S.h_aq, g_begin, g_end, anchor_budget, n_lanes), dbg);   // (cut by the anchors the first pass writes)
 		if (g_end >= n_q) break;
 		regrouped = true;
-		bool ok = false;
-		try { ok = seed_group(pt, pt.plan, true, stream, prim, g_end); }
-		catch (const LqOutOfMemory &) { (void)hipGetLastError(); seed_ws.release_large(); ok = false; }
-		if (!ok) {                                                  // (no room: the rest of the part without the filter)
-			pt.plan.bucketed = false;
-			pt.plan.h_aqf = pt.plan.h_aq;
-			LQ_HIP_CHECK(hipMemcpyAsync(aqf_off.p, aq_off.p, (n_q + 1) * 8, hipMemcpyDeviceToDevice, stream));
+		if (!seed_group_or_not(pt, S, true, stream, prim, g_end)) {   // (no room: the rest of the part without the filter)
+			rest_unfiltered(S, aqf_off, aq_off, g_end, stream);
 			LQ_HIP_CHECK(hipStreamSynchronize(stream));
-			pt.plan.n_written += h_aq[n_q] - h_aq[g_end];
 			g_begin = g_end; g_end = n_q;
 		}
-		last_n_written = pt.plan.n_written;
+		last_n_written = S.n_written;
 	}
-	if (regrouped) pt.plan.valid = false;                         // (the plan no longer starts at the first query: made again if the part is mapped again)
+	if (regrouped) S.valid = false;                               // (the plan no longer starts at the first query: made again if the part is mapped again)
 	if (dbg) { unsigned long long nd = 0; d2h(&nd, n_dbg.as<unsigned long long>(), 1, stream); n_dbg_host = nd; }
-	sat_replay_part(pt, h_aq, h_qmoff);
+	sat_replay_part(pt, S.h_aq, S.h_qmoff);
 	LQ_HIP_CHECK(hipStreamSynchronize(stream));
 	lq_tl("main", 0, "map_part ends");
 }

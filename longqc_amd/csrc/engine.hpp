@@ -10,6 +10,11 @@
 #include "prim.hpp"
 struct KeyMap;
 struct PsData;
+struct AvaView;
+struct EmitSub;
+struct SeedGeometry;
+struct SeedChunk;
+struct SeedRun;
 #include "../../include/lqcov.h"
 #include <string>
 #include <vector>
@@ -135,6 +140,8 @@ struct Part {
 	u64 n_keys = 0;
 	DBuf self_off, self_rid;              // per query: same-name targets (lqmap.c:180-186)
 	DBuf t_rank, q_lo;                    // -X only: name ranks for strcmp(qname, tname) > 0 (lqmap.c:187)
+	AvaView ava(const lqcov_params &p) const;   // ... as the kernels take them: both null without -X (engine.cpp)
+	u32 max_len() const { u32 m = 0; for (u32 v : rs.h_len) m = std::max(m, v); return m; }   // the longest target
 	// the object is used again for other reads: reads, sketch and index are forgotten, the buffers stay (lqcov_part_clear; run_files' two parts)
 	void clear()
 	{
@@ -382,13 +389,33 @@ struct lqcov_handle {
 	void build_part(Part &pt);
 	void open_gate();
 	void plan_part(Part &pt, hipStream_t s, Prim &pr);
+	// plan_part's steps
+	void pp_probe_marks(Part &pt, hipStream_t s);
+	void pp_survivors(Part &pt, hipStream_t s, Prim &pr);
+	bool seed_group_or_not(Part &pt, SeedPlan &S, bool swapped, hipStream_t s, Prim &pr, u32 q_begin);   // seed_group; false also where it ran out of memory
+	void rest_unfiltered(SeedPlan &S, DBuf &aqf, const DBuf &aq, u32 from, hipStream_t s);                // the queries from `from` on without the filter
 	bool plan_usable(const SeedPlan &S) const;   // the plan was made for these queries, this mid_occ and tie order, and holds its first group of survivors: the part can be mapped from it
 	bool seed_filter(Part &pt, hipStream_t s, Prim &pr, SeedWork &W, u32 n_min, u32 jb, u32 db, SeedJob &J);
 	bool seed_group(Part &pt, SeedPlan &S, bool swapped, hipStream_t s, Prim &pr, u32 q_begin);
+	// seed_filter's steps
+	std::vector<u64> sf_query_hits(hipStream_t s, Prim &pr, SeedWork &W, const SeedJob &J);
+	SeedRun sf_inputs(Part &pt, SeedWork &W, const SeedJob &J, u32 n_min, u32 jb, u32 db);
+	u32 sf_chunk(hipStream_t s, Prim &pr, SeedWork &W, SeedRun &R, const SeedChunk &c);
 	void swap_plan(SeedPlan &S);
 	u64 part_seed_survivors(Part &pt, u32 info[4], u64 *off, u64 off_cap, u32 *rows, u64 row_cap);   // tests: the plan's survivors, decoded (lqcov_part_seed_survivors)
 	void map_part(Part &pt);
+	// map_part's steps
+	void mp_prologue(Part &pt, bool dbg);
+	void mp_arenas(Part &pt);
+	void mp_pv_room(u64 nA_total);
+	void run_batches(Part &pt, const std::vector<std::pair<u32, u32>> &batches, bool dbg);
+	void grow_pv(u32 npv, u64 want_bytes, hipStream_t s);
 	void map_batch(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_aq, const std::vector<u64> &h_aqf, const std::vector<u64> &h_qmoff, bool dbg);
+	// map_batch's steps
+	void mb_emit(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_qmoff, u64 a_base, u64 nA);
+	void mb_first_pass(MapLane &L, Part &pt, u32 q0, u32 q1, const std::vector<u64> &h_off, u64 a_base, u64 nA, u32 ivl_cap, bool dbg);
+	void mb_second_pass(MapLane &L, Part &pt, u32 n_sens, const std::vector<u64> &h_aq, const std::vector<u64> &h_qmoff, u32 ivl_cap, bool dbg);
+	void emit_hits(MapLane &L, Part &pt, dim3 grid, u64 j0, u64 nj, u64 a_base, const u32 *klib, const EmitSub &sub, u64 bytes);
 	void batch_buffers(MapLane &L, u64 nA);
 	void chain_stage(MapLane &L, Part &pt, const u64 *aqb, u64 a_base, u32 nqb, u32 q0, const u32 *qmap, u64 nA, int tie_mode, u32 n_want, u32 ivl_cap, bool dbg, const SatSink *sink = nullptr);
 	void map_subset(MapLane &L, Part &pt, const std::vector<u32> &sq, const std::vector<u32> &sk, const std::vector<u64> &so, u64 max_mini, int tie_mode, u32 n_want, u32 ivl_cap, bool dbg, const SatSink *sink);
@@ -423,6 +450,9 @@ struct lqcov_handle {
 	                                     std::vector<std::string> &&names, std::vector<u32> &&lens);
 	Part &part(int id);
 };
+
+// a part's plan stands in the handle's work buffers (swap_plan) for as long as this lives
+struct PlanGuard { lqcov_handle *h; SeedPlan &S; ~PlanGuard() { h->swap_plan(S); } };
 
 u64 lq_packed_chunks(u32 n, const u64 *seq_off);
 #include <functional>

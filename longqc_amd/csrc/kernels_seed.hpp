@@ -35,6 +35,7 @@
 #pragma once
 #include "lq_common.hpp"
 #include "kernels_index.hpp"
+#include "seed_geom.hpp"
 
 #ifndef LQ_SD_SEGL
 #define LQ_SD_SEGL 256u                     // most minimizers of a segment (their hit offsets sit in LDS)
@@ -47,9 +48,6 @@
 #define LQ_SD_RPT 8                         // hits per thread and tile of the count / scatter kernels
 #endif
 #define LQ_SD_TILE (LQ_SD_THREADS * LQ_SD_RPT)
-#define LQ_SD_SL_SMALL 512u                 // slices per query: the two shapes of the scatter kernel
-#define LQ_SD_SL_BIG 2048u
-
 // record = rid << (jb + db + 1) | relative strand << (jb + db) | diagonal << jb | minimizer (index inside its query)
 struct SeedBits { u32 jb, db; };
 __device__ __forceinline__ u32 sd_rid(u64 r, SeedBits b) { return (u32)(r >> (b.jb + b.db + 1)); }
@@ -57,11 +55,7 @@ __device__ __forceinline__ u32 sd_rs(u64 r, SeedBits b) { return (u32)(r >> (b.j
 __device__ __forceinline__ u32 sd_diag(u64 r, SeedBits b) { return (u32)(r >> b.jb) & ((1u << b.db) - 1u); }
 __device__ __forceinline__ u32 sd_jl(u64 r, SeedBits b) { return (u32)r & ((1u << b.jb) - 1u); }
 
-// a query's slices of targets: slice of rid = (rid * mul) >> 32, monotone, below nsl for every rid of the part
-// (mul = floor(2^32 * nsl / n_targets)); a segment = minimizers [j0, j1) of one query; cb: the query's first entry in the
-// chunk's piece table, laid out [slice][segment]
-struct alignas(16) SeedQ { u32 mul, nsl, nseg, seg0; u64 cb; u64 bk; };   // bk: the query's first bucket in the chunk
-struct alignas(16) SeedSeg { u64 j0, j1; u32 q, ord; u32 pad0, pad1; };  // ord: the segment's number inside its query
+// SeedQ, SeedSeg and the slice counts LQ_SD_SL_SMALL / LQ_SD_SL_BIG: seed_geom.hpp (the host fills them: mapplan.hpp)
 __device__ __forceinline__ u32 sd_slice(u32 rid, u32 mul) { return (u32)(((u64)rid * mul) >> 32); }
 // first rid of slice s (the smallest rid with sd_slice(rid) == s)
 __device__ __forceinline__ u32 sd_slice_first(u32 s, u32 mul) { return s == 0 ? 0u : (u32)((((u64)s << 32) + mul - 1) / mul); }
